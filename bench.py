@@ -31,7 +31,19 @@ within SKGE_BENCH_DP_TIMEOUT seconds ends the job with a non-zero status
 (skge_amd.dp.dp_epoch with a NumPy rank compute, gloo) and the
 max-over-ranks bookkeeping on CPU, no GPU (tests/test_bench_dist.py).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--nb 100]
+A plain run sets up, warms up, times the K steps and prints the line: value,
+ms_per_step and what they were measured on; roofline, cpu_baseline and the
+detail measurements are null.  `--full` adds everything that takes runs of
+its own: the per-kernel profile and roofline, the measured gather roofline,
+the CPU baseline (oracle sample), the large-batch line, the hand-off probe,
+and at N > 1 the one-GPU / other-batch / independent-jobs comparisons.
+`--dump-outputs DIR` (configs 1-4) writes the tables the timed steps left
+(parameters, AdaGrad state, violation count) as DIR/<name>.npy, at most
+64 MB in all (larger tables: a fixed seeded sample of their elements); the
+inputs are seeded, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--nb 100] [--full]
+                       [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -329,6 +341,53 @@ def handoff_probe(dev, rounds=2000, reps=3):
                     "blocks 0/1 (round-robin: different XCDs), idle chip, best of %d" % reps}
 
 
+DUMP_BUDGET = 64_000_000   # bytes of --dump-outputs files in all
+
+
+def model_outputs(model, upd, nviol):
+    """What a caller of the timed path holds after its last step: the model's
+    tables, the updaters' state (AdaGrad's sums of squares) and the violation
+    count of the timed steps, as host arrays."""
+    out = {}
+    for pid, p in model.params.items():
+        out[pid] = p.data.detach().cpu().numpy()
+        p2 = getattr(upd[pid], "p2", None)
+        if p2 is not None:
+            out[pid + "_adagrad_p2"] = p2.detach().cpu().numpy()
+    out["nviol"] = np.array([nviol], dtype=np.float64)
+    return out
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: write {name: array} as dirname/<name>.npy (float32 or
+    float64).  Past `budget` bytes in all, the arrays above an equal share of
+    it are cut to a fixed sample of their flattened elements (RandomState(0),
+    sorted positions: the same positions in every run), the others whole."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    if sum(a.nbytes for a in arrs.values()) > budget:
+        big = sorted(arrs, key=lambda n: arrs[n].nbytes, reverse=True)
+        left = budget - sum(a.nbytes for a in arrs.values())
+        cut = []
+        # cut the largest arrays to an equal share of what the others leave
+        while left < 0 or (len(cut) < len(big) and
+                           left // len(cut) < arrs[big[len(cut)]].nbytes):
+            n = big[len(cut)]
+            cut.append(n)
+            left += arrs[n].nbytes
+        share = max(left, 0) // len(cut)
+        rs = np.random.RandomState(0)
+        for n in cut:
+            flat = arrs[n].reshape(-1)
+            keep = np.sort(rs.choice(flat.size, size=share // flat.itemsize, replace=False))
+            arrs[n] = flat[keep]
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def algorithmic_bytes(d, B, P, U_E, U_R, opt_k=12):
     """BYTES(batch) = 4d(3B + P) + k d (U_E + U_R) + 20B."""
     return 4 * d * (3 * B + P) + opt_k * d * (U_E + U_R) + 20 * B
@@ -459,11 +518,22 @@ def main():
                          "(union batch N x 1414, nb = nb / N: a larger batch, weak scaling)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only: the multi-rank launcher and bookkeeping over gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure (off by default): "
+                         "the CPU baseline, the per-kernel profile and roofline, the measured "
+                         "gather roofline, the large-batch line, the hand-off probe; at N > 1 "
+                         "the one-GPU, other-batch and independent-jobs comparisons")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="configs 1-4: after the timed steps write the tables the timed path "
+                         "left (parameters, updater state, violation count) as DIR/<name>.npy")
     ap.add_argument("--shard", action="store_true",
                     help="config 5 only: row-shard E and its AdaGrad state over the ranks "
                          "(skge_amd.shard; RCCL all-to-all row fetch + contribution "
                          "reduce-scatter, relation sums all-reduced) instead of replicas")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures its headline figure only
+        args.no_cpu, args.no_roofline, args.large_nb = True, True, 0
     if args.config == 1:
         # BASELINE configs[0]: TransE on WN18, ncomp=50, nb=100, margin 2.0, SGD
         # (run_transe_wn18.sh:3-5 / run_transe.py; the reference CLI itself
@@ -479,6 +549,10 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (launch N ranks with --gpus N)"
                          % (args.gpus, world))
+    if args.dump_outputs and (args.dry_run or args.config == 5 or
+                              (world > 1 and args.mode != "replicas")):
+        raise SystemExit("bench.py: --dump-outputs covers configs 1-4 on one GPU (or --mode "
+                         "replicas: rank 0's model), not --dry-run, config 5 or data parallel")
     if args.dry_run:
         return run_dry(args)
     if args.config == 5 and (args.shard or (world > 1 and args.mode != "replicas")):
@@ -543,21 +617,25 @@ def main():
     positives = N_TRIPLES * args.steps
     value = replica_value(positives, world, elapsed)
     rank_value = positives / (t1 - t0)      # this replica alone
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model_outputs(model, upd, nviol))
 
-    # ---- per-kernel timing (HIP events on the runner stream, eager launches of
-    # one more epoch, outside the timed region) for the roofline.  The tables
-    # are rolled back to the initial state first, so the profiled epoch does
-    # the same work as the timed region's first epoch ----
-    for pid, p in model.params.items():
-        p.data.copy_(init[pid])
-        upd[pid].reset()
-    torch.cuda.synchronize()
+    # ---- --full: per-kernel timing (HIP events on the runner stream, eager
+    # launches of one more epoch, outside the timed region) for the roofline.
+    # The tables are rolled back to the initial state first, so the profiled
+    # epoch does the same work as the timed region's first epoch ----
     opt_k = 4 if args.opt == "sgd" else 12     # k = 4 (SGD) / 12 (AdaGrad)
-    prof = pipe_profile(runner, kg, nb, d, epochs=args.steps,
-                        gpu_ms_per_epoch=gpu_ms / args.steps, opt_k=opt_k) if runner.pipelined else \
-        kernel_profile(model, upd, kg, nb, d, st, runner, opt_k=opt_k)
+    prof = None
+    if args.full:
+        for pid, p in model.params.items():
+            p.data.copy_(init[pid])
+            upd[pid].reset()
+        torch.cuda.synchronize()
+        prof = pipe_profile(runner, kg, nb, d, epochs=args.steps,
+                            gpu_ms_per_epoch=gpu_ms / args.steps, opt_k=opt_k) if runner.pipelined \
+            else kernel_profile(model, upd, kg, nb, d, st, runner, opt_k=opt_k)
     meas = None
-    if runner.pipelined and not args.no_roofline:
+    if prof is not None and runner.pipelined and not args.no_roofline:
         # the same per-launch row traffic without the path's
         # dependencies, and the streaming random-row gather rate of the table
         geo = prof["geometry"]
@@ -637,22 +715,40 @@ def main():
                  "runner": "pipelined" if r2.pipelined else "two-launch"}
         del r2
 
-    probe = handoff_probe(dev) if runner.pipelined else None
+    probe = handoff_probe(dev) if (args.full and runner.pipelined) else None
     pipelined, nlaunches = runner.pipelined, runner.nlaunches
     hot_rows = getattr(runner, "hot_rows", 0)
     acc_names = {"entity": acc_label(runner.accE), "relation": acc_label(runner.accR)}
-    launch_us_max = max_over_ranks(prof["dominant"]["avg_us"], world, dev)
+    launch_us_max = None if prof is None else \
+        max_over_ranks(prof["dominant"]["avg_us"], world, dev)
     line = None
     if rank == 0:
         # the CPU baseline on rank 0 at N = 1 only (the bench contract)
         cpu = None if (args.no_cpu or world > 1) else cpu_baseline(trip, d, nb, args.cpu_seconds,
                                                                    opt=args.opt)
-        k = prof["dominant"]
-        kname = {"transe_sample_grad": "sample_grad", "accum_apply": "k_apply",
-                 "pipe_batch": "k_pipe_batch", "pipe_fused": "k_pipe_fused"}[k["name"]]
-        # config 1's own PMC pass (pmc_c1.json: d=50 padded to 64, SGD), not config 2's
-        traffic, traffic_src = pmc_traffic(kname, "pmc.json" if args.config == 2 else
-                                           "pmc_c%d.json" % args.config)
+        roofline = None      # --full only: it takes the profiled epochs
+        if prof is not None:
+            k = prof["dominant"]
+            kname = {"transe_sample_grad": "sample_grad", "accum_apply": "k_apply",
+                     "pipe_batch": "k_pipe_batch", "pipe_fused": "k_pipe_fused"}[k["name"]]
+            # config 1's own PMC pass (pmc_c1.json: d=50 padded to 64, SGD), not config 2's
+            traffic, traffic_src = pmc_traffic(kname, "pmc.json" if args.config == 2 else
+                                               "pmc_c%d.json" % args.config)
+            roofline = {"bound": "hbm", "kernel": k["name"],
+                        "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
+                        "traffic": None if traffic is None else round(traffic),
+                        "traffic_source": traffic_src,
+                        "bytes_per_launch": round(k["bytes_per_launch"]),
+                        "bytes_formula": prof.get("formula"),
+                        "impl_bytes_per_launch": round(k.get("impl_bytes_per_launch",
+                                                             k["bytes_per_launch"])),
+                        "avg_launch_us": round(k["avg_us"], 3),
+                        "avg_launch_source": "timed-region HIP events (graph replays) minus "
+                                             "the draw/advance launches, per batch launch",
+                        "eager_avg_launch_us": round(k.get("eager_avg_us", k["avg_us"]), 3),
+                        "avg_launch_us_max_over_ranks": round(launch_us_max, 3),
+                        "measured": meas}
         line = {
             "metric": ("triples/sec (score+grad+update), WN18 TransE d=200, 1/2/4/8 MI355X"
                        if args.config == 2 else
@@ -685,23 +781,10 @@ def main():
                        "global_batch": N_TRIPLES // nb,
                        "parallelism": parallelism_label("replicas%d" % world, info)
                        if world > 1 else "1gpu"},
-            "roofline": {"bound": "hbm", "kernel": k["name"],
-                         "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
-                         "traffic": None if traffic is None else round(traffic),
-                         "traffic_source": traffic_src,
-                         "bytes_per_launch": round(k["bytes_per_launch"]),
-                         "bytes_formula": prof.get("formula"),
-                         "impl_bytes_per_launch": round(k.get("impl_bytes_per_launch",
-                                                              k["bytes_per_launch"])),
-                         "avg_launch_us": round(k["avg_us"], 3),
-                         "avg_launch_source": "timed-region HIP events (graph replays) minus "
-                                              "the draw/advance launches, per batch launch",
-                         "eager_avg_launch_us": round(k.get("eager_avg_us", k["avg_us"]), 3),
-                         "avg_launch_us_max_over_ranks": round(launch_us_max, 3),
-                         "measured": meas},
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "detail": {
+                "full": args.full,   # False: roofline, cpu_baseline, kernels, ... not measured
                 "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4),
                 # 2 pairs per positive (RandomModeSampler modes [0, 1]; on
                 # this sparse KG a negative is always found), the positive re-scored
@@ -709,10 +792,12 @@ def main():
                 "pairs_per_s": round(2.0 * value, 1),
                 "scored_triples_per_s": round(4.0 * value, 1),
                 "violations_per_pair": round(nviol / (2.0 * positives), 4),
-                "kernels": {n: {"avg_us": round(v["avg_us"], 3), "launches": v["launches"],
+                "kernels": None if prof is None else
+                           {n: {"avg_us": round(v["avg_us"], 3), "launches": v["launches"],
                                 "GB_s": round(v["achieved_gbs"], 1)}
                             for n, v in prof["kernels"].items()},
-                "step_algorithmic_GB_s": round(prof["epoch_bytes"] / (elapsed / args.steps) / 1e9, 1),
+                "step_algorithmic_GB_s": None if prof is None else
+                round(prof["epoch_bytes"] / (elapsed / args.steps) / 1e9, 1),
                 "launches_per_step": nlaunches,
                 "runner": "pipelined (1 launch/batch)" if pipelined else "two-launch",
                 "accumulator": acc_names,
@@ -988,7 +1073,8 @@ def run_dp(args):
     if rank == 0:
         skel = dp_line(args, world, {"value": None, "ms_per_step": None, "union_batch": bs,
                                      "per_gpu_batch": -(-bs // world)}, None, nb=nb, info=info)
-    m = run_with_watchdog(lambda: measure_dp(args, dev, nb, args.warmup, args.steps), skel, limit)
+    m = run_with_watchdog(lambda: measure_dp(args, dev, nb, args.warmup, args.steps,
+                                             profile=args.full), skel, limit)
     if failed(m):
         if rank == 0:
             mark_failure(skel, None, m)
@@ -1017,8 +1103,10 @@ def run_dp(args):
             "value": round(replica_value(N_TRIPLES * ind["epochs"], world, el), 1),
             "nb": args.nb, "ms_per_step": round(1000.0 * el / ind["epochs"], 4)}
         return out
-    det = run_with_watchdog(details, line, limit, key="details")
+    # the comparisons are measurements of their own: --full only
+    det = run_with_watchdog(details, line, limit, key="details") if args.full else {}
     if rank == 0:
+        line["detail"]["full"] = args.full
         if failed(det):
             mark_failure(line, "details", det)
         else:
@@ -1303,7 +1391,7 @@ def run_config5(args):
         dist.barrier()
     elapsed = max_over_ranks(elapsed, world, dev)
     counter_cost = None
-    if prof is not None and not args.c5_no_counter_split:
+    if args.full and prof is not None and not args.c5_no_counter_split:
         # the counters' price at the same epochs: the next epoch's even batches
         # count their rows, the odd ones do not
         _, alt = eager_epochs(runner, kg, nb, d, 1, counters="alt")
@@ -1316,18 +1404,37 @@ def run_config5(args):
                     "8(d) bytes), odd batches without"}
     value = replica_value(T * args.steps, world, elapsed)
     prof_epochs = args.steps
-    if prof is None:
+    if prof is None and args.full:
         # the pipelined runner: the batch launch's time from the timed region's
         # epoch time minus the other kernels (as config 2), counters from one
         # more eager epoch
         prof = pipe_profile(runner, kg, nb, d, gpu_ms_per_epoch=1000.0 * elapsed / args.steps)
         prof_epochs = 1
-    k = prof["dominant"]
     if rank == 0:
-        traffic, traffic_src = pmc_traffic_epochs(PMC_KERNEL.get(k["name"], k["name"]),
-                                                  "pmc_c5_epochs.json", args.warmup, args.steps)
-        if traffic is None:
-            traffic, traffic_src = pmc_traffic(PMC_KERNEL.get(k["name"], k["name"]), "pmc_c5.json")
+        roofline = kernels = kernels_ms = None   # pipelined runner without --full: no profile
+        if prof is not None:
+            k = prof["dominant"]
+            traffic, traffic_src = pmc_traffic_epochs(PMC_KERNEL.get(k["name"], k["name"]),
+                                                      "pmc_c5_epochs.json", args.warmup, args.steps)
+            if traffic is None:
+                traffic, traffic_src = pmc_traffic(PMC_KERNEL.get(k["name"], k["name"]),
+                                                   "pmc_c5.json")
+            roofline = {"bound": "hbm", "kernel": k["name"],
+                        "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
+                        "traffic": None if traffic is None else round(traffic),
+                        "traffic_source": traffic_src,
+                        "bytes_per_launch": round(k["bytes_per_launch"]),
+                        "avg_launch_us": round(k["avg_us"], 3),
+                        "avg_launch_source": prof.get("source"),
+                        "bytes_formula": prof.get("formula")}
+            kernels = {n: {"avg_us": round(v["avg_us"], 3), "launches": v["launches"],
+                           "GB_s": round(v["achieved_gbs"], 1)}
+                       for n, v in prof["kernels"].items()}
+            # the kernels' device time per step (<= ms_per_step: the rest is
+            # launch gaps)
+            kernels_ms = round(sum(v["avg_us"] * v["launches"] for v in prof["kernels"].values()
+                                   if v["launches"] > 1) / 1000.0 / prof_epochs, 3)
         line = {
             "metric": "triples/sec (score+grad+update), synthetic TransE |E|=50M |R|=10k d=512, "
                       "B=131072 per GPU (BASELINE configs[4])" +
@@ -1344,18 +1451,11 @@ def run_config5(args):
                                    "%d batches" % (d, nb),
                        "global_batch": T // nb * world,
                        "parallelism": "replicas%d" % world if world > 1 else "1gpu"},
-            "roofline": {"bound": "hbm", "kernel": k["name"],
-                         "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
-                         "traffic": None if traffic is None else round(traffic),
-                         "traffic_source": traffic_src,
-                         "bytes_per_launch": round(k["bytes_per_launch"]),
-                         "avg_launch_us": round(k["avg_us"], 3),
-                         "avg_launch_source": prof.get("source"),
-                         "bytes_formula": prof.get("formula")},
+            "roofline": roofline,
             "cpu_baseline": None if (args.no_cpu or world > 1) else
                             cpu_baseline_config5(args.cpu_seconds),   # N = 1 only
-            "detail": {"runner": "pipelined" if runner.pipelined else "two-launch",
+            "detail": {"full": args.full,
+                       "runner": "pipelined" if runner.pipelined else "two-launch",
                        "timed_epochs": ("epochs %d..%d (after %d warm-up epochs), replays of "
                                         "the epoch graph; the per-kernel detail from one more "
                                         "eager epoch" if runner.pipelined else
@@ -1368,15 +1468,8 @@ def run_config5(args):
                        "accumulator": {"entity": acc_label(runner.accE),
                                        "relation": acc_label(runner.accR)},
                        "build_s": round(t_build, 1),
-                       "kernels": {n: {"avg_us": round(v["avg_us"], 3), "launches": v["launches"],
-                                       "GB_s": round(v["achieved_gbs"], 1)}
-                                   for n, v in prof["kernels"].items()},
-                       # the kernels' device time per step (<= ms_per_step: the
-                       # rest is launch gaps)
-                       "kernels_ms_per_step": round(sum(v["avg_us"] * v["launches"]
-                                                        for v in prof["kernels"].values()
-                                                        if v["launches"] > 1)
-                                                    / 1000.0 / prof_epochs, 3),
+                       "kernels": kernels,
+                       "kernels_ms_per_step": kernels_ms,
                        "gpu_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)},
         }
         print(json.dumps(line), flush=True)
@@ -1517,10 +1610,20 @@ def run_config5_sharded(args):
         dist.barrier()
     elapsed = max_over_ranks(elapsed, world, dev)
     value = T * args.steps / elapsed
-    prof = shard_profile(runner, d)
+    prof = shard_profile(runner, d) if args.full else None   # (its own eager batches)
     nviol = int(runner.nviol_total.item())
     if rank == 0:
-        k = prof["dominant"]
+        roofline = phases = kernels = None
+        if prof is not None:
+            k = prof["dominant"]
+            roofline = {"bound": "hbm", "kernel": k["name"],
+                        "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
+                        "traffic": None, "bytes_per_launch": round(k["bytes_per_launch"]),
+                        "avg_launch_us": round(k["avg_us"], 3)}
+            phases = {n: round(v, 4) for n, v in prof["phases_ms"].items()}
+            kernels = {n: {"avg_us": round(v["avg_us"], 3), "GB_s": round(v["achieved_gbs"], 1)}
+                       for n, v in prof["kernels"].items()}
         line = {
             "metric": "triples/sec (score+grad+update), synthetic TransE |E|=50M |R|=10k d=512, "
                       "table row-sharded over the GPUs (BASELINE configs[4])",
@@ -1535,22 +1638,16 @@ def run_config5_sharded(args):
                                    "row-sharded (row %% G), R replicated; step = 1 epoch of %d "
                                    "batches of %d positives per rank" % (d, len(runner.batches), B5),
                        "global_batch": B5 * world, "parallelism": "rowshard%d" % world},
-            "roofline": {"bound": "hbm", "kernel": k["name"],
-                         "achieved": round(k["achieved_gbs"], 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(k["achieved_gbs"] / HBM_PEAK_GBS, 4),
-                         "traffic": None, "bytes_per_launch": round(k["bytes_per_launch"]),
-                         "avg_launch_us": round(k["avg_us"], 3)},
+            "roofline": roofline,
             "cpu_baseline": None if (args.no_cpu or world > 1) else
                             cpu_baseline_config5(args.cpu_seconds),   # N = 1 only
-            "detail": {"runner": "row-sharded (skge_amd.shard)",
+            "detail": {"full": args.full, "runner": "row-sharded (skge_amd.shard)",
                        "bucket_capacity": runner.C,
                        "captured_graph": runner.graph is not None,
                        "build_s": round(t_build, 1),
                        "violations_per_pair": round(nviol / (2.0 * T_r * (args.warmup + args.steps)), 4),
-                       "phases_ms_per_batch": {n: round(v, 4) for n, v in prof["phases_ms"].items()},
-                       "kernels": {n: {"avg_us": round(v["avg_us"], 3),
-                                       "GB_s": round(v["achieved_gbs"], 1)}
-                                   for n, v in prof["kernels"].items()},
+                       "phases_ms_per_batch": phases,
+                       "kernels": kernels,
                        "gpu_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)},
         }
         print(json.dumps(line), flush=True)
@@ -1696,8 +1793,10 @@ def run_config34(args):
     tfs = flops / elapsed / 1e12 * world
     nl = runner.nlaunches
     rname = type(runner).__name__
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model_outputs(model, upd, V))
     prof = None
-    if kind == "hole" and getattr(runner, "pipelined", False):
+    if args.full and kind == "hole" and getattr(runner, "pipelined", False):
         # the pipelined HolE runner's own counters over one more (eager) epoch;
         # the batch launches' time from the timed region's wall clock per epoch
         prof = pipe_profile(runner, kg, nb, d, gpu_ms_per_epoch=1000.0 * elapsed / args.steps,
@@ -1752,7 +1851,8 @@ def run_config34(args):
                                       margin, nb, N_TRIPLES // nb),
                        "global_batch": N_TRIPLES // nb,
                        "parallelism": "replicas%d" % world if world > 1 else "1gpu"},
-            "roofline": ({"bound": "hbm", "kernel": "k_hole_pipe",
+            "roofline": None if not args.full else   # (with the profile and the PMC lookup)
+                        ({"bound": "hbm", "kernel": "k_hole_pipe",
                           "achieved": round(prof["dominant"]["achieved_gbs"], 1),
                           "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": round(prof["dominant"]["achieved_gbs"] / HBM_PEAK_GBS, 4),
@@ -1771,7 +1871,8 @@ def run_config34(args):
                           "traffic": None if traffic is None else round(traffic),
                           "traffic_kernel": tkern, "traffic_source": traffic_src}),
             "cpu_baseline": cpu,
-            "detail": {"violations_per_pair": round(V / float(P), 4),
+            "detail": {"full": args.full,
+                       "violations_per_pair": round(V / float(P), 4),
                        "direct_form_TFLOP_s": round(tfs, 2),   # model_flops at the timed rate
                        "graph_nodes_per_step": nl,
                        "runner": rname,

@@ -6,14 +6,15 @@
 # measured first and last as "base" / "base2".
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
-timeout -k 10 600 bash tools/ablate.sh "$@" > gpurun_out/ab_lib_build.log 2>&1 || { tail -5 gpurun_out/ab_lib_build.log; exit 1; }
+export OUT=${OUT:-bench_out}   # logs
+mkdir -p "$OUT"
+timeout -k 10 600 bash tools/ablate.sh "$@" > "$OUT/ab_lib_build.log" 2>&1 || { tail -5 "$OUT/ab_lib_build.log"; exit 1; }
 one() {  # name libpath benchargs
   local n=$1 lp=$2 ba=$3
-  env ${lp:+SKGE_LIB_PATH=$lp} timeout -k 10 200 python bench.py --steps 10 --warmup 2 --no-cpu --no-roofline --large-nb 0 $ba > gpurun_out/ablib_$n.log 2>&1 || return 1
+  env ${lp:+SKGE_LIB_PATH=$lp} timeout -k 10 200 python bench.py --full --steps 10 --warmup 2 --no-cpu --no-roofline --large-nb 0 $ba > "$OUT/ablib_$n.log" 2>&1 || return 1
   python3 - "$n" "$ba" <<'PY'
-import json,sys; n=sys.argv[1]
-l=[x for x in open("gpurun_out/ablib_%s.log" % n) if x.startswith("{")][0]; j=json.loads(l)
+import json,os,sys; n=sys.argv[1]
+l=[x for x in open(os.path.join(os.environ["OUT"], "ablib_%s.log" % n)) if x.startswith("{")][0]; j=json.loads(l)
 hp = (j.get("detail") or {}).get("handoff_probe") or {}
 print(n, "[%s]" % sys.argv[2], round(j["value"]/1e6,2), j["ms_per_step"], j["roofline"].get("avg_launch_us"), j["roofline"].get("frac"), "hop_us", hp.get("us_per_hop"))
 PY

@@ -43,27 +43,27 @@ for st in ${STEPS:-tests smoke bench}; do
     smoke)
       run ${TAG}_smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
     bench)
-      run ${TAG}_bench$n ${TBENCH:-600} python bench.py ${arg:---steps 20 --warmup 3} || exit $?
+      run ${TAG}_bench$n ${TBENCH:-600} python bench.py --full ${arg:---steps 20 --warmup 3} || exit $?
       grep '^{' gpurun_out/${TAG}_bench$n.log > gpurun_out/${TAG}_bench$n.json ;;
     stats)
       D=gpurun_out/${TAG}_stats$n
       run ${TAG}_stats$n 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $D -o run \
-        -- python3 bench.py ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
+        -- python3 bench.py --full ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
       grep '^{' gpurun_out/${TAG}_stats$n.log > $D/bench_under_rocprof.json ;;
     pmc)
       D=gpurun_out/${TAG}_pmc$n
       run ${TAG}_pmcs$n 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $D/stats -o run \
-        -- python3 bench.py ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
+        -- python3 bench.py --full ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
       grep '^{' gpurun_out/${TAG}_pmcs$n.log > $D/bench_under_rocprof.json
       run ${TAG}_pmcf$n 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -T --output-format csv \
-        -d $D/fetch -o run -- python3 bench.py ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
+        -d $D/fetch -o run -- python3 bench.py --full ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
       run ${TAG}_pmcw$n 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -T --output-format csv \
-        -d $D/write -o run -- python3 bench.py ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
+        -d $D/write -o run -- python3 bench.py --full ${arg:---steps 20 --warmup 3 --no-cpu} || exit $?
       python3 tools/pmc_summary.py $D > $D/pmc.json && echo "pmc summary: $D/pmc.json" ;;
     pmcx)   # one --pmc pass of the counters in $PMCX (space separated) over a bench command
       D=gpurun_out/${TAG}_pmcx$n
       run ${TAG}_pmcx$n 300 rocprofv3 --pmc ${PMCX:-SQ_WAVES SQ_WAVE_CYCLES} --kernel-trace -T \
-        --output-format csv -d $D -o run -- python3 bench.py ${arg:---steps 5 --warmup 2 --no-cpu} || exit $?
+        --output-format csv -d $D -o run -- python3 bench.py --full ${arg:---steps 5 --warmup 2 --no-cpu} || exit $?
       python3 tools/pmc_counters.py $D > $D/pmc_counters.json && echo "pmc counters: $D/pmc_counters.json" ;;
     tool)   # tool:<script under tools/>,<args>  (python scripts and .sh drivers)
       set -- $arg
