@@ -82,7 +82,8 @@ __device__ __forceinline__ float af_g_given_f(int af, float fx) {
 // correctly rounded sequences).  Their gradients are exact small-integer sums
 // over the count (the mean itself stays correctly rounded), so H >= 1/32767
 // and the step's relative error stays ~1e-7: far inside the 1e-5 parity bar.
-// Shared by every packed apply (row_update, i16_finish): bitwise the same.
+// Shared by every packed apply (row_update_s in skge_row_update.h,
+// apply_row_rep_block in skge_update.hip): bitwise the same.
 __device__ __forceinline__ float adagrad_step_fast(float lr, float g, float a) {
   return (lr * g) * __builtin_amdgcn_rcpf(fmaxf(__builtin_amdgcn_sqrtf(a), 1e-7f));
 }

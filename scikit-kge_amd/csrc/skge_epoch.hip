@@ -12,6 +12,7 @@
 
 #include "skge_host.h"
 #include "skge_sampler.h"
+#include "skge_transe_l1.h"
 
 namespace skge {
 
@@ -232,33 +233,11 @@ __device__ __forceinline__ PosL1 transe_l1_front(const SampleArgs& a, const Perm
     if (neg0 >= 0 && neg0 != cand0) load_row4<KQ>(a.E, neg0, d, fs);
     if (neg1 >= 0 && neg1 != cand1) load_row4<KQ>(a.E, neg1, d, fo);
   }
-  float ps = 0.0f, n0 = 0.0f, n1 = 0.0f;
-#pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-#define SKGE_EL(X)                                                                    \
-  {                                                                                   \
-    const float vp = (es[m].X + rp[m].X) - eo[m].X;   /* transe.py:32 */              \
-    const float v0 = (fs[m].X + rp[m].X) - eo[m].X;                                   \
-    const float v1 = (es[m].X + rp[m].X) - fo[m].X;                                   \
-    ps += fabsf(vp);                                                                  \
-    n0 += fabsf(v0);                                                                  \
-    n1 += fabsf(v1);                                                                  \
-    gp[m].X = signf_np(-((eo[m].X - rp[m].X) - es[m].X)); /* transe.py:103,115 */     \
-    g0[m].X = signf_np((eo[m].X - rp[m].X) - fs[m].X);    /* transe.py:104,117 */     \
-    g1[m].X = signf_np((fo[m].X - rp[m].X) - es[m].X);                                \
-  }
-    SKGE_EL(x)
-    SKGE_EL(y)
-    SKGE_EL(z)
-    SKGE_EL(w)
-#undef SKGE_EL
-  }
-  const float pscore = -wave_sum(ps);
-  const float ns0 = -wave_sum(n0), ns1 = -wave_sum(n1);
+  float ps, n0, n1;
+  l1_scores_signs<KQ>(es, eo, fs, fo, rp, ps, n0, n1, gp, g0, g1);
   r.neg0 = neg0;
   r.neg1 = neg1;
-  r.v0 = (neg0 >= 0 && ns0 + a.margin > pscore) ? 1 : 0;   // strict >, transe.py:73
-  r.v1 = (neg1 >= 0 && ns1 + a.margin > pscore) ? 1 : 0;
+  l1_decide(ps, n0, n1, neg0, neg1, a.margin, r.v0, r.v1);
   return r;
 }
 
@@ -284,22 +263,11 @@ __device__ __forceinline__ void transe_l1_commit(const SampleArgs& a, long long 
     }
   }
   if (v0 + v1 == 0) return;
-  const float fv0 = (float)v0, fv1 = (float)v1;
   float4 cs[KQ], co[KQ], c0[KQ], c1[KQ], cr[KQ];
+  const float fv0 = (float)v0, fv1 = (float)v1;
 #pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-#define SKGE_CO(X)                                                   \
-  cs[m].X = fv0 * gp[m].X + fv1 * (gp[m].X + g1[m].X);               \
-  co[m].X = -(fv0 * (gp[m].X + g0[m].X) + fv1 * gp[m].X);            \
-  c0[m].X = g0[m].X;                                                 \
-  c1[m].X = -g1[m].X;                                                \
-  cr[m].X = fv0 * (gp[m].X + g0[m].X) + fv1 * (gp[m].X + g1[m].X);
-    SKGE_CO(x)
-    SKGE_CO(y)
-    SKGE_CO(z)
-    SKGE_CO(w)
-#undef SKGE_CO
-  }
+  for (int m = 0; m < KQ; ++m)
+    l1_contrib(fv0, fv1, gp[m], g0[m], g1[m], cs[m], co[m], c0[m], c1[m], cr[m]);
   acc_row4_i16<KQ>(a.accE, r.s, cs, d);
   acc_row4_i16<KQ>(a.accE, r.o, co, d);
   if (v0) acc_row4_i16<KQ>(a.accE, r.neg0, c0, d);

@@ -24,48 +24,13 @@ namespace skge {
 // (their correlations are the launch's long pole): the apply waves then run
 // beside them.
 
-// One row's update from fp32 sums (zero past the row); row_update's arithmetic
+// One row's update from fp32 sums (zero past the row): the shared row update
+// (skge_row_update.h) with correctly rounded divides and square roots
 template <int KQ>
 __device__ __forceinline__ void row_update_f(const UpdParams& t, int c, int d,
                                              const float4 (&sm)[KQ], float4 (&p)[KQ],
                                              float4 (&a)[KQ]) {
-  const int l = lane_id(), nq = d >> 2;
-  const bool ada = t.opt == OPT_ADAGRAD;
-  const float div = t.fdiv > 0.0f ? t.fdiv : (float)c;
-  float ss = 0.0f;
-#pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-    const bool in = 64 * m + l < nq;
-#define SKGE_UP(X)                                                      \
-  {                                                                     \
-    const float g = (sm[m].X + t.rin * p[m].X) / div + t.rout * p[m].X; \
-    float pv = p[m].X;                                                  \
-    if (ada) {                                                          \
-      a[m].X = a[m].X + g * g;                        /* param.py:147 */\
-      pv = pv - (t.lr * g) / fmaxf(sqrtf(a[m].X), 1e-7f); /* 152-155 */ \
-    } else {                                                            \
-      pv = pv - t.lr * g;                             /* param.py:130 */\
-    }                                                                   \
-    p[m].X = in ? pv : 0.0f;                                            \
-    ss += p[m].X * p[m].X;                                              \
-  }
-    SKGE_UP(x)
-    SKGE_UP(y)
-    SKGE_UP(z)
-    SKGE_UP(w)
-#undef SKGE_UP
-  }
-  if (t.post != POST_NONE) {
-    ss = wave_sum(ss);
-    const float nrm = t.post == POST_NORMALIZE ? sqrtf(ss) : (ss < 1.0f ? 1.0f : ss);
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-      p[m].x = p[m].x / nrm;
-      p[m].y = p[m].y / nrm;
-      p[m].z = p[m].z / nrm;
-      p[m].w = p[m].w / nrm;
-    }
-  }
+  row_update_s<KQ, true>(t, c, d, sm, p, a);
 }
 
 // P, A (P again when A is null: discarded) and fp32 sums of one quad-layout

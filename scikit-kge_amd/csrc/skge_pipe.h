@@ -1,9 +1,11 @@
 // Shared by the pipelined runners (skge_pipeline.hip: TransE;
-// skge_hole_pipe.hip: HolE): the launch arguments, the row update every
-// apply shares, the claim / hand-off protocol and the relation-row helpers.
+// skge_hole_pipe.hip: HolE): the launch arguments, the claim / hand-off
+// protocol and the relation-row helpers (the row update every apply shares is
+// skge_row_update.h).
 // The protocol itself is described at the top of skge_pipeline.hip.
 #pragma once
 #include "skge_host.h"
+#include "skge_row_update.h"
 
 namespace skge {
 
@@ -27,11 +29,6 @@ enum : int { ERR_WAIT = 1, ERR_PACKED = 2 };
 // ~3.5 slots per row and batch; hot rows there cost 531 / 519 vs 540 M).
 // (HOT_MIN 2 / 3, HOT_REL 4: within noise of these, same box)
 constexpr int HOT_REPS = 4, HOT_MIN = 4, HOT_REL = 8, HOT_MAX = 256;
-
-struct UpdParams {
-  int opt, post;
-  float lr, rin, rout, fdiv;   // g = (sum + rin*P)/div + rout*P, div = fdiv > 0 ? fdiv : count
-};
 
 struct PipeTab {               // entity table
   float* P;
@@ -227,78 +224,6 @@ __device__ __forceinline__ void load_upd_row(const float* P, const float* A,
     p[m] = prow[qc];
     a[m] = A ? arow[qc] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-}
-
-// One row's update from its exact packed sums (W32: int32x2 in sv / sw, else
-// int16x4 in sv) and occurrence count c > 0: segment
-// mean + AdaGrad / SGD + projection; the same arithmetic as apply_row_i16
-// (skge_update.hip) and the reference (skge/param.py:130, 147-155;
-// skge/transe.py normalize).  Lanes past the row end with zeros.
-// (row_update_s: the same from the sums already decoded to floats, zero past
-// the row -- the fused runner's form; every packed apply shares this code, so
-// a row's update has the same bits whichever kernel computes it)
-template <int KQ>
-__device__ __forceinline__ void row_update_s(const UpdParams& t, int c, int d,
-                                             const float4 (&sms)[KQ], float4 (&p)[KQ],
-                                             float4 (&a)[KQ]) {
-  const int l = lane_id(), nq = d >> 2;
-  const bool ada = t.opt == OPT_ADAGRAD;
-  const float div = t.fdiv > 0.0f ? t.fdiv : (float)c;
-  float ss = 0.0f;
-#pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-    const bool in = 64 * m + l < nq;
-    const float4 sm = sms[m];
-#define SKGE_UP(X)                                                      \
-  {                                                                     \
-    const float g = (sm.X + t.rin * p[m].X) / div + t.rout * p[m].X;    \
-    float pv = p[m].X;                                                  \
-    if (ada) {                                                          \
-      a[m].X = a[m].X + g * g;                        /* param.py:147 */\
-      pv = pv - adagrad_step_fast(t.lr, g, a[m].X);   /* 152-155 */     \
-    } else {                                                            \
-      pv = pv - t.lr * g;                             /* param.py:130 */\
-    }                                                                   \
-    p[m].X = in ? pv : 0.0f;                                            \
-    ss += p[m].X * p[m].X;                                              \
-  }
-    SKGE_UP(x)
-    SKGE_UP(y)
-    SKGE_UP(z)
-    SKGE_UP(w)
-#undef SKGE_UP
-  }
-  if (t.post != POST_NONE) {
-    ss = wave_sum(ss);
-    const float inv = proj_scale_fast(t.post, ss);   // param.py:165-166 / 171-173
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-      p[m].x = p[m].x * inv;
-      p[m].y = p[m].y * inv;
-      p[m].z = p[m].z * inv;
-      p[m].w = p[m].w * inv;
-    }
-  }
-}
-
-template <int KQ, bool W32>
-__device__ __forceinline__ void row_update(const UpdParams& t, int c, int d,
-                                           const unsigned long long (&sv)[KQ],
-                                           const unsigned long long (&sw)[KQ], float4 (&p)[KQ],
-                                           float4 (&a)[KQ]) {
-  const int l = lane_id(), nq = d >> 2;
-  float4 sm[KQ];
-#pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-    const bool in = 64 * m + l < nq;
-    if (W32) {   // int32x2 sums: quad q in words sv (elements 0, 1) and sw (2, 3)
-      const float2 lo = unpack_i32x2(in ? sv[m] : 0ull), hi = unpack_i32x2(in ? sw[m] : 0ull);
-      sm[m] = make_float4(lo.x, lo.y, hi.x, hi.y);
-    } else {     // int16x4 sums
-      sm[m] = unpack_i16x4(in ? sv[m] : 0ull);
-    }
-  }
-  row_update_s<KQ>(t, c, d, sm, p, a);
 }
 
 // Claim a pending entity row's update (the first wave to swap its count out

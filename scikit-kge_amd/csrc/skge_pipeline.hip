@@ -43,6 +43,7 @@
 #include "skge_hole_fft.h"
 #include "skge_pipe.h"
 #include "skge_sampler.h"
+#include "skge_transe_l1.h"
 
 namespace skge {
 
@@ -52,8 +53,9 @@ namespace skge {
 #define SKGE_HPIPE_HOT 1
 #endif
 
-// k_pipe_batch (large batches: more than 16k slot records per batch; smaller
-// batches run k_pipe_fused below): nA apply workgroups (dispatched first: they
+// k_pipe_batch (every runner but the one k_pipe_fused below takes: batches of
+// up to 16k slot records with rows of up to 64 floats, one GPU; see
+// pipe_create's r->fused): nA apply workgroups (dispatched first: they
 // start the hand-offs the scoring waves may wait on), then the scoring ones.
 // GRP: owner marks, GRP_ROWS owner rows per apply round trip.
 // DP: the data-parallel form (a slice [lo, hi) of the batch scored, records
@@ -233,32 +235,11 @@ __global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG) void k_pipe_batch
       }
     }
     if (a.trace) tt[2] = now_10ns();
-    float ps = 0.0f, n0 = 0.0f, n1 = 0.0f;
+    float ps, n0, n1;
     float4 gp4[KQ], g0[KQ], g1[KQ];
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-#define SKGE_EL(X)                                                                    \
-  {                                                                                   \
-    const float vp = (es[m].X + rp[m].X) - eo[m].X;   /* transe.py:32 */              \
-    const float v0 = (fs[m].X + rp[m].X) - eo[m].X;                                   \
-    const float v1 = (es[m].X + rp[m].X) - fo[m].X;                                   \
-    ps += fabsf(vp);                                                                  \
-    n0 += fabsf(v0);                                                                  \
-    n1 += fabsf(v1);                                                                  \
-    gp4[m].X = signf_np(-((eo[m].X - rp[m].X) - es[m].X)); /* transe.py:103,115 */    \
-    g0[m].X = signf_np((eo[m].X - rp[m].X) - fs[m].X);     /* transe.py:104,117 */    \
-    g1[m].X = signf_np((fo[m].X - rp[m].X) - es[m].X);                                \
-  }
-      SKGE_EL(x)
-      SKGE_EL(y)
-      SKGE_EL(z)
-      SKGE_EL(w)
-#undef SKGE_EL
-    }
-    const float pscore = -wave_sum(ps);
-    const float ns0 = -wave_sum(n0), ns1 = -wave_sum(n1);
-    const int v0 = (neg0 >= 0 && ns0 + a.margin > pscore) ? 1 : 0;   // strict >, transe.py:73
-    const int v1 = (neg1 >= 0 && ns1 + a.margin > pscore) ? 1 : 0;
+    int v0, v1;
+    l1_scores_signs<KQ>(es, eo, fs, fo, rp, ps, n0, n1, gp4, g0, g1);
+    l1_decide(ps, n0, n1, neg0, neg1, a.margin, v0, v1);
     if (a.trace) tt[3] = now_10ns();
     if (DP && a.dprec) {   // data-parallel: the positive's record for the other ranks
       uint32_t* out = a.dprec + (size_t)(w - lo) * pipe_dp_record_words(d);
@@ -290,22 +271,11 @@ __global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG) void k_pipe_batch
     }
     if (v0 + v1 > 0) {
       nv += v0 + v1;
-      const float fv0 = (float)v0, fv1 = (float)v1;
       float4 cs[KQ], co[KQ], c0[KQ], c1[KQ], cr[KQ];
+      const float fv0 = (float)v0, fv1 = (float)v1;
 #pragma unroll
-      for (int m = 0; m < KQ; ++m) {
-#define SKGE_CO(X)                                                   \
-  cs[m].X = fv0 * gp4[m].X + fv1 * (gp4[m].X + g1[m].X);             \
-  co[m].X = -(fv0 * (gp4[m].X + g0[m].X) + fv1 * gp4[m].X);          \
-  c0[m].X = g0[m].X;                                                 \
-  c1[m].X = -g1[m].X;                                                \
-  cr[m].X = fv0 * (gp4[m].X + g0[m].X) + fv1 * (gp4[m].X + g1[m].X);
-        SKGE_CO(x)
-        SKGE_CO(y)
-        SKGE_CO(z)
-        SKGE_CO(w)
-#undef SKGE_CO
-      }
+      for (int m = 0; m < KQ; ++m)
+        l1_contrib(fv0, fv1, gp4[m], g0[m], g1[m], cs[m], co[m], c0[m], c1[m], cr[m]);
       if (E8) {   // int8x4 sums: one 32-bit atomic per quad
         unsigned int* es8 = reinterpret_cast<unsigned int*>(esum);
         acc_row4_i8<KQ>(es8, s, cs, d);
@@ -326,19 +296,7 @@ __global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG) void k_pipe_batch
       }
       // relation sums: rows of rw words; int32x2 (two words per quad) when a
       // hot relation's batch total could pass 16 bits
-      unsigned long long* rrow = racc + (size_t)p * a.R.rw;
-#pragma unroll
-      for (int m = 0; m < KQ; ++m) {
-        const int q = 64 * m + l;
-        if (q < nq) {
-          if (W32) {
-            atomicAdd(rrow + 2 * q, pack_i32x2(cr[m].x, cr[m].y));
-            atomicAdd(rrow + 2 * q + 1, pack_i32x2(cr[m].z, cr[m].w));
-          } else {
-            atomicAdd(rrow + q, pack_i16x4(cr[m]));
-          }
-        }
-      }
+      l1_add_rel<KQ, W32>(racc + (size_t)p * a.R.rw, cr, d);
     }
     if (a.trace) {   // stamp after issue (no drain: the trace must not slow the launch)
       if (l == 0) {
@@ -613,32 +571,11 @@ __global__ __launch_bounds__(SKGE_PIPE_WG) void k_pipe_fused(PipeArgs a) {
       }
     }
     if (a.trace) tt[2] = now_10ns();
-    float ps = 0.0f, n0 = 0.0f, n1 = 0.0f;
+    float ps, n0, n1;
     float4 gp4[KQ], g0[KQ], g1[KQ];
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-#define SKGE_EL(X)                                                                    \
-  {                                                                                   \
-    const float vp = (e[0][m].X + rp[m].X) - e[1][m].X;   /* transe.py:32 */          \
-    const float v0 = (e[2][m].X + rp[m].X) - e[1][m].X;                               \
-    const float v1 = (e[0][m].X + rp[m].X) - e[3][m].X;                               \
-    ps += fabsf(vp);                                                                  \
-    n0 += fabsf(v0);                                                                  \
-    n1 += fabsf(v1);                                                                  \
-    gp4[m].X = signf_np(-((e[1][m].X - rp[m].X) - e[0][m].X)); /* transe.py:103,115 */ \
-    g0[m].X = signf_np((e[1][m].X - rp[m].X) - e[2][m].X);     /* transe.py:104,117 */ \
-    g1[m].X = signf_np((e[3][m].X - rp[m].X) - e[0][m].X);                            \
-  }
-      SKGE_EL(x)
-      SKGE_EL(y)
-      SKGE_EL(z)
-      SKGE_EL(w)
-#undef SKGE_EL
-    }
-    const float pscore = -wave_sum(ps);
-    const float ns0 = -wave_sum(n0), ns1 = -wave_sum(n1);
-    const int v0 = (neg0 >= 0 && ns0 + a.margin > pscore) ? 1 : 0;   // strict >, transe.py:73
-    const int v1 = (neg1 >= 0 && ns1 + a.margin > pscore) ? 1 : 0;
+    int v0, v1;
+    l1_scores_signs<KQ>(e[0], e[1], e[2], e[3], rp, ps, n0, n1, gp4, g0, g1);   // s, o, s', o'
+    l1_decide(ps, n0, n1, neg0, neg1, a.margin, v0, v1);
     if (a.trace) tt[3] = now_10ns();
     unsigned long long* const racc = racc0 + (size_t)(w & rmask) * rrep;
     {
@@ -659,22 +596,11 @@ __global__ __launch_bounds__(SKGE_PIPE_WG) void k_pipe_fused(PipeArgs a) {
     }
     if (v0 + v1 > 0) {
       nv += v0 + v1;
-      const float fv0 = (float)v0, fv1 = (float)v1;
       float4 cs[KQ], co[KQ], c0[KQ], c1[KQ], cr[KQ];
+      const float fv0 = (float)v0, fv1 = (float)v1;
 #pragma unroll
-      for (int m = 0; m < KQ; ++m) {
-#define SKGE_CO(X)                                                   \
-  cs[m].X = fv0 * gp4[m].X + fv1 * (gp4[m].X + g1[m].X);             \
-  co[m].X = -(fv0 * (gp4[m].X + g0[m].X) + fv1 * gp4[m].X);          \
-  c0[m].X = g0[m].X;                                                 \
-  c1[m].X = -g1[m].X;                                                \
-  cr[m].X = fv0 * (gp4[m].X + g0[m].X) + fv1 * (gp4[m].X + g1[m].X);
-        SKGE_CO(x)
-        SKGE_CO(y)
-        SKGE_CO(z)
-        SKGE_CO(w)
-#undef SKGE_CO
-      }
+      for (int m = 0; m < KQ; ++m)
+        l1_contrib(fv0, fv1, gp4[m], g0[m], g1[m], cs[m], co[m], c0[m], c1[m], cr[m]);
       if (E8) {
         unsigned int* es8 = reinterpret_cast<unsigned int*>(esum);
         acc_row4_i8<KQ>(es8, s, cs, d);
@@ -689,19 +615,7 @@ __global__ __launch_bounds__(SKGE_PIPE_WG) void k_pipe_fused(PipeArgs a) {
         if (v0) acc_row4_i16<KQ>(aE, neg0, c0, d);
         if (v1) acc_row4_i16<KQ>(aE, neg1, c1, d);
       }
-      unsigned long long* rrow = racc + (size_t)p * a.R.rw;
-#pragma unroll
-      for (int m = 0; m < KQ; ++m) {
-        const int q = 64 * m + l;
-        if (q < nq) {
-          if (W32) {
-            atomicAdd(rrow + 2 * q, pack_i32x2(cr[m].x, cr[m].y));
-            atomicAdd(rrow + 2 * q + 1, pack_i32x2(cr[m].z, cr[m].w));
-          } else {
-            atomicAdd(rrow + q, pack_i16x4(cr[m]));
-          }
-        }
-      }
+      l1_add_rel<KQ, W32>(racc + (size_t)p * a.R.rw, cr, d);
     }
     if (a.trace && l == 0) {   // stamp after issue (no drain)
       unsigned long long* tr = a.trace + 2 + 6 * (size_t)w;
@@ -819,19 +733,8 @@ __global__ __launch_bounds__(256) void k_pipe_dp_scatter(PipeArgs a, const uint3
     for (int m = 0; m < KQ; ++m) {
       const int q = 64 * m + l;
       const uint32_t x = q < nq ? in[1 + q] : 0u;
-      const float4 gp4 = untern4q(x & 0xFFu), g0 = untern4q((x >> 8) & 0xFFu),
-                   g1 = untern4q((x >> 16) & 0xFFu);
-#define SKGE_CO(X)                                             \
-  cs[m].X = fv0 * gp4.X + fv1 * (gp4.X + g1.X);                \
-  co[m].X = -(fv0 * (gp4.X + g0.X) + fv1 * gp4.X);             \
-  c0[m].X = g0.X;                                              \
-  c1[m].X = -g1.X;                                             \
-  cr[m].X = fv0 * (gp4.X + g0.X) + fv1 * (gp4.X + g1.X);
-      SKGE_CO(x)
-      SKGE_CO(y)
-      SKGE_CO(z)
-      SKGE_CO(w)
-#undef SKGE_CO
+      l1_contrib(fv0, fv1, untern4q(x & 0xFFu), untern4q((x >> 8) & 0xFFu),
+                 untern4q((x >> 16) & 0xFFu), cs[m], co[m], c0[m], c1[m], cr[m]);
     }
     if (E8) {
       unsigned int* es8 = reinterpret_cast<unsigned int*>(esum);
@@ -845,19 +748,7 @@ __global__ __launch_bounds__(256) void k_pipe_dp_scatter(PipeArgs a, const uint3
       if (v0) add_row4_i16<KQ>(esum + (size_t)neg0 * nq, c0, d);
       if (v1) add_row4_i16<KQ>(esum + (size_t)neg1 * nq, c1, d);
     }
-    unsigned long long* rrow = racc + (size_t)p * a.R.rw;
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-      const int q = 64 * m + l;
-      if (q < nq) {
-        if (W32) {
-          atomicAdd(rrow + 2 * q, pack_i32x2(cr[m].x, cr[m].y));
-          atomicAdd(rrow + 2 * q + 1, pack_i32x2(cr[m].z, cr[m].w));
-        } else {
-          atomicAdd(rrow + q, pack_i16x4(cr[m]));
-        }
-      }
-    }
+    l1_add_rel<KQ, W32>(racc + (size_t)p * a.R.rw, cr, d);
   }
 }
 

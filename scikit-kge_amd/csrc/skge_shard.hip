@@ -22,6 +22,7 @@
 // ranks and atomics add them: a G-rank step gives, bit for bit, the parameters
 // one rank would compute for the union batch.
 #include "skge_host.h"
+#include "skge_transe_l1.h"
 
 namespace skge {
 
@@ -276,51 +277,18 @@ __global__ __launch_bounds__(256) void k_shard_score(ShardScoreArgs a) {
     load_fetched<KQ>(a.F, p0_, d, fs);
     load_fetched<KQ>(a.F, p1_, d, fo);
     load_row4<KQ>(a.R, p, d, rp);
-    float ps = 0.0f, n0 = 0.0f, n1 = 0.0f;
+    float ps, n0, n1;
     float4 gp[KQ], g0[KQ], g1[KQ];
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-#define SKGE_EL(X)                                                                    \
-  {                                                                                   \
-    const float vp = (es[m].X + rp[m].X) - eo[m].X;   /* transe.py:32 */              \
-    const float v0 = (fs[m].X + rp[m].X) - eo[m].X;                                   \
-    const float v1 = (es[m].X + rp[m].X) - fo[m].X;                                   \
-    ps += fabsf(vp);                                                                  \
-    n0 += fabsf(v0);                                                                  \
-    n1 += fabsf(v1);                                                                  \
-    gp[m].X = signf_np(-((eo[m].X - rp[m].X) - es[m].X)); /* transe.py:103,115 */     \
-    g0[m].X = signf_np((eo[m].X - rp[m].X) - fs[m].X);    /* transe.py:104,117 */     \
-    g1[m].X = signf_np((fo[m].X - rp[m].X) - es[m].X);                                \
-  }
-      SKGE_EL(x)
-      SKGE_EL(y)
-      SKGE_EL(z)
-      SKGE_EL(w)
-#undef SKGE_EL
-    }
-    const float pscore = -wave_sum(ps);
-    const float ns0 = -wave_sum(n0), ns1 = -wave_sum(n1);
-    const int v0 = (p0_ >= 0 && ns0 + a.margin > pscore) ? 1 : 0;   // strict >, transe.py:73
-    const int v1 = (p1_ >= 0 && ns1 + a.margin > pscore) ? 1 : 0;
+    int v0, v1;
+    l1_scores_signs<KQ>(es, eo, fs, fo, rp, ps, n0, n1, gp, g0, g1);
+    l1_decide(ps, n0, n1, p0_, p1_, a.margin, v0, v1);   // (no row fetched: no negative)
     nv += v0 + v1;
-    // pair 0 lists (sp,op,sn,on) = (s,o,s',o), pair 1 = (s,o,s,o'):
     // rows s, o, s', o' receive (cs, co, c0, c1) with counts (v0+2v1, 2v0+v1, v0, v1)
-    const float fv0 = (float)v0, fv1 = (float)v1;
     float4 cs[KQ], co[KQ], c0[KQ], c1[KQ], cr[KQ];
+    const float fv0 = (float)v0, fv1 = (float)v1;
 #pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-#define SKGE_CO(X)                                                   \
-  cs[m].X = fv0 * gp[m].X + fv1 * (gp[m].X + g1[m].X);               \
-  co[m].X = -(fv0 * (gp[m].X + g0[m].X) + fv1 * gp[m].X);            \
-  c0[m].X = g0[m].X;                                                 \
-  c1[m].X = -g1[m].X;                                                \
-  cr[m].X = fv0 * (gp[m].X + g0[m].X) + fv1 * (gp[m].X + g1[m].X);
-      SKGE_CO(x)
-      SKGE_CO(y)
-      SKGE_CO(z)
-      SKGE_CO(w)
-#undef SKGE_CO
-    }
+    for (int m = 0; m < KQ; ++m)
+      l1_contrib(fv0, fv1, gp[m], g0[m], g1[m], cs[m], co[m], c0[m], c1[m], cr[m]);
     store_contrib<KQ>(a.C, a.cstride, ps_, v0 + 2 * v1, cs, d);
     store_contrib<KQ>(a.C, a.cstride, po_, 2 * v0 + v1, co, d);
     if (p0_ >= 0) store_contrib<KQ>(a.C, a.cstride, p0_, v0, c0, d);

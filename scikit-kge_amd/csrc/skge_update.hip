@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "skge_host.h"
+#include "skge_row_update.h"
 
 namespace skge {
 
@@ -28,7 +29,7 @@ int* dev_err_word() {   // the error word's device address (Accum::err)
 }
 
 // FX64 sums wrap silently past +-2^63 (2^23 in gradient units, FX_SCALE):
-// flag any decoded element at or past half of that range (partial: see above)
+// flag any decoded element at or past half of that range (error bit 4 above)
 __device__ __forceinline__ void fx_check(long long x) {
   constexpr long long HALF = 1ll << 62;
   if (x >= HALF || x <= -HALF) atomicOr(&g_skge_dev_err, 4);
@@ -265,42 +266,10 @@ __device__ __forceinline__ void i16_finish(const TableDev& t, int row, bool upd,
   // each occurrence adds a coefficient no larger than its count: c <= 32767
   // means no 16-bit field can have wrapped
   if (c > 32767 && l == 0) atomicOr(&g_skge_dev_err, 2);
-  const float div = t.fdiv > 0.0f ? t.fdiv : (float)c;
-  float ss = 0.0f;
-#pragma unroll
-  for (int m = 0; m < KQ; ++m) {
-    const bool in = 64 * m + l < nq;
-    const float4 sm = unpack_i16x4(in ? sv[m] : 0ull);
-#define SKGE_UP(X)                                                      \
-  {                                                                     \
-    const float g = (sm.X + t.rin * p[m].X) / div + t.rout * p[m].X;    \
-    float pv = p[m].X;                                                  \
-    if (ada) {                                                          \
-      a[m].X = a[m].X + g * g;                        /* param.py:147 */\
-      pv = pv - adagrad_step_fast(t.lr, g, a[m].X);   /* 152-155 */     \
-    } else {                                                            \
-      pv = pv - t.lr * g;                             /* param.py:130 */\
-    }                                                                   \
-    p[m].X = in ? pv : 0.0f;                                            \
-    ss += p[m].X * p[m].X;                                              \
-  }
-    SKGE_UP(x)
-    SKGE_UP(y)
-    SKGE_UP(z)
-    SKGE_UP(w)
-#undef SKGE_UP
-  }
-  if (t.post != POST_NONE && upd) {
-    ss = wave_sum(ss);
-    const float inv = proj_scale_fast(t.post, ss);   // param.py:165-166 / 171-173
-#pragma unroll
-    for (int m = 0; m < KQ; ++m) {
-      p[m].x = p[m].x * inv;
-      p[m].y = p[m].y * inv;
-      p[m].z = p[m].z * inv;
-      p[m].w = p[m].w * inv;
-    }
-  }
+  // the shared packed row update; a gated-off row (!upd) skips the projection:
+  // its p is never stored
+  const UpdParams u = {t.opt, upd ? t.post : POST_NONE, t.lr, t.rin, t.rout, t.fdiv};
+  row_update<KQ, false>(u, c, w, sv, sv, p, a);
 #pragma unroll
   for (int m = 0; m < KQ; ++m) {
     const int q = 64 * m + l;

@@ -74,6 +74,7 @@ def _same(a, b):
     (500, 7, 3001, 200, 7),         # ragged remainder batch
     (40, 3, 1200, 52, 4),           # tiny graph: rows shared by most positives
     (2000, 11, 8000, 512, 20),      # config-5 width
+    (64, 4, 256, 516, 2),           # four quads per lane (the smallest such width)
     (40943, 18, 141442, 200, 50),   # WN18, 2 x 1414 positives per union batch
 ])
 def test_dp_one_process_bitwise_equals_one_gpu_runner(n_ent, n_rel, T, d, nb):
@@ -145,7 +146,10 @@ def _spawn(world, backend, args):
 @pytest.mark.parametrize("world,args", [(2, (500, 7, 3001, 200, 7, 2, 5)),      # ragged: last slice short
                                         (2, (40943, 18, 14140, 200, 5, 2, 9)),  # WN18 rows, 2828 / batch
                                         (3, (500, 7, 3001, 200, 7, 2, 5)),      # slices of unequal size
-                                        (4, (40943, 18, 14140, 200, 5, 2, 9))])
+                                        (4, (40943, 18, 14140, 200, 5, 2, 9)),
+                                        # (appended: the ids above carry their position)
+                                        (2, (64, 4, 256, 260, 2, 2, 5)),        # remote scatter, two quads per lane
+                                        (2, (64, 4, 256, 516, 2, 2, 5))])       # ... and four
 def test_dp_ranks_on_one_gpu_gloo_bitwise(world, args):
     """world ranks (processes) sharing one GPU, the exchange over gloo: every
     rank's tables bit for bit the one-GPU pipelined runner's (the N > 1

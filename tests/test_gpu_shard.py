@@ -131,6 +131,7 @@ def _init_tables(n_ent, n_rel, d, seed):
     (500, 7, 3001, 200, 7),     # ragged remainder batch
     (40, 3, 1200, 52, 4),       # tiny graph: every row in every batch
     (2000, 11, 8000, 512, 20),  # config-5 width
+    (64, 4, 256, 516, 2),       # four quads per lane (the smallest such width)
 ])
 def test_single_rank_bitwise_equals_device_runner(n_ent, n_rel, T, d, nb):
     from test_gpu_device_loop import _runner_result
