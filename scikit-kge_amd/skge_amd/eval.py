@@ -34,6 +34,25 @@ def _model_code(model):
     raise NotImplementedError("no evaluator for %s" % type(model).__name__)
 
 
+def check_triple_ids(triples, n_ent, n_rel, what="triples"):
+    """Raise ValueError, naming the first offender, unless every (s, o, p) row
+    of ``triples`` has 0 <= s, o < n_ent and 0 <= p < n_rel.  The ranking
+    kernels index the tables with these ids unchecked, so this is the bounds
+    check: it runs on the host, before anything is allocated or launched."""
+    if torch.is_tensor(triples):
+        triples = triples.cpu().numpy()
+    a = np.asarray(triples).reshape(-1, 3)
+    if a.shape[0] == 0:
+        return
+    bad = ((a[:, 0] < 0) | (a[:, 0] >= n_ent) | (a[:, 1] < 0) | (a[:, 1] >= n_ent) |
+           (a[:, 2] < 0) | (a[:, 2] >= n_rel))
+    if bad.any():
+        i = int(np.argmax(bad))
+        s, o, p = (int(x) for x in a[i])
+        raise ValueError("%s: triple %d (s=%d, o=%d, p=%d) is out of range for %d entities and "
+                         "%d relations" % (what, i, s, o, p, n_ent, n_rel))
+
+
 class FilteredRankingEval(object):
     """xs: test triples (s, o, p); true_triples: every known triple (the
     filter).  neval is accepted for signature compatibility (the reference
@@ -85,18 +104,23 @@ class FilteredRankingEval(object):
         code, rel = _model_code(model)
         dev = model.device
         q = [(s, o, p) for p, sos in self.idx.items() for (s, o) in sos]
+        E = model.params["E"]
+        check_triple_ids(q, E.rows, rel.rows, "test triples")
+        check_triple_ids(self._true, E.rows, rel.rows, "known triples")
         if not q:
             return np.zeros((0, 4), dtype=np.int64)
         queries = torch.as_tensor(np.asarray(q, dtype=np.int32), device=dev)
-        E = model.params["E"]
         lib = L.lib()
         out = torch.empty((len(q), 4), dtype=torch.int32, device=dev)
         if os.environ.get("SKGE_RANK_SET") == "1":   # A/B: the triple-set form (round 1)
-            kg = self._known_set(dev)
+            # no known triples: no set (skge_rank then filters nothing); an
+            # empty triple array has no device pointer to build one from
+            kg = self._known_set(dev) if len(self._true) else None
             nbytes = lib.skge_rank_workspace_bytes(len(q), model.d)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             L.check(lib.skge_rank(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), E.rows,
-                                  model.d, L.ptr(queries), len(q), L.ptr(kg.slots), kg.capacity,
+                                  model.d, L.ptr(queries), len(q),
+                                  L.ptr(kg.slots) if kg else None, kg.capacity if kg else 0,
                                   L.ptr(ws), nbytes, L.ptr(out)), "rank")
         else:
             toff, tent, hoff, hent = self._known_answers(q, dev)
