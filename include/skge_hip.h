@@ -172,6 +172,14 @@ int skge_pair_grad(void *stream, int model, int af, const skge_table_t *ent,
  * Replaces HolE._gradients (skge/hole.py:22-42) and RESCAL._gradients
  * (skge/rescal.py:37-76).  score may be NULL; *loss += sum logaddexp(0,-y*f);
  * coef [T] receives fs = -y*sigmoid(-y*f) (used by skge_rescal_wgrad).
+ * A labelled triple whose relation is -1 is SKIPPED: it is not scored
+ * (score[i] is left unwritten), adds nothing to the loss, makes no
+ * contribution, takes no touched slot (its slots are written -1) and no
+ * occurrence count, gets coef 0, and its s and o are not read.  The device
+ * logistic loop (skge_triple_runner_*) marks so a negative its sampler did
+ * not find in ntries draws (skge/sample.py:41-46 has no such triple).  The
+ * same holds for skge_triple_step, and skge_rescal_wgrad leaves an item with
+ * relation -1 out of every relation's sum and count.
  */
 int skge_triple_grad(void *stream, int model, const skge_table_t *ent, const skge_table_t *rel,
                      int d, const int *trip, const float *ys, int T, float *score, float *coef,
@@ -324,6 +332,36 @@ skge_pair_runner_t *skge_pair_runner_create(void *stream, int model, int af,
 int skge_pair_runner_run(skge_pair_runner_t *r, void *stream, int nepochs);
 int skge_pair_runner_nlaunches(const skge_pair_runner_t *r);
 void skge_pair_runner_destroy(skge_pair_runner_t *r);
+
+/*
+ * Device logistic loop (HolE, RESCAL): one epoch of StochasticTrainer with
+ * RandomModeSampler(1, [0, 1]) (skge/base.py:1242-1316, skge/sample.py:28-46)
+ * captured into a hipGraph: the epoch's permutation and negatives (the same
+ * keyed draws as the other runners, replayed by skge_epoch_sample), then per
+ * batch of c positives (the np.split geometry, remainder batch included) its
+ * 3c labelled triples in the order `xys += samplef(xys)` gives -- the c
+ * positives (y = +1), then for positive j its s-corruption at c + 2j and its
+ * o-corruption at c + 2j + 1 (y = -1); a negative not found in ntries draws is
+ * a skipped triple in place (relation -1, see skge_triple_grad) -- and one
+ * skge_triple_step on them.  Every batch steps (there is no gate).  HolE with
+ * d in the wave FFT's range and tables the per-positive kernels take scores a
+ * positive and its two corruptions in one wave straight from the records
+ * (k_hole_logistic_pos: 5 forward and 5 inverse transforms per positive
+ * instead of 9 and 9; SKGE_HOLE_TRIPLES=1 keeps the explicit triples).  ent
+ * needs 6 * batch_size touched slots, rel (if it records slots) 3 *
+ * batch_size, RESCAL's W rel->rows.  The loss of every batch is added into
+ * *loss_total (optional); *epoch_key += 1 at the end of the epoch.
+ * nlaunches reports the graph's node count.
+ */
+typedef struct skge_triple_runner skge_triple_runner_t;
+skge_triple_runner_t *skge_triple_runner_create(void *stream, int model, const skge_table_t *ent,
+                                                const skge_table_t *rel, int d, const int *trip,
+                                                int64_t T, const void *set, int64_t set_capacity,
+                                                int nbatches, uint64_t seed, uint64_t *epoch_key,
+                                                int ntries, float *loss_total);
+int skge_triple_runner_run(skge_triple_runner_t *r, void *stream, int nepochs);
+int skge_triple_runner_nlaunches(const skge_triple_runner_t *r);
+void skge_triple_runner_destroy(skge_triple_runner_t *r);
 
 /*
  * Pipelined epoch runner for TransE-L1 with packed accumulators (the

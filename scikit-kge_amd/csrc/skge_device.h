@@ -92,6 +92,14 @@ __device__ __forceinline__ float proj_scale_fast(int post, float ss) {
                                                       : (ss < 1.0f ? 1.0f : ss));
 }
 
+// logistic loss of one labelled triple (skge/hole.py:22-42, rescal.py:37-76):
+// its loss term logaddexp(0, -y f) and fs = -y sigmoid(-y f)
+__device__ __forceinline__ void logistic(float y, float score, float* loss_i, float* fs) {
+  const float ysc = y * score;
+  *loss_i = fmaxf(-ysc, 0.0f) + log1pf(expf(-fabsf(ysc)));  // logaddexp(0, -ys)
+  *fs = -(y * (1.0f / (1.0f + expf(ysc))));                   // -(y * sigmoid(-ys))
+}
+
 __device__ __forceinline__ float signf_np(float x) {  // numpy.sign
   return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f);
 }

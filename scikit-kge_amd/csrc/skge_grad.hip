@@ -853,11 +853,17 @@ int launch_hole_pos(hipStream_t st, int af, const skge_table_t* ent, const skge_
 
 // ---------------------------------------------------------------------------
 // logistic loss: HolE skge/hole.py:22-42, RESCAL skge/rescal.py:37-76
+// (logistic(): skge_device.h).  A triple with relation -1 is SKIPPED
+// (skge_triple_grad in skge_hip.h): its slots name no row, coef 0, nothing
+// else read or written.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void logistic(float y, float score, float* loss_i, float* fs) {
-  const float ysc = y * score;
-  *loss_i = fmaxf(-ysc, 0.0f) + log1pf(expf(-fabsf(ysc)));  // logaddexp(0, -ys)
-  *fs = -(y * (1.0f / (1.0f + expf(ysc))));                   // -(y * sigmoid(-ys))
+// the slots and coef of skipped triple i (entity 2i, 2i+1; HolE relation i)
+template <int MODEL>
+__device__ __forceinline__ void skip_triple(const PairArgs& a, int i) {
+  const int l = lane_id();
+  if (l < 2) commit_slot(a.accE, -1, 0, 2 * i + l);
+  if (MODEL == HOLE && l == 2) commit_slot(replica(a.accR, i), -1, 0, i);
+  if (l == 0 && a.coef) a.coef[i] = 0.0f;
 }
 
 template <int MODEL, int KM>
@@ -879,7 +885,12 @@ __global__ __launch_bounds__(256) void k_triple_grad(PairArgs a) {
   float* fout = fRp2 + 2 * d + 4;
   float lsum = 0.0f;
   for (int i = blockIdx.x * wpb + wave; i < a.P; i += gridDim.x * wpb) {
-    const int s = uni(a.pos[3 * i]), o = uni(a.pos[3 * i + 1]), p = uni(a.pos[3 * i + 2]);
+    const int p = uni(a.pos[3 * i + 2]);
+    if (p < 0) {   // skipped triple
+      skip_triple<MODEL>(a, i);
+      continue;
+    }
+    const int s = uni(a.pos[3 * i]), o = uni(a.pos[3 * i + 1]);
     const float y = a.ys[i];
     float es[KM], eo[KM], x[KM], t[KM];
     load_row<KM>(a.E, s, d, es);
@@ -977,7 +988,12 @@ __global__ __launch_bounds__(256) void k_hole_triple_fft(PairArgs a) {
   float2* const b1 = b0 + 3 * M;
   float lsum = 0.0f;
   for (int i = blockIdx.x * wpb + wave; i < a.P; i += gridDim.x * wpb) {
-    const int s = uni(a.pos[3 * i]), o = uni(a.pos[3 * i + 1]), p = uni(a.pos[3 * i + 2]);
+    const int p = uni(a.pos[3 * i + 2]);
+    if (p < 0) {   // skipped triple
+      skip_triple<HOLE>(a, i);
+      continue;
+    }
+    const int s = uni(a.pos[3 * i]), o = uni(a.pos[3 * i + 1]);
     const float y = a.ys[i];
     float4 es[1], eo[1], rp[1];
     load_row4<1>(a.E, s, d, es);

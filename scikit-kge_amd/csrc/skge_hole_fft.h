@@ -397,12 +397,15 @@ __device__ __forceinline__ HoleSpec hole_fft_forward(float* wbuf, const float2* 
 // the inverse transforms' inputs (pre-processed half spectra) of the
 // contribution rows t in [lo, hi): 0 E[s], 1 E[o], 2 R[p], then E[s'] (v0),
 // E[o'] (v1)
-__device__ __forceinline__ void hole_inv_inputs(float2* b0, int M, const float2* tw,
-                                                const HoleSpec& h, int v0, int v1, float gp,
-                                                float g0, float g1, int lo, int hi) {
+// with the coefficients given (v0 / v1: the negatives' rows exist; g0 / g1
+// must be 0 for a negative that does not): cp the positive's, so E[s]:
+// conj(R) (cp E^o + g1 E^o'), u = cp E[s] + g0 E[s']
+__device__ __forceinline__ void hole_inv_inputs_c(float2* b0, int M, const float2* tw,
+                                                  const HoleSpec& h, int v0, int v1, float cp,
+                                                  float g0, float g1, int lo, int hi) {
   if (!h.on) return;
-  const float cE = (float)(v0 + v1) * gp, cF = v1 ? g1 : 0.0f;   // E[s] row
-  const float cu = (float)(v0 + v1) * gp, cf = v0 ? g0 : 0.0f;   // u = cu E[s] + cf E[s']
+  const float cE = cp, cF = v1 ? g1 : 0.0f;   // E[s] row
+  const float cu = cp, cf = v0 ? g0 : 0.0f;   // u = cu E[s] + cf E[s']
   float2 H[5][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -425,7 +428,16 @@ __device__ __forceinline__ void hole_inv_inputs(float2* b0, int M, const float2*
   }
   if (v1 && lo <= t && t < hi) fft_real_inv_pair(b0 + t * M, M, k, tw, H[4][0], H[4][1]);
 }
+// pairwise: the positive's coefficient is gp once per violating pair
+__device__ __forceinline__ void hole_inv_inputs(float2* b0, int M, const float2* tw,
+                                                const HoleSpec& h, int v0, int v1, float gp,
+                                                float g0, float g1, int lo, int hi) {
+  hole_inv_inputs_c(b0, M, tw, h, v0, v1, (float)(v0 + v1) * gp, g0, g1, lo, hi);
+}
 
+// PAIRWISE: cp = (v0 + v1) gp (hole_inv_inputs); else cp is the positive's
+// own coefficient (the logistic loss: hole_inv_inputs_c)
+template <bool PAIRWISE = true>
 __device__ __forceinline__ const float* hole_fft_rows(float* wbuf, const float2* tw, int d,
                                                       const HoleSpec& h, int v0, int v1,
                                                       float gp, float g0, float g1) {
@@ -434,7 +446,10 @@ __device__ __forceinline__ const float* hole_fft_rows(float* wbuf, const float2*
   float2* b1 = b0 + 5 * M;
   const int nt = 3 + v0 + v1;
   __builtin_amdgcn_wave_barrier();   // every lane is done reading the forward buffers
-  hole_inv_inputs(b0, M, tw, h, v0, v1, gp, g0, g1, 0, 5);
+  if constexpr (PAIRWISE)
+    hole_inv_inputs(b0, M, tw, h, v0, v1, gp, g0, g1, 0, 5);
+  else
+    hole_inv_inputs_c(b0, M, tw, h, v0, v1, gp, g0, g1, 0, 5);
   float2* z;
   if (M == 100 && nt == 5)
     z = fft_run_c<100, 5, true>(b0, b1, tw);

@@ -1536,6 +1536,12 @@ __global__ __launch_bounds__(256) void k_rescal_logistic(const int* __restrict__
   const int wpb = blockDim.x >> 6, ncb = (d + GC - 1) / GC;
   float lsum = 0.0f;
   for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < T; i += gridDim.x * wpb) {
+    if (__builtin_amdgcn_readfirstlane(trip[3 * i + 2]) < 0) {
+      // skipped triple: never bucketed (relation -1), so it has no GEMM rows,
+      // no partial scores and no dW coefficient; its slots name no row
+      if (lane_id() < 2) commit_slot(accE, -1, 0, 2 * i + lane_id());
+      continue;
+    }
     const int s = __builtin_amdgcn_readfirstlane(trip[3 * i]);
     const int o = __builtin_amdgcn_readfirstlane(trip[3 * i + 1]);
     const float score = spart_sum(ws, i, ncb);   // fixed order

@@ -78,6 +78,11 @@ SIGNATURES = {
     "skge_epoch_sample": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
+    "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
+                                        c_p, c_i, c_p]),
+    "skge_triple_runner_run": (c_i, [c_p, c_p, c_i]),
+    "skge_triple_runner_nlaunches": (c_i, [c_p]),
+    "skge_triple_runner_destroy": (None, [c_p]),
     "skge_pipe_runner_create": (c_p, [c_p, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p,
                                       c_f, c_i, c_p]),
     "skge_pipe_runner_create_ex": (c_p, [c_p, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,

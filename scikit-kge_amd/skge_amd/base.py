@@ -12,6 +12,8 @@ numeric step of a batch runs as HIP kernels through libskgehip.so:
 * ``device_loop=True`` (PairwiseStochasticTrainer, every model): the whole
   epoch runs on the device -- permutation, negative sampling, score,
   scatter, update -- captured once into a hipGraph by a native runner.
+  StochasticTrainer (the logistic loss: HolE, RESCAL) takes the same kwarg
+  (device.LogisticLoopRunner, skge_triple_runner_*).
 """
 import logging
 import os
@@ -313,6 +315,12 @@ class StochasticTrainer(object):
                             for u in self._updaters.values())
         self._loss_dev = None
         self._loss_host = 0.0
+        # device-resident epochs (PairwiseStochasticTrainer pops its own before
+        # this runs: what it set stays)
+        self.device_loop = kwargs.pop("device_loop", getattr(self, "device_loop", False))
+        self.seed = kwargs.pop("seed", getattr(self, "seed", 0))
+        self.ntries = kwargs.pop("ntries", getattr(self, "ntries", 100))
+        self._runner = None
 
     def set_max_epochs(self, epoch):
         self.max_epochs = epoch
@@ -330,6 +338,20 @@ class StochasticTrainer(object):
         self.hyperparams[param_id] = value
 
     def fit(self, xs, ys):
+        if self.device_loop:
+            from .device import (_require_logistic_model, device_sampler_args,
+                                 logistic_device_optim)
+            _require_logistic_model(self.model)
+            if self.samplef is None:
+                use_device, ntries, why = False, self.ntries, "samplef is None (no negatives)"
+            else:
+                use_device, ntries, why = device_sampler_args(self, xs, ys)
+            if use_device:
+                logistic_device_optim(self, xs, ntries=ntries)
+                return
+            # the device loop draws RandomModeSampler(1, [0, 1]) negatives
+            # itself; anything else trains on the per-batch path instead
+            warnings.warn("device_loop: %s; training on the per-batch path" % why)
         self._optim(list(zip(xs, ys)))
 
     def _pre_epoch(self):

@@ -567,6 +567,108 @@ class PairLoopRunner(object):
             self.handle = None
 
 
+def _require_logistic_model(model):
+    if model._kernel_model() not in (L.SKGE_HOLE, L.SKGE_RESCAL):
+        raise NotImplementedError("%s has no logistic loss in the reference"
+                                  % type(model).__name__)
+
+
+class LogisticLoopRunner(object):
+    """Native hipGraph epoch of the device logistic loop for HolE and RESCAL
+    (skge_triple_runner_*, csrc/skge_tripleloop.hip): one epoch of
+    StochasticTrainer with RandomModeSampler(1, [0, 1]) (skge/base.py:
+    1242-1316) -- the epoch's permutation and negatives drawn on the device
+    (the same keyed draws as the other runners), every batch's labelled
+    triples built once per epoch in the order ``xys += samplef(xys)`` gives
+    (positives, then each positive's s- and o-corruption; a negative not
+    found in ntries draws is a skipped triple), then per batch one
+    skge_triple_step -- the kernels of the per-batch path, so a device epoch
+    trains like feeding those triples to model._logistic_step.  HolE in the
+    wave FFT's range scores a positive and both corruptions in one wave
+    instead (k_hole_logistic_pos: the same triples, contributions and counts;
+    SKGE_HOLE_TRIPLES=1 selects the explicit triples).  The epoch's loss is
+    added into ``loss_total``; the per-row counters (updateCounts) are kept
+    as on the per-batch path."""
+
+    pipelined = False
+    counters = True
+
+    def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
+                 loss_total=None):
+        _require_logistic_model(model)
+        dev = model.device
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+        self.kg = kg
+        self.model = model
+        self.nbatches = nbatches
+        self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.loss_total = loss_total if loss_total is not None else \
+            torch.zeros(1, dtype=torch.float32, device=dev)
+        T3 = 3 * max(batch_sizes(kg.T, nbatches))
+        self.te, self.tr = model._tables("logistic", updaters, slots=model._triple_slots(T3))
+        # the graph captures raw pointers to the model's accumulators and
+        # counters: hold the tensors, so a later per-batch call that grows the
+        # model's slot arrays cannot free what this runner still writes
+        self._captured = [(a.sum, a.cnt, a.touched) for a in model._acc.values()] + \
+            [p._counters.copy() for p in model.params.values()]
+        torch.cuda.current_stream().synchronize()
+        lib = L.lib()
+        h = lib.skge_triple_runner_create(
+            L.stream_ptr(self.stream), model._kernel_model(), self.te, self.tr, model.d,
+            L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity, int(nbatches),
+            int(seed) & (2 ** 64 - 1), L.ptr(self.epoch_key), int(ntries),
+            L.ptr(self.loss_total))
+        if not h:
+            raise L.SkgeError("skge_triple_runner_create: %s" % lib.skge_last_error().decode())
+        self.handle = h
+        self.nlaunches = lib.skge_triple_runner_nlaunches(h)
+
+    def run(self, nepochs=1):
+        self.stream.wait_stream(torch.cuda.current_stream())
+        L.check(L.lib().skge_triple_runner_run(self.handle, L.stream_ptr(self.stream),
+                                               int(nepochs)), "triple runner run")
+        torch.cuda.current_stream().wait_stream(self.stream)
+
+    def synchronize(self):
+        self.stream.synchronize()
+        L.check_device_error(L.stream_ptr(self.stream), "logistic-loop runner")
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                self.stream.synchronize()
+                L.lib().skge_triple_runner_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+def logistic_device_optim(trainer, xs, ntries=None):
+    """StochasticTrainer.fit with device_loop=True: per epoch _pre_epoch, one
+    graph replay, the runner's error word, then the post_epoch callbacks (which
+    read the epoch's loss through trainer.loss as on the per-batch path)."""
+    model = trainer.model
+    dev = model.device
+    if trainer._loss_dev is None:
+        trainer._loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+    kg = DeviceKG(xs, dev)
+    runner = LogisticLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
+                                ntries=trainer.ntries if ntries is None else ntries,
+                                loss_total=trainer._loss_dev)
+    trainer._runner = runner
+    trainer.batch_size = kg.T // trainer.nbatches
+    with torch.cuda.stream(runner.stream):
+        for trainer.epoch in range(1, trainer.max_epochs + 1):
+            trainer._pre_epoch()
+            trainer.epoch_start = timeit.default_timer()
+            runner.run(1)
+            runner.synchronize()   # raises on the epoch's error bits
+            for f in trainer.post_epoch:
+                if not f(trainer):
+                    break
+
+
 def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None):
     """The epoch's positives and draws as the device loops make them:
     (rec [T, 4] = (s, o, p, s' or -1), rec_n1 [T] = o' or -1) on the device."""
