@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "skge_host.h"
+#include "skge_graph_runner.h"
 #include "skge_sampler.h"
 #include "skge_transe_l1.h"
 
@@ -373,15 +373,6 @@ extern "C" size_t skge_triple_set_bytes(int64_t capacity) {
   return (size_t)capacity * sizeof(int4) + (size_t)capacity;   // slots + 8 filter bits per slot
 }
 
-static TripleSet triple_set_of(const void* set, int64_t capacity) {
-  TripleSet ts;
-  ts.slots = (const int4*)set;
-  ts.filter = (const uint32_t*)((const int4*)set + capacity);
-  ts.mask = (uint64_t)(capacity - 1);
-  ts.fmask = (uint64_t)(8 * capacity - 1);
-  return ts;
-}
-
 extern "C" int skge_triple_set_build(void* stream, const int* trip, int64_t T, void* set,
                                      int64_t capacity) {
   SKGE_CHECK_ARG(trip && set, "NULL argument");
@@ -394,7 +385,7 @@ extern "C" int skge_triple_set_build(void* stream, const int* trip, int64_t T, v
   if (T == 0) return SKGE_OK;
   long long blocks = (T + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  TripleSet ts = triple_set_of(set, capacity);
+  TripleSet ts = triple_set_view(set, capacity);
   hipLaunchKernelGGL(k_set_build, dim3((unsigned)blocks), dim3(256), 0, st, trip, (long long)T,
                      (int4*)ts.slots, (unsigned long long)ts.mask, (uint32_t*)ts.filter,
                      (unsigned long long)ts.fmask);
@@ -423,7 +414,7 @@ static int fill_sample_args(SampleArgs& a, int l1, const skge_table_t* ent, cons
   a.accR = accum_of(rel);
   a.trip = trip;
   a.T = T;
-  a.set = triple_set_of(set_slots, set_capacity);
+  a.set = triple_set_view(set_slots, set_capacity);
   a.d = d;
   a.n_ent = ent->rows;
   a.ntries = ntries;
@@ -478,20 +469,10 @@ extern "C" int skge_epoch_advance(void* stream, uint64_t* epoch_key) {
 }
 
 // ---- native epoch runner: one hipGraph per epoch ----
-struct skge_runner {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int nlaunch = 0;
+struct skge_runner : GraphRunnerCore {
+  int nlaunch = 0;         // kernel launches per epoch, counted as they are captured
   int* shards = nullptr;
 };
-
-static void runner_free(skge_runner_t* r) {
-  if (!r) return;
-  if (r->exec) (void)hipGraphExecDestroy(r->exec);
-  if (r->graph) (void)hipGraphDestroy(r->graph);
-  if (r->shards) (void)hipFree(r->shards);
-  delete r;
-}
 
 extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_table_t* ent,
                                              const skge_table_t* rel, int d, const int* trip,
@@ -500,37 +481,20 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
                                              uint64_t* epoch_key, float margin, int ntries,
                                              int* nviol, int* nviol_total) {
   SampleArgs a;
+  // (this runner takes any T and any power-of-two set, as skge_transe_sample_grad does)
   if (fill_sample_args(a, l1, ent, rel, d, trip, T, set_slots, set_capacity, seed, epoch_key,
-                       margin, ntries, nviol, nviol_total))
+                       margin, ntries, nviol, nviol_total) ||
+      !check_runner_args("runner", trip, set_slots, epoch_key, T, INT64_MAX, nbatches,
+                         set_capacity, 1, ntries, stream))
     return nullptr;
-  if (nbatches < 1 || nbatches > T) {
-    set_error("nbatches must be in [1, T]");
-    return nullptr;
-  }
-  if (stream == nullptr) {
-    set_error("runner needs a non-default stream (graph capture)");
-    return nullptr;
-  }
   hipStream_t st = as_stream(stream);
-  // batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268)
-  const int64_t bs = T / nbatches;
-  std::vector<std::pair<int64_t, int64_t>> batches;
-  for (int64_t s0 = 0; s0 < T; s0 += bs) batches.push_back({s0, (s0 + bs <= T) ? bs : T - s0});
-  skge_runner_t* r = new skge_runner_t();
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  std::unique_ptr<skge_runner_t> r(new skge_runner_t());
   skge_table_t tabs[2] = {*ent, *rel};
-  if (hipMalloc(&r->shards, NSHARD * SHARD_STRIDE * 4) != hipSuccess ||
-      hipMemset(r->shards, 0, NSHARD * SHARD_STRIDE * 4) != hipSuccess) {
-    set_error("runner: device allocation failed");
-    runner_free(r);
-    return nullptr;
-  }
+  r->shards = (int*)r->alloc(NSHARD * SHARD_STRIDE * 4, true);
+  if (!r->alloc_ok) return fail("runner: device allocation failed");
   a.vshards = r->shards;
-  if (hipStreamSynchronize(st) != hipSuccess ||
-      hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    set_error("hipStreamBeginCapture failed");
-    runner_free(r);
-    return nullptr;
-  }
+  if (!r->begin_capture(st)) return nullptr;
   int rc = SKGE_OK;
   // large batches: when a batch's entity slot records outnumber the table's
   // rows, the entity table is applied densely (one wave per row, claimed as
@@ -541,7 +505,7 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
   // SKGE_APPLY_DENSE=0: slot records always.
   const char* de = getenv("SKGE_APPLY_DENSE");
   const int dense_mode = de ? atoi(de) : 1;
-  for (auto& b : batches) {
+  for (auto& b : batches.batches) {
     a.start = b.first;
     a.count = (int)b.second;
     a.neg_out = nullptr;
@@ -560,30 +524,13 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
     hipLaunchKernelGGL(k_epoch_end, dim3(1), dim3(64), 0, st, epoch_key, r->shards, nviol_total);
     r->nlaunch += 1;
   }
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc || e != hipSuccess) {
-    if (!rc) set_error("hipStreamEndCapture: %s", hipGetErrorString(e));
-    if (g) (void)hipGraphDestroy(g);
-    runner_free(r);
-    return nullptr;
-  }
-  r->graph = g;
-  e = hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0);
-  if (e != hipSuccess) {
-    set_error("hipGraphInstantiate: %s", hipGetErrorString(e));
-    runner_free(r);
-    return nullptr;
-  }
-  return r;
+  return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
 extern "C" int skge_runner_run(skge_runner_t* r, void* stream, int nepochs) {
-  SKGE_CHECK_ARG(r && r->exec, "bad runner");
-  for (int i = 0; i < nepochs; ++i) SKGE_CHECK_HIP(hipGraphLaunch(r->exec, as_stream(stream)));
-  return SKGE_OK;
+  return run_graph(r, stream, nepochs);
 }
 
 extern "C" int skge_runner_nlaunches(const skge_runner_t* r) { return r ? r->nlaunch : -1; }
 
-extern "C" void skge_runner_destroy(skge_runner_t* r) { runner_free(r); }
+extern "C" void skge_runner_destroy(skge_runner_t* r) { delete r; }

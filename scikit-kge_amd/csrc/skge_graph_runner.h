@@ -1,0 +1,152 @@
+// Host half shared by the device epoch runners (skge_epoch.hip,
+// skge_pipeline.hip, skge_pairloop.hip, skge_tripleloop.hip): the batch
+// geometry, the argument refusals, and GraphRunnerCore -- the captured graph
+// and the device buffers it names.  A runner supplies its own checks beyond
+// check_runner_args, its buffers (alloc) and the launches between
+// begin_capture and end_capture.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <utility>
+#include <vector>
+
+#include "skge_host.h"
+
+namespace skge {
+
+// set the error text; converts to any runner's NULL handle
+template <class... A>
+inline std::nullptr_t fail(const char* fmt, A... a) {
+  if constexpr (sizeof...(A) == 0) set_error("%s", fmt);
+  else set_error(fmt, a...);
+  return nullptr;
+}
+
+// batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268):
+// nbatches batches of bs = T / nbatches and the remainder, as (start, count)
+// (k_triples_of_epoch, skge_tripleloop.hip, re-derives a positive's batch on the device)
+struct EpochBatches {
+  int64_t bs = 0, maxb = 0;
+  std::vector<std::pair<int64_t, int64_t>> batches;
+  int size() const { return (int)batches.size(); }
+  const std::pair<int64_t, int64_t>& operator[](int k) const { return batches[k]; }
+};
+
+inline EpochBatches epoch_batches(int64_t T, int nbatches) {
+  EpochBatches b;
+  b.bs = T / nbatches;
+  for (int64_t s0 = 0; s0 < T; s0 += b.bs) {
+    const int64_t c = (s0 + b.bs <= T) ? b.bs : T - s0;
+    b.batches.push_back({s0, c});
+    b.maxb = std::max(b.maxb, c);
+  }
+  return b;
+}
+
+// The refusals every runner makes before its first HIP call.  Tmax and cap_min
+// are the runner's own bounds: the pair loop indexes 2T pairs with ints and the
+// triple loop 3T triples; the pair and triple loops and the device sampler
+// need a set of >= 2T slots, the pipelined runner takes any set of >= 4.
+inline bool check_runner_args(const char* who, const void* trip, const void* set,
+                              const void* epoch_key, int64_t T, int64_t Tmax, int nbatches,
+                              int64_t set_capacity, int64_t cap_min, int ntries, void* stream) {
+  auto no = [who](const char* fmt, long long bound) {
+    char what[96];
+    snprintf(what, sizeof(what), fmt, bound);
+    set_error("%s: %s", who, what);
+    return false;
+  };
+  if (!trip || !set || !epoch_key) return no("NULL argument", 0);
+  if (T <= 0 || T > Tmax)
+    return Tmax == INT64_MAX ? no("T must be >= 1", 0) : no("T must be in [1, %lld]", Tmax);
+  if (nbatches < 1 || nbatches > T) return no("nbatches must be in [1, T]", 0);
+  if (set_capacity < cap_min || (set_capacity & (set_capacity - 1)))
+    return no("set capacity must be a power of 2 >= %lld", cap_min);
+  if (ntries < 1) return no("ntries >= 1", 0);
+  if (!stream) return no("needs a non-default stream (graph capture)", 0);
+  return true;
+}
+
+// One captured epoch and the device buffers its nodes name.  Runner structs
+// derive from it; deleting a runner releases everything.
+struct GraphRunnerCore {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  int nnodes = 0;             // nodes of the captured graph
+  std::vector<void*> bufs;
+  bool alloc_ok = true;       // false once an alloc() has failed
+
+  GraphRunnerCore() = default;
+  GraphRunnerCore(const GraphRunnerCore&) = delete;
+  GraphRunnerCore& operator=(const GraphRunnerCore&) = delete;
+
+  // A device buffer owned by the runner.  zero: at least 4 bytes, zero-filled
+  // before this returns; otherwise as hipMalloc leaves it (the graph writes it
+  // before it reads it).  nullptr on failure (alloc_ok stays false).
+  void* alloc(size_t bytes, bool zero) {
+    if (zero && bytes < 4) bytes = 4;
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+      alloc_ok = false;
+      return nullptr;
+    }
+    bufs.push_back(p);
+    if (zero && hipMemset(p, 0, bytes) != hipSuccess) {
+      alloc_ok = false;
+      return nullptr;
+    }
+    return p;
+  }
+
+  // the stream's earlier work done (the caller's tables, the zero fills), then
+  // thread-local capture
+  bool begin_capture(hipStream_t st) {
+    if (hipStreamSynchronize(st) == hipSuccess &&
+        hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess)
+      return true;
+    set_error("hipStreamBeginCapture failed");
+    return false;
+  }
+
+  // rc: the captured launches' result (its error text already set).  Ends the
+  // capture either way; on success the graph is instantiated and counted.
+  bool end_capture(hipStream_t st, int rc) {
+    hipError_t e = hipStreamEndCapture(st, &graph);
+    if (!rc && e != hipSuccess) set_error("hipStreamEndCapture: %s", hipGetErrorString(e));
+    if (rc || e != hipSuccess) {
+      if (graph) (void)hipGraphDestroy(graph);
+      graph = nullptr;
+      return false;
+    }
+    size_t n = 0;
+    if (hipGraphGetNodes(graph, nullptr, &n) == hipSuccess) nnodes = (int)n;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) set_error("hipGraphInstantiate: %s", hipGetErrorString(e));
+    return e == hipSuccess;
+  }
+
+  hipError_t launch(hipStream_t st, int nepochs) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < nepochs && e == hipSuccess; ++i) e = hipGraphLaunch(exec, st);
+    return e;
+  }
+
+  ~GraphRunnerCore() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    for (void* p : bufs) (void)hipFree(p);
+    // HIP's last-error word is sticky.  A runner is deleted right after a
+    // failed allocation or capture; the error is cleared here, once, after the
+    // frees, so that it cannot fail a later launch check.
+    (void)hipGetLastError();
+  }
+};
+
+// the run / nlaunches bodies of the runners that are nothing but their graph
+inline int run_graph(GraphRunnerCore* r, void* stream, int nepochs) {
+  SKGE_CHECK_ARG(r && r->exec, "bad runner");
+  SKGE_CHECK_HIP(r->launch(as_stream(stream), nepochs));
+  return SKGE_OK;
+}
+
+}  // namespace skge

@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "skge_host.h"
+#include "skge_graph_runner.h"
 #include "skge_hole_fft.h"
 #include "skge_sampler.h"
 
@@ -93,10 +93,7 @@ __global__ __launch_bounds__(256) void k_pairs_epoch_end(const int* __restrict__
 
 using namespace skge;
 
-struct skge_pair_runner {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int nlaunch = 0;
+struct skge_pair_runner : GraphRunnerCore {
   int4* rec = nullptr;
   int* rec_n1 = nullptr;
   int* pairs = nullptr;   // the epoch's pairs: pos [2T][3], then neg [2T][3]
@@ -105,48 +102,21 @@ struct skge_pair_runner {
   size_t ws_bytes = 0;
 };
 
-static void pair_runner_free(skge_pair_runner_t* r) {
-  if (!r) return;
-  if (r->exec) (void)hipGraphExecDestroy(r->exec);
-  if (r->graph) (void)hipGraphDestroy(r->graph);
-  if (r->rec) (void)hipFree(r->rec);
-  if (r->rec_n1) (void)hipFree(r->rec_n1);
-  if (r->pairs) (void)hipFree(r->pairs);
-  if (r->nviol) (void)hipFree(r->nviol);
-  if (r->ws) (void)hipFree(r->ws);
-  (void)hipGetLastError();   // a failed allocation must not poison later checks
-  delete r;
-}
-
 extern "C" skge_pair_runner_t* skge_pair_runner_create(
     void* stream, int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
     uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total) {
-  auto fail = [](const char* fmt, const char* what) -> skge_pair_runner_t* {
-    set_error(fmt, what);
+  if (!ent || !rel) return fail("pair runner: NULL table");
+  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("pair runner: unknown model");
+  if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity,
+                         2 * T, ntries, stream))
     return nullptr;
-  };
-  if (!ent || !rel || !trip || !set || !epoch_key) return fail("%s", "NULL argument");
-  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("%s", "unknown model");
-  if (T <= 0 || T > INT32_MAX) return fail("%s", "T must be in [1, 2^31)");
-  if (nbatches < 1 || nbatches > T) return fail("%s", "nbatches must be in [1, T]");
-  if (set_capacity < 2 * T || (set_capacity & (set_capacity - 1)))
-    return fail("%s", "set capacity must be a power of 2 >= 2T");
-  if (ntries < 1) return fail("%s", "ntries >= 1");
-  if (stream == nullptr) return fail("%s", "runner needs a non-default stream (graph capture)");
   hipStream_t st = as_stream(stream);
-  // batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268)
-  const int64_t bs = T / nbatches;
-  std::vector<std::pair<int64_t, int64_t>> batches;
-  int64_t maxb = 0;
-  for (int64_t s0 = 0; s0 < T; s0 += bs) {
-    const int64_t c = (s0 + bs <= T) ? bs : T - s0;
-    batches.push_back({s0, c});
-    maxb = std::max(maxb, c);
-  }
-  const int Pmax = (int)(2 * maxb);
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  const int64_t bs = batches.bs;
+  const int Pmax = (int)(2 * batches.maxb);
   if ((long long)4 * Pmax > ent->touched_cap && ent->acc_touched)
-    return fail("%s", "entity accumulator needs 8 * batch_size touched slots");
+    return fail("pair runner: entity accumulator needs 8 * batch_size touched slots");
   // HolE with the register-tiled correlations: both pairs of a positive in
   // one wave straight from the records, 4 entity slots and 1 relation slot per
   // positive (SKGE_HOLE_PAIRS=1 keeps the explicit pairs)
@@ -158,36 +128,27 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create(
   const char* rp = getenv("SKGE_RESCAL_PAIRS");
   const bool rpos = model == SKGE_RESCAL && !(rp && atoi(rp)) &&
                     rescal_pair_mfma_selected(d, rel->rows);
-  const int nb = (int)batches.size();
+  const int nb = batches.size();
   // RESCAL: every batch's relation buckets built once per epoch, up front (the
   // items do not depend on the parameters); SKGE_RESCAL_EPOCH_BUCKETS=0 keeps
   // the per-batch bucketing
   const char* eb = getenv("SKGE_RESCAL_EPOCH_BUCKETS");
   const bool rep = rpos && rescal_epoch_ok(rel->rows) && !(eb && atoi(eb) == 0);
-  skge_pair_runner_t* r = new skge_pair_runner_t();
+  std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
   r->ws_bytes = rep ? rescal_epoch_ws_bytes((int)bs, nb, rel->rows, d)
                     : skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
-  if (hipMalloc(&r->rec, (size_t)T * sizeof(int4)) != hipSuccess ||
-      hipMalloc(&r->rec_n1, (size_t)T * sizeof(int)) != hipSuccess ||
-      (!hpos && hipMalloc(&r->pairs, (size_t)T * 12 * sizeof(int)) != hipSuccess) ||
-      hipMalloc(&r->nviol, (size_t)nb * sizeof(int)) != hipSuccess ||
-      (r->ws_bytes && hipMalloc(&r->ws, r->ws_bytes) != hipSuccess) ||
-      hipMemset(r->nviol, 0, (size_t)nb * sizeof(int)) != hipSuccess) {
-    pair_runner_free(r);
-    return fail("%s", "pair runner: device allocation failed");
-  }
+  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
+  r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
+  if (!hpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
+  r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  if (!r->alloc_ok) return fail("pair runner: device allocation failed");
   int* pos = r->pairs;
   int* neg = r->pairs ? r->pairs + (size_t)T * 6 : nullptr;
   const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d)) {   // before the capture
-    pair_runner_free(r);
-    return fail("%s", "pair runner: HolE FFT twiddle table allocation failed");
-  }
-  if (hipStreamSynchronize(st) != hipSuccess ||
-      hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    pair_runner_free(r);
-    return fail("%s", "hipStreamBeginCapture failed");
-  }
+  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
+    return fail("pair runner: HolE FFT twiddle table allocation failed");
+  if (!r->begin_capture(st)) return nullptr;
   int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
                                r->rec, r->rec_n1);
   if (!rc) {
@@ -246,24 +207,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create(
       rc = SKGE_EHIP;
     }
   }
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc || e != hipSuccess) {
-    if (!rc) set_error("hipStreamEndCapture: %s", hipGetErrorString(e));
-    if (g) (void)hipGraphDestroy(g);
-    pair_runner_free(r);
-    return nullptr;
-  }
-  r->graph = g;
-  size_t nnodes = 0;
-  if (hipGraphGetNodes(g, nullptr, &nnodes) == hipSuccess) r->nlaunch = (int)nnodes;
-  e = hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0);
-  if (e != hipSuccess) {
-    set_error("hipGraphInstantiate: %s", hipGetErrorString(e));
-    pair_runner_free(r);
-    return nullptr;
-  }
-  return r;
+  return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
 extern "C" int skge_epoch_sample(void* stream, const int* trip, int64_t T, const void* set,
@@ -280,13 +224,11 @@ extern "C" int skge_epoch_sample(void* stream, const int* trip, int64_t T, const
 }
 
 extern "C" int skge_pair_runner_run(skge_pair_runner_t* r, void* stream, int nepochs) {
-  SKGE_CHECK_ARG(r && r->exec, "bad runner");
-  for (int i = 0; i < nepochs; ++i) SKGE_CHECK_HIP(hipGraphLaunch(r->exec, as_stream(stream)));
-  return SKGE_OK;
+  return run_graph(r, stream, nepochs);
 }
 
 extern "C" int skge_pair_runner_nlaunches(const skge_pair_runner_t* r) {
-  return r ? r->nlaunch : -1;
+  return r ? r->nnodes : -1;
 }
 
-extern "C" void skge_pair_runner_destroy(skge_pair_runner_t* r) { pair_runner_free(r); }
+extern "C" void skge_pair_runner_destroy(skge_pair_runner_t* r) { delete r; }

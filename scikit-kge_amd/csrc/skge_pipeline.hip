@@ -39,6 +39,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "skge_graph_runner.h"
 #include "skge_hole.h"
 #include "skge_hole_fft.h"
 #include "skge_pipe.h"
@@ -806,10 +807,7 @@ int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t s
 using namespace skge;
 
 // ---- pipelined runner ----
-struct skge_pipe_runner {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  std::vector<void*> bufs;
+struct skge_pipe_runner : GraphRunnerCore {
   int* err = nullptr;
   int* stats = nullptr;            // [nlaunch][3] (profile only)
   // the epoch's launches
@@ -836,23 +834,6 @@ struct skge_pipe_runner {
   int n_rows = 0, d = 0;           // fused: the entity table's geometry (k_fused_fin)
   int nlaunch() const { return (int)batch.size() + 2; }
 };
-
-static void* dalloc(skge_pipe_runner* r, size_t bytes) {
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-  r->bufs.push_back(p);
-  if (hipMemset(p, 0, bytes ? bytes : 4) != hipSuccess) return nullptr;
-  return p;
-}
-
-static void pipe_free(skge_pipe_runner* r) {
-  (void)hipGetLastError();   // a failed allocation must not poison later launch checks
-  if (!r) return;
-  if (r->exec) (void)hipGraphExecDestroy(r->exec);
-  if (r->graph) (void)hipGraphDestroy(r->graph);
-  for (void* p : r->bufs) (void)hipFree(p);
-  delete r;
-}
 
 static void launch_fused(const skge_pipe_runner* r, dim3 gr, hipStream_t st, const PipeArgs& a) {
   const dim3 bl(SKGE_PIPE_WG);
@@ -1074,20 +1055,17 @@ static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const
     h[rows[j]] = j;
   }
   t.hw = (row_words + 15) / 16 * 16;   // 8-B words per replica row: whole 128-B lines
-  int* dh = (int*)dalloc(r, (size_t)N * 4);
-  int* dr = (int*)dalloc(r, (size_t)nh * 4);
-  bool got = dh && dr;
+  int* dh = (int*)r->alloc((size_t)N * 4, true);
+  int* dr = (int*)r->alloc((size_t)nh * 4, true);
   for (int k = 0; k < 3; ++k) {
-    t.hsum[k] = (unsigned long long*)dalloc(r, (size_t)nh * HOT_REPS * t.hw * 8);
-    t.hcnt[k] = (int*)dalloc(r, (size_t)nh * HOT_REPS * 4);
-    got = got && t.hsum[k] && t.hcnt[k];
+    t.hsum[k] = (unsigned long long*)r->alloc((size_t)nh * HOT_REPS * t.hw * 8, true);
+    t.hcnt[k] = (int*)r->alloc((size_t)nh * HOT_REPS * 4, true);
   }
   for (int k = 0; k < 2; ++k) {
-    t.hP[k] = (float*)dalloc(r, (size_t)nh * d * 4);
-    t.hA[k] = t.A ? (float*)dalloc(r, (size_t)nh * d * 4) : nullptr;
-    got = got && t.hP[k] && (!t.A || t.hA[k]);
+    t.hP[k] = (float*)r->alloc((size_t)nh * d * 4, true);
+    t.hA[k] = t.A ? (float*)r->alloc((size_t)nh * d * 4, true) : nullptr;
   }
-  if (!got ||
+  if (!r->alloc_ok ||
       hipMemcpy(dh, h.data(), (size_t)N * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(dr, rows.data(), (size_t)nh * 4, hipMemcpyHostToDevice) != hipSuccess)
     return false;
@@ -1140,21 +1118,17 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
               "d %% 4 == 0, no gates");
     return nullptr;
   }
-  if (!trip || !set || !epoch_key || T <= 0 || nbatches < 1 || nbatches > T || !stream ||
-      set_capacity < 4 || (set_capacity & (set_capacity - 1)) || ntries < 1) {
-    set_error("pipelined runner: bad arguments");
+  // (any T -- the slot capacity bounds the batch -- and any set of >= 4 slots)
+  if (!check_runner_args("pipelined runner", trip, set, epoch_key, T, INT64_MAX, nbatches,
+                         set_capacity, 4, ntries, stream))
     return nullptr;
-  }
-  // batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268)
   const int64_t bs = T / nbatches;
-  if (4 * bs > ent->touched_cap || 4 * bs > (1ll << 30)) {
-    set_error("pipelined runner: batch too large for the slot capacity");
-    return nullptr;
-  }
-  std::vector<std::pair<int64_t, int64_t>> batches;
-  for (int64_t s0 = 0; s0 < T; s0 += bs) batches.push_back({s0, (s0 + bs <= T) ? bs : T - s0});
-  const int nb1 = (int)batches.size();
-  skge_pipe_runner* r = new skge_pipe_runner();
+  if (4 * bs > ent->touched_cap || 4 * bs > (1ll << 30))
+    return fail("pipelined runner: batch too large for the slot capacity");
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  const int nb1 = batches.size();
+  const int64_t maxb = batches.maxb;
+  std::unique_ptr<skge_pipe_runner> r(new skge_pipe_runner());
   r->hole = hole;
   r->dp = dp;
   // HolE at d = 200 in the FFT form: two waves per positive (the pair form)
@@ -1162,8 +1136,6 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   // residency.  WN18 d = 200, same box: nb = 100 93.7 -> 106.7 M triples/s
   // (14.6 -> 12.8 us per launch); nb = 2 (70k positives per launch) 157 ->
   // 142 M, so off there
-  int64_t maxb = 0;
-  for (const auto& bt : batches) maxb = std::max(maxb, bt.second);
   const bool hole_pair = hole && hole_use_fft(d) && d == 200 && 2 * maxb <= 4 * 4 * 256;
   r->e8 = !hole && ent->acc_mode == SKGE_ACC_I8X4;
   const int nq = d / 4;
@@ -1208,40 +1180,37 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
       FusedTab& F = a.F;
       const size_t sb = (size_t)N * nq * (r->e8 ? 4 : 8);
       F.P[0] = ent->param;
-      F.P[1] = (float*)dalloc(r, (size_t)N * d * 4);
+      F.P[1] = (float*)r->alloc((size_t)N * d * 4, true);
       F.A[0] = t.A;
-      F.A[1] = F.A[0] ? (float*)dalloc(r, (size_t)N * d * 4) : nullptr;
+      F.A[1] = F.A[0] ? (float*)r->alloc((size_t)N * d * 4, true) : nullptr;
       F.sum[0] = ent->acc_sum;
       F.cnt[0] = ent->acc_cnt;
       F.touched[0] = ent->acc_touched;
       for (int k = 1; k < 3; ++k) {
-        F.sum[k] = dalloc(r, sb);
-        F.cnt[k] = (int*)dalloc(r, (size_t)N * 4);
-        F.touched[k] = (int*)dalloc(r, (size_t)4 * bs * 4);
-        ok = ok && F.sum[k] && F.cnt[k] && F.touched[k];
+        F.sum[k] = r->alloc(sb, true);
+        F.cnt[k] = (int*)r->alloc((size_t)N * 4, true);
+        F.touched[k] = (int*)r->alloc((size_t)4 * bs * 4, true);
       }
-      F.meta = (int4*)dalloc(r, (size_t)N * sizeof(int4));
-      ok = ok && F.P[1] && (!F.A[0] || F.A[1]) && F.meta;
+      F.meta = (int4*)r->alloc((size_t)N * sizeof(int4), true);
       r->n_rows = N;
       r->d = d;
     } else {
       // a second accumulator copy, slot records, batch marks, done words
-      t.done = (int*)dalloc(r, (size_t)N * 4);
-      t.sum[1] = (unsigned long long*)dalloc(r, (size_t)N * nq * (hole ? 16 : (r->e8 ? 4 : 8)));
-      t.cnt[1] = (int*)dalloc(r, (size_t)N * 4);
-      t.touched[1] = (int*)dalloc(r, (size_t)4 * bs * 4);
-      t.pend[0] = (int*)dalloc(r, (size_t)N * 4);
-      t.pend[1] = (int*)dalloc(r, (size_t)N * 4);
-      ok = ok && t.done && t.sum[1] && t.cnt[1] && t.touched[1] && t.pend[0] && t.pend[1];
+      t.done = (int*)r->alloc((size_t)N * 4, true);
+      t.sum[1] = (unsigned long long*)r->alloc((size_t)N * nq * (hole ? 16 : (r->e8 ? 4 : 8)),
+                                               true);
+      t.cnt[1] = (int*)r->alloc((size_t)N * 4, true);
+      t.touched[1] = (int*)r->alloc((size_t)4 * bs * 4, true);
+      t.pend[0] = (int*)r->alloc((size_t)N * 4, true);
+      t.pend[1] = (int*)r->alloc((size_t)N * 4, true);
       if (grouped) {
-        t.own[0] = (int*)dalloc(r, (size_t)N * 4);
-        t.own[1] = (int*)dalloc(r, (size_t)N * 4);
-        ok = ok && t.own[0] && t.own[1];
+        t.own[0] = (int*)r->alloc((size_t)N * 4, true);
+        t.own[1] = (int*)r->alloc((size_t)N * 4, true);
       }
       // (the data-parallel form keeps every row in the tables: no hot rows;
       // HolE: the pair form only, fp32 sums of d floats per replica row)
-      if (ok && !r->e8 && !dp && (!hole || (hole_pair && SKGE_HPIPE_HOT)))
-        ok = find_hot_rows(r, as_stream(stream), t, trip, T, nb1, N, d, hole ? d / 2 : nq);
+      if (r->alloc_ok && !r->e8 && !dp && (!hole || (hole_pair && SKGE_HPIPE_HOT)))
+        ok = find_hot_rows(r.get(), as_stream(stream), t, trip, T, nb1, N, d, hole ? d / 2 : nq);
     }
     RelTab& q = a.R;
     const int M = rel->rows;
@@ -1270,23 +1239,18 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
     q.u = upd(rel);
     q.updated = nullptr;
     q.P[0] = rel->param;
-    q.P[1] = (float*)dalloc(r, (size_t)M * d * 4);
+    q.P[1] = (float*)r->alloc((size_t)M * d * 4, true);
     q.A[0] = ada ? rel->state : nullptr;
-    q.A[1] = ada ? (float*)dalloc(r, (size_t)M * d * 4) : nullptr;
+    q.A[1] = ada ? (float*)r->alloc((size_t)M * d * 4, true) : nullptr;
     for (int k = 0; k < 3; ++k)
-      q.acc[k] = (unsigned long long*)dalloc(r, (size_t)q.reps * M * q.rw * 8);
-    ok = ok && q.P[1] && (!ada || q.A[1]) && q.acc[0] && q.acc[1] && q.acc[2];
+      q.acc[k] = (unsigned long long*)r->alloc((size_t)q.reps * M * q.rw * 8, true);
   }
-  r->rec = (int4*)dalloc(r, (size_t)T * sizeof(int4));
-  r->rec_n1 = (int*)dalloc(r, (size_t)T * 4);
-  r->err = (int*)dalloc(r, 4);
-  r->stats = (int*)dalloc(r, (size_t)(nb1 + 3) * 3 * NSHARD * SHARD_STRIDE * 4);
-  int* vsh = (int*)dalloc(r, (size_t)NSHARD * SHARD_STRIDE * 4);
-  if (!ok || !r->rec || !r->rec_n1 || !r->err || !r->stats || !vsh) {
-    set_error("pipelined runner: device allocation failed");
-    pipe_free(r);
-    return nullptr;
-  }
+  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), true);
+  r->rec_n1 = (int*)r->alloc((size_t)T * 4, true);
+  r->err = (int*)r->alloc(4, true);
+  r->stats = (int*)r->alloc((size_t)(nb1 + 3) * 3 * NSHARD * SHARD_STRIDE * 4, true);
+  int* vsh = (int*)r->alloc((size_t)NSHARD * SHARD_STRIDE * 4, true);
+  if (!ok || !r->alloc_ok) return fail("pipelined runner: device allocation failed");
   r->trip = trip;
   r->T = T;
   r->half = perm_half(T);
@@ -1294,10 +1258,7 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   r->ntries = ntries;
   r->seed = seed;
   r->epoch_key = epoch_key;
-  r->set.slots = (const int4*)set;
-  r->set.filter = (const uint32_t*)((const int4*)set + set_capacity);
-  r->set.mask = (uint64_t)(set_capacity - 1);
-  r->set.fmask = (uint64_t)(8 * set_capacity - 1);
+  r->set = triple_set_view(set, set_capacity);
   r->kq = (nq + 63) / 64;
   a.rec = r->rec;
   a.rec_n1 = r->rec_n1;
@@ -1320,11 +1281,7 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
     a.pair_r1 = 1;
   }
   a.tw = r->fft ? hole_fft_table(d) : nullptr;
-  if (r->fft && !a.tw) {
-    set_error("pipelined runner: HolE FFT twiddle table allocation failed");
-    pipe_free(r);
-    return nullptr;
-  }
+  if (r->fft && !a.tw) return fail("pipelined runner: HolE FFT twiddle table allocation failed");
   r->lds = !hole ? 0
            : r->pair ? hole_fft_lds_bytes(d, 1)
            : r->fft ? hole_fft_lds_bytes(d, SKGE_PIPE_WG / 64)
@@ -1379,35 +1336,17 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   }
   hipStream_t st = as_stream(stream);
   if (dp) {   // driven launch by launch by the caller (skge_pipe_runner_dp_*), no graph
-    if (hipStreamSynchronize(st) != hipSuccess) {
-      set_error("hipStreamSynchronize failed");
-      pipe_free(r);
-      return nullptr;
-    }
-    return r;
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("hipStreamSynchronize failed");
+    return r.release();
   }
-  if (hipStreamSynchronize(st) != hipSuccess ||
-      hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    set_error("hipStreamBeginCapture failed");
-    pipe_free(r);
-    return nullptr;
+  if (!r->begin_capture(st)) return nullptr;
+  enqueue_epoch(r.get(), st, nullptr, nullptr);
+  int rc = SKGE_OK;
+  if (hipGetLastError() != hipSuccess) {
+    set_error("pipelined runner: a launch of the captured epoch failed");
+    rc = SKGE_EHIP;
   }
-  enqueue_epoch(r, st, nullptr, nullptr);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (e != hipSuccess || hipGetLastError() != hipSuccess) {
-    set_error("pipelined runner capture failed: %s", hipGetErrorString(e));
-    if (g) (void)hipGraphDestroy(g);
-    pipe_free(r);
-    return nullptr;
-  }
-  r->graph = g;
-  if (hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0) != hipSuccess) {
-    set_error("hipGraphInstantiate failed");
-    pipe_free(r);
-    return nullptr;
-  }
-  return r;
+  return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
 extern "C" skge_pipe_runner_t* skge_pipe_runner_create_ex(
@@ -1456,8 +1395,7 @@ extern "C" int skge_pipe_runner_run(skge_pipe_runner_t* r, void* stream, int nep
   if (r->invalid) return refuse_invalid(r);
   hipStream_t st = as_stream(stream);
   hot_io(r, st, false);
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < nepochs && e == hipSuccess; ++i) e = hipGraphLaunch(r->exec, st);
+  const hipError_t e = r->launch(st, nepochs);
   // the epilogue runs even after a failed launch: hub rows and the fused
   // kernel's second-buffer rows go back to the caller's tables either way
   hot_io(r, st, true);
@@ -1656,4 +1594,4 @@ extern "C" int skge_pipe_runner_hot_rows(const skge_pipe_runner_t* r) {
   return r ? (r->batch.empty() ? 0 : r->batch[0].E.nhot) : -1;
 }
 
-extern "C" void skge_pipe_runner_destroy(skge_pipe_runner_t* r) { pipe_free(r); }
+extern "C" void skge_pipe_runner_destroy(skge_pipe_runner_t* r) { delete r; }

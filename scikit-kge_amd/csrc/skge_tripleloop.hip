@@ -26,7 +26,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "skge_host.h"
+#include "skge_graph_runner.h"
 #include "skge_hole_fft.h"
 
 namespace skge {
@@ -38,6 +38,7 @@ __global__ __launch_bounds__(256) void k_triples_of_epoch(const int4* __restrict
                                                           float* __restrict__ ys) {
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
        j += (long long)gridDim.x * blockDim.x) {
+    // (the host's split of the same epoch: epoch_batches, skge_graph_runner.h)
     const long long s0 = (j / bs) * bs;                       // the batch's first positive
     const long long c = s0 + bs <= T ? bs : T - s0, jj = j - s0;
     const int4 r = rec[j];
@@ -184,10 +185,7 @@ static int launch_hole_logistic_pos(hipStream_t st, const skge_table_t* ent,
 
 using namespace skge;
 
-struct skge_triple_runner {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  int nlaunch = 0;
+struct skge_triple_runner : GraphRunnerCore {
   int4* rec = nullptr;
   int* rec_n1 = nullptr;
   int* trip = nullptr;    // the epoch's labelled triples [3T][3], batch b's at 9 * start_b
@@ -196,85 +194,53 @@ struct skge_triple_runner {
   size_t ws_bytes = 0;
 };
 
-static void triple_runner_free(skge_triple_runner_t* r) {
-  if (!r) return;
-  if (r->exec) (void)hipGraphExecDestroy(r->exec);
-  if (r->graph) (void)hipGraphDestroy(r->graph);
-  if (r->rec) (void)hipFree(r->rec);
-  if (r->rec_n1) (void)hipFree(r->rec_n1);
-  if (r->trip) (void)hipFree(r->trip);
-  if (r->ys) (void)hipFree(r->ys);
-  if (r->ws) (void)hipFree(r->ws);
-  (void)hipGetLastError();   // a failed allocation must not poison later checks
-  delete r;
-}
-
 extern "C" skge_triple_runner_t* skge_triple_runner_create(
     void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
     uint64_t* epoch_key, int ntries, float* loss_total) {
-  auto fail = [](const char* fmt, long long need) -> skge_triple_runner_t* {
-    set_error(fmt, need);
-    return nullptr;
-  };
-  if (!ent || !rel || !trip || !set || !epoch_key) return fail("NULL argument", 0);
-  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("unknown model", 0);
+  if (!ent || !rel) return fail("triple runner: NULL table");
   if (model != SKGE_HOLE && model != SKGE_RESCAL)
-    return fail("logistic loss is defined for HolE and RESCAL only", 0);
-  if (T <= 0 || T > INT32_MAX / 3) return fail("T must be in [1, 2^31 / 3)", 0);
-  if (nbatches < 1 || nbatches > T) return fail("nbatches must be in [1, T]", 0);
-  if (set_capacity < 2 * T || (set_capacity & (set_capacity - 1)))
-    return fail("set capacity must be a power of 2 >= 2T", 0);
-  if (ntries < 1) return fail("ntries >= 1", 0);
-  if (stream == nullptr) return fail("runner needs a non-default stream (graph capture)", 0);
+    return fail("triple runner: logistic loss is defined for HolE and RESCAL only");
+  if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / 3, nbatches,
+                         set_capacity, 2 * T, ntries, stream))
+    return nullptr;
   hipStream_t st = as_stream(stream);
-  // batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268)
-  const int64_t bs = T / nbatches;
-  std::vector<std::pair<int64_t, int64_t>> batches;
-  int64_t maxb = 0;
-  for (int64_t s0 = 0; s0 < T; s0 += bs) {
-    const int64_t c = (s0 + bs <= T) ? bs : T - s0;
-    batches.push_back({s0, c});
-    maxb = std::max(maxb, c);
-  }
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  const int64_t bs = batches.bs, maxb = batches.maxb;
   // the explicit triples' slot map (skge_triple_grad): 2 entity slots per
   // triple; a relation slot per triple (HolE) or per relation (RESCAL's W)
   if (ent->acc_touched && 6 * maxb > ent->touched_cap)
-    return fail("entity accumulator needs 6 * batch_size = %lld touched slots", 6 * maxb);
+    return fail("triple runner: entity accumulator needs 6 * batch_size = %lld touched slots",
+                (long long)(6 * maxb));
   if (rel->acc_touched) {
     const long long need = model == SKGE_RESCAL ? rel->rows : 3 * maxb;
     if (need > rel->touched_cap)
       return fail(model == SKGE_RESCAL
-                      ? "W accumulator needs rel->rows = %lld touched slots"
-                      : "relation accumulator needs 3 * batch_size = %lld touched slots",
+                      ? "triple runner: W accumulator needs rel->rows = %lld touched slots"
+                      : "triple runner: relation accumulator needs 3 * batch_size = %lld touched "
+                        "slots",
                   need);
   }
   // HolE in the wave FFT's range: a positive and both corruptions in one wave
   // straight from the records (SKGE_HOLE_TRIPLES=1 keeps the explicit triples)
   const char* ht = getenv("SKGE_HOLE_TRIPLES");
   const bool hpos = model == SKGE_HOLE && !(ht && atoi(ht)) && hole_logistic_pos_ok(ent, rel, d);
-  const int nb = (int)batches.size();
+  const int nb = batches.size();
   const int Tmax = (int)(3 * maxb);
-  skge_triple_runner_t* r = new skge_triple_runner_t();
+  std::unique_ptr<skge_triple_runner_t> r(new skge_triple_runner_t());
   r->ws_bytes = hpos ? 0 : skge_triple_step_workspace_bytes(model, Tmax, rel->rows, d);
-  if (hipMalloc(&r->rec, (size_t)T * sizeof(int4)) != hipSuccess ||
-      hipMalloc(&r->rec_n1, (size_t)T * sizeof(int)) != hipSuccess ||
-      (!hpos && (hipMalloc(&r->trip, (size_t)T * 9 * sizeof(int)) != hipSuccess ||
-                 hipMalloc(&r->ys, (size_t)T * 3 * sizeof(float)) != hipSuccess)) ||
-      (r->ws_bytes && hipMalloc(&r->ws, r->ws_bytes) != hipSuccess)) {
-    triple_runner_free(r);
-    return fail("triple runner: device allocation failed", 0);
+  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
+  r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
+  if (!hpos) {
+    r->trip = (int*)r->alloc((size_t)T * 9 * sizeof(int), false);
+    r->ys = (float*)r->alloc((size_t)T * 3 * sizeof(float), false);
   }
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  if (!r->alloc_ok) return fail("triple runner: device allocation failed");
   const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d)) {   // before the capture
-    triple_runner_free(r);
-    return fail("triple runner: HolE FFT twiddle table allocation failed", 0);
-  }
-  if (hipStreamSynchronize(st) != hipSuccess ||
-      hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    triple_runner_free(r);
-    return fail("hipStreamBeginCapture failed", 0);
-  }
+  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
+    return fail("triple runner: HolE FFT twiddle table allocation failed");
+  if (!r->begin_capture(st)) return nullptr;
   int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
                                r->rec, r->rec_n1);
   if (!rc && !hpos) {
@@ -302,34 +268,15 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create(
     }
   }
   if (!rc) rc = skge_epoch_advance(stream, epoch_key);
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc || e != hipSuccess) {
-    if (!rc) set_error("hipStreamEndCapture: %s", hipGetErrorString(e));
-    if (g) (void)hipGraphDestroy(g);
-    triple_runner_free(r);
-    return nullptr;
-  }
-  r->graph = g;
-  size_t nnodes = 0;
-  if (hipGraphGetNodes(g, nullptr, &nnodes) == hipSuccess) r->nlaunch = (int)nnodes;
-  e = hipGraphInstantiate(&r->exec, g, nullptr, nullptr, 0);
-  if (e != hipSuccess) {
-    set_error("hipGraphInstantiate: %s", hipGetErrorString(e));
-    triple_runner_free(r);
-    return nullptr;
-  }
-  return r;
+  return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
 extern "C" int skge_triple_runner_run(skge_triple_runner_t* r, void* stream, int nepochs) {
-  SKGE_CHECK_ARG(r && r->exec, "bad runner");
-  for (int i = 0; i < nepochs; ++i) SKGE_CHECK_HIP(hipGraphLaunch(r->exec, as_stream(stream)));
-  return SKGE_OK;
+  return run_graph(r, stream, nepochs);
 }
 
 extern "C" int skge_triple_runner_nlaunches(const skge_triple_runner_t* r) {
-  return r ? r->nlaunch : -1;
+  return r ? r->nnodes : -1;
 }
 
-extern "C" void skge_triple_runner_destroy(skge_triple_runner_t* r) { triple_runner_free(r); }
+extern "C" void skge_triple_runner_destroy(skge_triple_runner_t* r) { delete r; }

@@ -8,6 +8,7 @@ loop (skge_pair_runner_*, csrc/skge_pairloop.hip): one epoch of
 PairwiseStochasticTrainer batches (nbatches full batches + the remainder,
 skge/base.py:1246-1268), captured once into a hipGraph and replayed."""
 import math
+import os as _os
 import timeit
 import warnings
 
@@ -39,10 +40,9 @@ class DeviceKG(object):
 
 
 PACKED_MAX = 32767   # a 16-bit packed field's bound (csrc/skge_pipeline.hip PACKED_MAX)
-import os as _os
 
 
-def _bincount_max(col, n):
+def _row_counts(col, n):
     return torch.bincount(col.long(), minlength=n)
 
 
@@ -67,7 +67,7 @@ def packed_count_bound(kg, n_ent, batch, tail=None):
     B = float(min(int(batch), int(kg.trip.shape[0])))
 
     def per_batch(col):
-        c = _bincount_max(col, n_ent).double()
+        c = _row_counts(col, n_ent).double()
         mu = c * (B / T)
         return torch.minimum(torch.minimum(c, torch.full_like(c, B)), (tail or _tail)(mu))
     occ = per_batch(kg.trip[:, 0]) + per_batch(kg.trip[:, 1])
@@ -101,14 +101,12 @@ def relation_replicas(kg, n_rel, batch, max_reps=32, ranks=1):
     sample of the triples, below the binomial tail of mu = per * count_p / T.
     Each positive adds <= 4 to its relation's count.  Returns 0 when even
     max_reps copies cannot keep 4 * bound <= PACKED_MAX."""
-    cnt = _bincount_max(kg.trip[:, 2], n_rel).double()
+    cnt = _row_counts(kg.trip[:, 2], n_rel).double()
     T = float(max(int(kg.trip.shape[0]), 1))
     reps = 1
     while True:
         per = float(int(ranks) * -(-int(batch) // reps))
-        mu = cnt * (per / T)
-        tail = mu + 12.0 * torch.sqrt(mu) + 40.0
-        bound = torch.minimum(torch.minimum(cnt, torch.full_like(cnt, per)), tail)
+        bound = torch.minimum(torch.minimum(cnt, torch.full_like(cnt, per)), _tail(cnt * (per / T)))
         if 4.0 * float(bound.max().item()) <= PACKED_MAX:
             return reps
         reps *= 2
@@ -130,147 +128,95 @@ def padded_width(d):
     return d32 if d32 <= 1.3 * d else (d + 3) // 4 * 4
 
 
-class EpochRunner(object):
-    """Native hipGraph epoch of the TransE device batch loop (keeps no per-row
-    counters).
+class _Runner(object):
+    """What the device runners share: the stream, the kg / model / nbatches /
+    seed / ntries fields, the epoch key, create-or-raise, run() ordered
+    against the caller's stream, and the handle's release.  A subclass builds
+    its tables, calls _create with its ABI prefix (skge_<prefix>_create / _run
+    / _nlaunches / _destroy, include/skge_hip.h) and overrides synchronize."""
 
-    pipelined: None (auto) uses the one-launch-per-batch pipelined runner
-    (skge_pipe_runner_*) whenever it applies (TransE-L1, packed accumulators,
-    single-copy relation accumulator) and the two-launch runner otherwise;
-    True demands it, False forces the two-launch runner.  Both give identical
-    parameters.
+    pipelined = False
+    counters = False   # keeps the per-row counters (updateCounts, violations)
+    _pad = False
+    graph = None       # dp.DataParallelRunner: the torch graph of its captured epoch
 
-    Packed (exact int16x4) entity sums are used for TransE-L1 unless
-    force_f32, or unless packed_count_bound() says a row's per-batch count
-    could pass 32767 (then fp32 sums: packed=None decides, packed=True
-    insists).  The pipelined runner keeps relation sums as int32x2; the
-    two-launch runner spreads them over relation_replicas() copies.
-    """
-
-    counters = False
-
-    def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 nviol_total=None, force_f32=False, replicas=1, pipelined=None, packed=None):
-        from .transe import TransE
-        if not isinstance(model, TransE):
-            raise NotImplementedError("device_loop supports TransE (the north-star path) only")
+    def _setup(self, model, kg, nbatches, seed, ntries, stream):
         dev = model.device
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.kg = kg
-        self.model = model
+        self.kg, self.model, self.nbatches = kg, model, nbatches
         self.seed, self.ntries = int(seed) & (2 ** 64 - 1), int(ntries)
         self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.nviol_total = nviol_total if nviol_total is not None else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
-        bs = kg.T // nbatches
-        self.nbatches = nbatches
-        self._auto = pipelined is None
-        self.hot_rows = 0   # pipelined TransE: entity rows with replicated sums (skewed KGs)
-        # d % 4 != 0 (e.g. the reference's d = 50): the packed / pipelined
-        # runners work on quads, so they run on zero-padded copies of the
-        # tables (width rounded up to 4), copied in and out around every run().
-        # A zero column stays zero (TransE-L1: sign(0) = 0 contributions, AdaGrad
-        # and the projection leave 0 at 0) and adds nothing to a score or norm,
-        # so the padded step is the d-wide step.
-        self.d_pad = padded_width(model.d)
-        self._pad = (bool(model.l1) and model.d % 4 != 0 and not force_f32 and replicas <= 1
-                     and pipelined is not False and packed is not False
-                     and _os.environ.get("SKGE_PIPE_PAD", "1") != "0")
-        # TransE-L1 sign contributions are small integers: exact packed int16x4
-        # sums while every row's per-batch count stays <= 32767 (the applies
-        # flag a larger count, checked by synchronize())
-        can_pack = bool(model.l1) and (model.d % 4 == 0 or self._pad) and not force_f32
-        self.count_bound = packed_count_bound(kg, model.E.rows, bs) if can_pack else 0
-        auto_packed = packed is None
-        if packed is None:
-            packed = can_pack and self.count_bound <= PACKED_MAX
-        elif packed and not can_pack:
-            raise ValueError("packed sums need TransE-L1, d % 4 == 0 and no force_f32")
-        packed = bool(packed)
-        # the two-launch runner's packed relation sums: hot relations spread
-        # over accumulator copies (0: not even 32 copies suffice)
-        rel_reps = relation_replicas(kg, model.R.rows, bs) if packed else 1
-        E, R = model.params["E"], model.params["R"]
-        can_pipe = packed and replicas <= 1 and pipelined is not False
-        if pipelined and not can_pipe:
-            raise ValueError("pipelined runner needs TransE-L1, d % 4 == 0, packed sums "
-                             "and replicas == 1")
-        if can_pipe and pipelined is None:
-            # the pipelined runner's scratch (auto mode: only if it fits): the
-            # epoch's records and, per entity row, k_pipe_fused (rows of <= 64
-            # floats, batches of <= 16k slot records; skge_pipeline.hip) three
-            # accumulator copies, a second copy of E and its AdaGrad state and a
-            # meta word -- k_pipe_batch two accumulator copies (the table's and
-            # one more, packed 16- or 8-bit fields) and five words (done word,
-            # pending marks and owner marks of both copies)
-            torch.cuda.synchronize(dev)
-            torch.cuda.empty_cache()
-            wd = self.d_pad if self._pad else model.d
-            if wd <= 64 and 4 * bs <= 4 * 4096:
-                acc = E.rows * (E.width * 2 + 4) + 4 * 4 * bs
-                extra = 3 * acc + kg.T * 20 + (64 << 20) + E.rows * (16 + 8 * E.width)
-            else:
-                e8_est = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
-                          _os.environ.get("SKGE_PIPE_E8", "1") != "0")
-                acc = E.rows * ((wd // 4) * (4 if e8_est else 8) + 4) + 2 * 4 * 4 * bs
-                extra = 2 * acc + E.rows * 5 * 4 + kg.T * 20 + (256 << 20)
-            can_pipe = extra < torch.cuda.mem_get_info(dev)[0] * 0.9
-        torch.cuda.current_stream().synchronize()
+
+    def _total(self, given, dtype):
+        """The caller's running total (violations / loss), or the runner's own."""
+        return given if given is not None else torch.zeros(1, dtype=dtype,
+                                                           device=self.model.device)
+
+    def _hold_captured(self):
+        """The graph captures raw pointers to the model's accumulators and
+        counters: hold the tensors, so a later per-batch call that grows the
+        model's slot arrays cannot free what this runner still writes."""
+        m = self.model
+        self._captured = [(a.sum, a.cnt, a.touched) for a in m._acc.values()] + \
+            [p._counters.copy() for p in m.params.values()]
+
+    def _epoch_args(self):
+        kg = self.kg
+        return (L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity, int(self.nbatches), self.seed,
+                L.ptr(self.epoch_key))
+
+    def _create(self, prefix, *args, create=None):
+        """The tables' zero-filled accumulators were made on the current
+        stream and the runner works on its own (a reused allocation could
+        otherwise hold a freed runner's counts when the first launch runs):
+        synchronize, then create or raise with the library's error text."""
         lib = L.lib()
-        if can_pipe:
-            # relation sums in 16-bit fields while a relation's per-batch count
-            # fits them (faster: half the atomics), else int32x2; entity sums in
-            # 8-bit fields while every entity's per-batch count is <= 127 (half
-            # the atomic bytes again; the apply checks every count)
-            e8 = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
-                  _os.environ.get("SKGE_PIPE_E8", "1") != "0")
-            self._tables(model, updaters, packed, 1, rel_w32=rel_reps != 1, ent_i8=e8,
-                         pad=self._pad)
-            # the tables' zero-filled accumulators were made on the current
-            # stream; the runner works on its own (a reused allocation could
-            # otherwise hold a freed runner's counts when the first launch runs)
-            torch.cuda.current_stream().synchronize()
-            self.ent_i8 = e8
-            h = lib.skge_pipe_runner_create(
-                L.stream_ptr(self.stream), self.te, self.tr,
-                self.d_pad if self._pad else model.d, L.ptr(kg.trip), kg.T,
-                L.ptr(kg.slots), kg.capacity, int(nbatches), int(seed) & (2 ** 64 - 1),
-                L.ptr(self.epoch_key), float(model.margin), int(ntries), L.ptr(self.nviol_total))
-            if h:
-                self.pipelined = True
-                self.handle = h
-                self.nlaunches = lib.skge_pipe_runner_nlaunches(h)
-                self.hot_rows = lib.skge_pipe_runner_hot_rows(h)
-                self.kernel = ("k_pipe_batch", "k_pipe_fused")[lib.skge_pipe_runner_kernel(h)]
-                return
-            err = lib.skge_last_error().decode()
-            if not (self._auto and "allocation" in err):
-                raise L.SkgeError("skge_pipe_runner_create: %s" % err)
-            # auto mode: out of device memory -> two-launch runner
-            self.accE = self.accR = self.te = self.tr = None
-            torch.cuda.empty_cache()
-        self.pipelined = False
-        self.kernel = "k_transe_sample_grad"
-        if self._pad:   # the two-launch runner takes any d: no padded copies
-            self._pad = False
-            packed = packed and model.d % 4 == 0
-            rel_reps = relation_replicas(kg, model.R.rows, bs) if packed else 1
-        if packed and rel_reps == 0:
-            if not auto_packed:
-                raise ValueError("packed sums: a relation's per-batch count exceeds what 32 "
-                                 "accumulator copies hold; use packed=None or force_f32=True")
-            packed = False
-        self._tables(model, updaters, packed, max(int(replicas), rel_reps) if packed else replicas)
-        torch.cuda.current_stream().synchronize()   # (as above)
-        h = lib.skge_runner_create(L.stream_ptr(self.stream), int(bool(model.l1)),
-                                   self.te, self.tr,
-                                   model.d, L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity,
-                                   int(nbatches), int(seed) & (2 ** 64 - 1), L.ptr(self.epoch_key),
-                                   float(model.margin), int(ntries), None, L.ptr(self.nviol_total))
+        torch.cuda.current_stream(self.model.device).synchronize()
+        name = create or prefix + "_create"
+        h = getattr(lib, name)(L.stream_ptr(self.stream), *args)
         if not h:
-            raise L.SkgeError("skge_runner_create: %s" % lib.skge_last_error().decode())
-        self.handle = h
-        self.nlaunches = lib.skge_runner_nlaunches(h)
+            raise L.SkgeError("%s: %s" % (name, lib.skge_last_error().decode()))
+        self._abi, self.handle = prefix, h
+        self.nlaunches = getattr(lib, prefix + "_nlaunches")(h)
+
+    def _pad_in(self):
+        pass
+
+    def _pad_out(self):
+        pass
+
+    def _launch(self, nepochs):
+        L.check(getattr(L.lib(), self._abi + "_run")(self.handle, L.stream_ptr(self.stream),
+                                                     int(nepochs)), self._abi + "_run")
+
+    def run(self, nepochs=1):
+        """nepochs epochs on the runner's stream, ordered after the caller's
+        stream (parameters it wrote) and before its later work."""
+        self.stream.wait_stream(torch.cuda.current_stream())
+        self._pad_in()
+        self._launch(nepochs)
+        self._pad_out()
+        torch.cuda.current_stream().wait_stream(self.stream)
+
+    def synchronize(self):
+        self.stream.synchronize()
+        L.check_device_error(L.stream_ptr(self.stream), self._who)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                self.graph = None   # (it names the handle's buffers)
+                self.stream.synchronize()
+                getattr(L.lib(), self._abi + "_destroy")(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+class _PaddedTables(object):
+    """The TransE-L1 runners' own accumulators and tables, over zero-padded
+    copies of the parameters where d % 4 != 0 (EpochRunner, dp.DataParallelRunner)."""
 
     def _tables(self, model, updaters, packed, rel_replicas, rel_w32=False, ent_i8=False,
                 pad=False):
@@ -323,7 +269,7 @@ class EpochRunner(object):
     def _pad_in(self):
         """Padded tables: the model's parameters / states into the copies
         (ordered after the caller's stream)."""
-        if not getattr(self, "_pad", False):
+        if not self._pad:
             return
         d = self.model.d
         self.stream.wait_stream(torch.cuda.current_stream())
@@ -334,7 +280,7 @@ class EpochRunner(object):
                     sp[:, :d].copy_(st)
 
     def _pad_out(self):
-        if not getattr(self, "_pad", False):
+        if not self._pad:
             return
         d = self.model.d
         with torch.cuda.stream(self.stream):
@@ -344,16 +290,26 @@ class EpochRunner(object):
                     st.copy_(sp[:, :d])
         torch.cuda.current_stream().wait_stream(self.stream)
 
-    def run(self, nepochs=1):
-        """nepochs epochs on the runner's stream, ordered after the caller's
-        stream (parameters it wrote) and before its later work."""
-        lib = L.lib()
-        fn = lib.skge_pipe_runner_run if self.pipelined else lib.skge_runner_run
-        self.stream.wait_stream(torch.cuda.current_stream())
-        self._pad_in()
-        L.check(fn(self.handle, L.stream_ptr(self.stream), int(nepochs)), "runner run")
-        self._pad_out()
-        torch.cuda.current_stream().wait_stream(self.stream)
+
+class _PipeRunner(_Runner):
+    """The pipelined runners (skge_pipe_runner_*): their error word and profile()."""
+
+    pipelined = True
+    _packed_hint = ""
+
+    def synchronize(self):
+        """Read the error word; once it is set the runner is invalid (later
+        epochs of this run changed nothing and every later run() is refused)."""
+        self.stream.synchronize()
+        rc = L.lib().skge_pipe_runner_error(self.handle, L.stream_ptr(self.stream))
+        left = "; the tables hold that epoch's partial updates and the runner refuses further runs"
+        if rc < 0:
+            raise L.SkgeError("%s: %s" % (self._who, L.lib().skge_last_error().decode()))
+        if rc & 1:
+            raise L.SkgeError("%s: a cross-workgroup wait timed out%s" % (self._who, left))
+        if rc & 2:
+            raise L.SkgeError("%s: a row's per-batch count exceeded 32767 (packed sums may have "
+                              "wrapped)%s%s" % (self._who, left, self._packed_hint))
 
     def profile(self, trace_launch=None):
         """Pipelined runner only: one eager epoch with HIP events around every
@@ -363,56 +319,151 @@ class EpochRunner(object):
         launch (include/skge_hip.h, skge_pipe_runner_profile)."""
         if not self.pipelined:
             raise ValueError("profile() needs the pipelined runner")
-        import numpy as np
         n = self.nlaunches
         us = np.zeros(n, dtype=np.float32)
         stats = np.zeros((n, 3), dtype=np.int32)
         tr = np.zeros(2 + 6 * self.kg.T + 8 * self.kg.T + 64, dtype=np.uint64) \
             if trace_launch else None
         self.stream.wait_stream(torch.cuda.current_stream())
-        EpochRunner._pad_in(self)   # (also HolePipeRunner.profile: no padded tables there)
+        self._pad_in()
         L.check(L.lib().skge_pipe_runner_profile(
             self.handle, L.stream_ptr(self.stream), us.ctypes.data, stats.ctypes.data, n,
             int(trace_launch or 0), None if tr is None else tr.ctypes.data,
             0 if tr is None else len(tr)), "runner profile")
-        EpochRunner._pad_out(self)
+        self._pad_out()
         if trace_launch:
             return us, stats, tr
         return us, stats
 
-    def synchronize(self):
-        self.stream.synchronize()
-        if not self.pipelined:
-            L.check_device_error(L.stream_ptr(self.stream), "epoch runner")
-        if self.pipelined:
-            rc = L.lib().skge_pipe_runner_error(self.handle, L.stream_ptr(self.stream))
-            if rc < 0:
-                raise L.SkgeError("pipelined runner: %s" % L.lib().skge_last_error().decode())
-            # (the runner is now invalid: later epochs of this run changed
-            # nothing and every later run() is refused)
-            if rc & 1:
-                raise L.SkgeError("pipelined runner: a cross-workgroup wait timed out; the "
-                                  "tables hold that epoch's partial updates and the runner "
-                                  "refuses further runs")
-            if rc & 2:
-                raise L.SkgeError("pipelined runner: a row's per-batch count exceeded 32767 "
-                                  "(packed sums may have wrapped); the tables hold that "
-                                  "epoch's partial updates and the runner refuses further "
-                                  "runs; use force_f32=True")
 
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
+class EpochRunner(_PaddedTables, _PipeRunner):
+    """Native hipGraph epoch of the TransE device batch loop (keeps no per-row
+    counters).
+
+    pipelined: None (auto) uses the one-launch-per-batch pipelined runner
+    (skge_pipe_runner_*) whenever it applies (TransE-L1, packed accumulators,
+    single-copy relation accumulator) and the two-launch runner otherwise;
+    True demands it, False forces the two-launch runner.  Both give identical
+    parameters.
+
+    Packed (exact int16x4) entity sums are used for TransE-L1 unless
+    force_f32, or unless packed_count_bound() says a row's per-batch count
+    could pass 32767 (then fp32 sums: packed=None decides, packed=True
+    insists).  The pipelined runner keeps relation sums as int32x2; the
+    two-launch runner spreads them over relation_replicas() copies.
+    """
+
+    _who = "pipelined runner"
+    _packed_hint = "; use force_f32=True"
+
+    def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
+                 nviol_total=None, force_f32=False, replicas=1, pipelined=None, packed=None):
+        from .transe import TransE
+        if not isinstance(model, TransE):
+            raise NotImplementedError("device_loop supports TransE (the north-star path) only")
+        dev = model.device
+        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self.nviol_total = self._total(nviol_total, torch.int32)
+        bs = kg.T // nbatches
+        self.hot_rows = 0   # pipelined TransE: entity rows with replicated sums (skewed KGs)
+        # d % 4 != 0 (e.g. the reference's d = 50): the packed / pipelined
+        # runners work on quads, so they run on zero-padded copies of the
+        # tables (width rounded up to 4), copied in and out around every run().
+        # A zero column stays zero (TransE-L1: sign(0) = 0 contributions, AdaGrad
+        # and the projection leave 0 at 0) and adds nothing to a score or norm,
+        # so the padded step is the d-wide step.
+        self.d_pad = padded_width(model.d)
+        self._pad = (bool(model.l1) and model.d % 4 != 0 and not force_f32 and replicas <= 1
+                     and pipelined is not False and packed is not False
+                     and _os.environ.get("SKGE_PIPE_PAD", "1") != "0")
+        # TransE-L1 sign contributions are small integers: exact packed int16x4
+        # sums while every row's per-batch count stays <= 32767 (the applies
+        # flag a larger count, checked by synchronize())
+        can_pack = bool(model.l1) and (model.d % 4 == 0 or self._pad) and not force_f32
+        self.count_bound = packed_count_bound(kg, model.E.rows, bs) if can_pack else 0
+        auto_packed = packed is None
+        if packed is None:
+            packed = can_pack and self.count_bound <= PACKED_MAX
+        elif packed and not can_pack:
+            raise ValueError("packed sums need TransE-L1, d % 4 == 0 and no force_f32")
+        packed = bool(packed)
+        # the two-launch runner's packed relation sums: hot relations spread
+        # over accumulator copies (0: not even 32 copies suffice)
+        rel_reps = relation_replicas(kg, model.R.rows, bs) if packed else 1
+        E, R = model.params["E"], model.params["R"]
+        can_pipe = packed and replicas <= 1 and pipelined is not False
+        if pipelined and not can_pipe:
+            raise ValueError("pipelined runner needs TransE-L1, d % 4 == 0, packed sums "
+                             "and replicas == 1")
+        if can_pipe and pipelined is None:
+            # the pipelined runner's scratch (auto mode: only if it fits): the
+            # epoch's records and, per entity row, k_pipe_fused (rows of <= 64
+            # floats, batches of <= 16k slot records; skge_pipeline.hip) three
+            # accumulator copies, a second copy of E and its AdaGrad state and a
+            # meta word -- k_pipe_batch two accumulator copies (the table's and
+            # one more, packed 16- or 8-bit fields) and five words (done word,
+            # pending marks and owner marks of both copies)
+            torch.cuda.synchronize(dev)
+            torch.cuda.empty_cache()
+            wd = self.d_pad if self._pad else model.d
+            if wd <= 64 and 4 * bs <= 4 * 4096:
+                acc = E.rows * (E.width * 2 + 4) + 4 * 4 * bs
+                extra = 3 * acc + kg.T * 20 + (64 << 20) + E.rows * (16 + 8 * E.width)
+            else:
+                e8_est = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
+                          _os.environ.get("SKGE_PIPE_E8", "1") != "0")
+                acc = E.rows * ((wd // 4) * (4 if e8_est else 8) + 4) + 2 * 4 * 4 * bs
+                extra = 2 * acc + E.rows * 5 * 4 + kg.T * 20 + (256 << 20)
+            can_pipe = extra < torch.cuda.mem_get_info(dev)[0] * 0.9
+        lib = L.lib()
+        if can_pipe:
+            # relation sums in 16-bit fields while a relation's per-batch count
+            # fits them (faster: half the atomics), else int32x2; entity sums in
+            # 8-bit fields while every entity's per-batch count is <= 127 (half
+            # the atomic bytes again; the apply checks every count)
+            e8 = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
+                  _os.environ.get("SKGE_PIPE_E8", "1") != "0")
+            self._tables(model, updaters, packed, 1, rel_w32=rel_reps != 1, ent_i8=e8,
+                         pad=self._pad)
+            self.ent_i8 = e8
             try:
-                self.stream.synchronize()
-                lib = L.lib()
-                (lib.skge_pipe_runner_destroy if self.pipelined else lib.skge_runner_destroy)(h)
-            except Exception:
-                pass
-            self.handle = None
+                self._create("skge_pipe_runner", self.te, self.tr,
+                             self.d_pad if self._pad else model.d, *self._epoch_args(),
+                             float(model.margin), self.ntries, L.ptr(self.nviol_total))
+                self.hot_rows = lib.skge_pipe_runner_hot_rows(self.handle)
+                self.kernel = ("k_pipe_batch",
+                               "k_pipe_fused")[lib.skge_pipe_runner_kernel(self.handle)]
+                return
+            except L.SkgeError as e:
+                if not (pipelined is None and "allocation" in str(e)):
+                    raise
+            # auto mode: out of device memory -> two-launch runner
+            self.accE = self.accR = self.te = self.tr = None
+            torch.cuda.empty_cache()
+        self.pipelined = False
+        self.kernel = "k_transe_sample_grad"
+        if self._pad:   # the two-launch runner takes any d: no padded copies
+            self._pad = False
+            packed = packed and model.d % 4 == 0
+            rel_reps = relation_replicas(kg, model.R.rows, bs) if packed else 1
+        if packed and rel_reps == 0:
+            if not auto_packed:
+                raise ValueError("packed sums: a relation's per-batch count exceeds what 32 "
+                                 "accumulator copies hold; use packed=None or force_f32=True")
+            packed = False
+        self._tables(model, updaters, packed, max(int(replicas), rel_reps) if packed else replicas)
+        self._create("skge_runner", int(bool(model.l1)), self.te, self.tr, model.d,
+                     *self._epoch_args(), float(model.margin), self.ntries, None,
+                     L.ptr(self.nviol_total))
+
+    def synchronize(self):
+        if self.pipelined:
+            return _PipeRunner.synchronize(self)
+        self.stream.synchronize()
+        L.check_device_error(L.stream_ptr(self.stream), "epoch runner")
 
 
-class HolePipeRunner(object):
+class HolePipeRunner(_PipeRunner):
     """Pipelined HolE device loop (skge_hole_pipe_runner_create,
     csrc/skge_pipeline.hip k_hole_pipe): the TransE pipelined runner's launch
     structure -- launch g scores batch b (both pairs of a positive per wave,
@@ -422,8 +473,7 @@ class HolePipeRunner(object):
     any order).  Needs d % 4 == 0, 4 <= d <= 256.  Keeps no per-row
     counters."""
 
-    pipelined = True
-    counters = False   # keeps no per-row counters (updateCounts)
+    _who = "pipelined HolE runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
                  nviol_total=None):
@@ -432,13 +482,8 @@ class HolePipeRunner(object):
         if not isinstance(model, HolE):
             raise TypeError("HolePipeRunner trains HolE")
         dev = model.device
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.kg = kg
-        self.model = model
-        self.nbatches = nbatches
-        self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.nviol_total = nviol_total if nviol_total is not None else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
+        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self.nviol_total = self._total(nviol_total, torch.int32)
         E, R = model.params["E"], model.params["R"]
         bs = kg.T // nbatches
         self.accE = Accumulator(E.rows, E.width, dev, slots=4 * bs)
@@ -448,51 +493,17 @@ class HolePipeRunner(object):
                                       rout=reg["E"][1], fixed_div=reg["E"][2])
         self.tr = updaters["R"].table(self.accR, counters=False, rin=reg["R"][0],
                                       rout=reg["R"][1], fixed_div=reg["R"][2])
-        torch.cuda.current_stream().synchronize()
-        lib = L.lib()
-        h = lib.skge_hole_pipe_runner_create(
-            L.stream_ptr(self.stream), model._af_code(), self.te, self.tr, model.d,
-            L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity, int(nbatches),
-            int(seed) & (2 ** 64 - 1), L.ptr(self.epoch_key), float(model.margin), int(ntries),
-            L.ptr(self.nviol_total))
-        if not h:
-            raise L.SkgeError("skge_hole_pipe_runner_create: %s" % lib.skge_last_error().decode())
-        self.handle = h
-        self.nlaunches = lib.skge_pipe_runner_nlaunches(h)
-        self.hot_rows = lib.skge_pipe_runner_hot_rows(h)   # hub rows (pair form, skewed KGs)
+        self._create("skge_pipe_runner", model._af_code(), self.te, self.tr, model.d,
+                     *self._epoch_args(), float(model.margin), self.ntries,
+                     L.ptr(self.nviol_total), create="skge_hole_pipe_runner_create")
+        # hub rows (pair form, skewed KGs)
+        self.hot_rows = L.lib().skge_pipe_runner_hot_rows(self.handle)
 
     @staticmethod
     def eligible(model):
         from .hole import HolE
         d = model.d
         return isinstance(model, HolE) and d % 4 == 0 and 4 <= d <= 256
-
-    def run(self, nepochs=1):
-        self.stream.wait_stream(torch.cuda.current_stream())
-        L.check(L.lib().skge_pipe_runner_run(self.handle, L.stream_ptr(self.stream),
-                                             int(nepochs)), "hole runner run")
-        torch.cuda.current_stream().wait_stream(self.stream)
-
-    profile = EpochRunner.profile
-
-    def synchronize(self):
-        self.stream.synchronize()
-        rc = L.lib().skge_pipe_runner_error(self.handle, L.stream_ptr(self.stream))
-        if rc < 0:
-            raise L.SkgeError("pipelined HolE runner: %s" % L.lib().skge_last_error().decode())
-        if rc & 1:
-            raise L.SkgeError("pipelined HolE runner: a cross-workgroup wait timed out; the "
-                              "runner refuses further runs")
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                self.stream.synchronize()
-                L.lib().skge_pipe_runner_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
 
 
 def batch_sizes(T, nbatches):
@@ -501,7 +512,7 @@ def batch_sizes(T, nbatches):
     return [min(bs, T - s0) for s0 in range(0, T, bs)]
 
 
-class PairLoopRunner(object):
+class PairLoopRunner(_Runner):
     """Native hipGraph epoch of the device pair loop for any model
     (skge_pair_runner_*, csrc/skge_pairloop.hip): the epoch's permutation and
     negatives drawn on the device (the same keyed draws as EpochRunner), every
@@ -514,57 +525,19 @@ class PairLoopRunner(object):
     pairs).  The per-row counters (updateCounts, TransE violations) are kept
     as on that path."""
 
-    pipelined = False
     counters = True    # updateCounts / TransE violations, as on the per-batch path
+    _who = "pair-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
                  nviol_total=None):
-        dev = model.device
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.kg = kg
-        self.model = model
-        self.nbatches = nbatches
-        self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.nviol_total = nviol_total if nviol_total is not None else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
+        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self.nviol_total = self._total(nviol_total, torch.int32)
         P = 2 * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("pairwise", updaters, slots=model._pair_slots(P))
-        # the graph captures raw pointers to the model's accumulators and
-        # counters: hold the tensors, so a later per-batch call that grows the
-        # model's slot arrays cannot free what this runner still writes
-        self._captured = [(a.sum, a.cnt, a.touched) for a in model._acc.values()] + \
-            [p._counters.copy() for p in model.params.values()]
-        torch.cuda.current_stream().synchronize()
-        lib = L.lib()
-        h = lib.skge_pair_runner_create(
-            L.stream_ptr(self.stream), model._kernel_model(), model._af_code(), self.te, self.tr,
-            model.d, L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity, int(nbatches),
-            int(seed) & (2 ** 64 - 1), L.ptr(self.epoch_key), float(model.margin), int(ntries),
-            L.ptr(self.nviol_total))
-        if not h:
-            raise L.SkgeError("skge_pair_runner_create: %s" % lib.skge_last_error().decode())
-        self.handle = h
-        self.nlaunches = lib.skge_pair_runner_nlaunches(h)
-
-    def run(self, nepochs=1):
-        self.stream.wait_stream(torch.cuda.current_stream())
-        L.check(L.lib().skge_pair_runner_run(self.handle, L.stream_ptr(self.stream),
-                                             int(nepochs)), "pair runner run")
-        torch.cuda.current_stream().wait_stream(self.stream)
-
-    def synchronize(self):
-        self.stream.synchronize()
-        L.check_device_error(L.stream_ptr(self.stream), "pair-loop runner")
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                self.stream.synchronize()
-                L.lib().skge_pair_runner_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+        self._hold_captured()
+        self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te, self.tr,
+                     model.d, *self._epoch_args(), float(model.margin), self.ntries,
+                     L.ptr(self.nviol_total))
 
 
 def _require_logistic_model(model):
@@ -573,7 +546,7 @@ def _require_logistic_model(model):
                                   % type(model).__name__)
 
 
-class LogisticLoopRunner(object):
+class LogisticLoopRunner(_Runner):
     """Native hipGraph epoch of the device logistic loop for HolE and RESCAL
     (skge_triple_runner_*, csrc/skge_tripleloop.hip): one epoch of
     StochasticTrainer with RandomModeSampler(1, [0, 1]) (skge/base.py:
@@ -590,58 +563,35 @@ class LogisticLoopRunner(object):
     added into ``loss_total``; the per-row counters (updateCounts) are kept
     as on the per-batch path."""
 
-    pipelined = False
     counters = True
+    _who = "logistic-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
                  loss_total=None):
         _require_logistic_model(model)
-        dev = model.device
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self.kg = kg
-        self.model = model
-        self.nbatches = nbatches
-        self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.loss_total = loss_total if loss_total is not None else \
-            torch.zeros(1, dtype=torch.float32, device=dev)
+        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self.loss_total = self._total(loss_total, torch.float32)
         T3 = 3 * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("logistic", updaters, slots=model._triple_slots(T3))
-        # the graph captures raw pointers to the model's accumulators and
-        # counters: hold the tensors, so a later per-batch call that grows the
-        # model's slot arrays cannot free what this runner still writes
-        self._captured = [(a.sum, a.cnt, a.touched) for a in model._acc.values()] + \
-            [p._counters.copy() for p in model.params.values()]
-        torch.cuda.current_stream().synchronize()
-        lib = L.lib()
-        h = lib.skge_triple_runner_create(
-            L.stream_ptr(self.stream), model._kernel_model(), self.te, self.tr, model.d,
-            L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity, int(nbatches),
-            int(seed) & (2 ** 64 - 1), L.ptr(self.epoch_key), int(ntries),
-            L.ptr(self.loss_total))
-        if not h:
-            raise L.SkgeError("skge_triple_runner_create: %s" % lib.skge_last_error().decode())
-        self.handle = h
-        self.nlaunches = lib.skge_triple_runner_nlaunches(h)
+        self._hold_captured()
+        self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
+                     *self._epoch_args(), self.ntries, L.ptr(self.loss_total))
 
-    def run(self, nepochs=1):
-        self.stream.wait_stream(torch.cuda.current_stream())
-        L.check(L.lib().skge_triple_runner_run(self.handle, L.stream_ptr(self.stream),
-                                               int(nepochs)), "triple runner run")
-        torch.cuda.current_stream().wait_stream(self.stream)
 
-    def synchronize(self):
-        self.stream.synchronize()
-        L.check_device_error(L.stream_ptr(self.stream), "logistic-loop runner")
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                self.stream.synchronize()
-                L.lib().skge_triple_runner_destroy(h)
-            except Exception:
-                pass
-            self.handle = None
+def _fit_epochs(trainer, runner):
+    """The device fits' epoch loop: per epoch _pre_epoch, one graph replay, the
+    runner's error word (read before the post_epoch callbacks, so no callback
+    ever sees parameters from a failed epoch), then the callbacks."""
+    trainer._runner = runner
+    with torch.cuda.stream(runner.stream):
+        for trainer.epoch in range(1, trainer.max_epochs + 1):
+            trainer._pre_epoch()
+            trainer.epoch_start = timeit.default_timer()
+            runner.run(1)
+            runner.synchronize()   # raises on the epoch's error bits
+            for f in trainer.post_epoch:
+                if not f(trainer):
+                    break
 
 
 def logistic_device_optim(trainer, xs, ntries=None):
@@ -656,17 +606,8 @@ def logistic_device_optim(trainer, xs, ntries=None):
     runner = LogisticLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                                 ntries=trainer.ntries if ntries is None else ntries,
                                 loss_total=trainer._loss_dev)
-    trainer._runner = runner
     trainer.batch_size = kg.T // trainer.nbatches
-    with torch.cuda.stream(runner.stream):
-        for trainer.epoch in range(1, trainer.max_epochs + 1):
-            trainer._pre_epoch()
-            trainer.epoch_start = timeit.default_timer()
-            runner.run(1)
-            runner.synchronize()   # raises on the epoch's error bits
-            for f in trainer.post_epoch:
-                if not f(trainer):
-                    break
+    _fit_epochs(trainer, runner)
 
 
 def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None):
@@ -760,13 +701,4 @@ def device_optim(trainer, xs, ntries=None):
     runner = make_runner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                          ntries=trainer.ntries if ntries is None else ntries,
                          nviol_total=trainer._nviol_dev, runner=which)
-    trainer._runner = runner
-    with torch.cuda.stream(runner.stream):
-        for trainer.epoch in range(1, trainer.max_epochs + 1):
-            trainer._pre_epoch()
-            trainer.epoch_start = timeit.default_timer()
-            runner.run(1)
-            runner.synchronize()   # raises on the epoch's error bits
-            for f in trainer.post_epoch:
-                if not f(trainer):
-                    break
+    _fit_epochs(trainer, runner)

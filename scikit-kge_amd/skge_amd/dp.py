@@ -33,11 +33,15 @@ drives the same protocol over gloo with a NumPy compute stand-in
 (tests/dp_numpy.py).  Under the "nccl" backend (RCCL) the whole epoch --
 kernels and all-gathers -- is captured in one hipGraph per rank.
 """
+import os
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .device import (_PaddedTables, _PipeRunner, packed_count_bound, relation_replicas,
+                     padded_width, _tail8, PACKED_MAX)
 
 SKGE_PIPE_DP = 1   # skge_pipe_runner_create_ex flag (include/skge_hip.h)
 
@@ -156,7 +160,7 @@ class DPOps(object):
         L.check(L.lib().skge_pipe_runner_dp_end(r.handle, r.sp), "dp end")
 
 
-class DataParallelRunner(object):
+class DataParallelRunner(_PaddedTables, _PipeRunner):
     """TransE-L1 PairwiseStochasticTrainer epochs (margin, strict >,
     RandomModeSampler(1, [0, 1]) negatives drawn on the device) of ONE model
     replicated over the ranks of a process group.
@@ -172,20 +176,21 @@ class DataParallelRunner(object):
     and runs eagerly under gloo.
     """
 
+    _who = "data-parallel runner"
+
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, group=None, stream=None,
                  capture=None):
         from .transe import TransE
-        from .device import (EpochRunner, packed_count_bound, relation_replicas, padded_width,
-                             _tail8, PACKED_MAX)
-        import os
         if not isinstance(model, TransE) or not model.l1 or model.d > 1024:
             raise ValueError("data-parallel runner: TransE-L1 with d <= 1024")
+        T = kg.T
+        if not 1 <= nbatches <= T:
+            raise ValueError("nbatches must be in [1, T]")
         self.ex = DPExchange(group)
         self.G, self.rank = self.ex.G, self.ex.rank
-        self.model, self.kg = model, kg
+        self._setup(model, kg, nbatches, seed, ntries, stream)
         dev = model.device
         self.device = dev
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
         self.sp = L.stream_ptr(self.stream)
         # d % 4 != 0 (the reference's d = 50): the kernels work on quads, so
         # they run on zero-padded copies of the tables and AdaGrad states (as
@@ -196,12 +201,6 @@ class DataParallelRunner(object):
         self._pad = model.d % 4 != 0
         self.d = self.d_pad if self._pad else int(model.d)
         self.margin = float(model.margin)
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.ntries = int(ntries)
-        T = kg.T
-        if not 1 <= nbatches <= T:
-            raise ValueError("nbatches must be in [1, T]")
-        self.nbatches = nbatches
         bs = T // nbatches
         self.batches = [(s0, min(bs, T - s0)) for s0 in range(0, T, bs)]
         if packed_count_bound(kg, model.E.rows, bs) > PACKED_MAX:
@@ -214,22 +213,15 @@ class DataParallelRunner(object):
         e8 = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
               os.environ.get("SKGE_PIPE_E8", "1") != "0")
         # the one-GPU pipelined runner's tables (same encodings: the same sums)
-        EpochRunner._tables(self, model, updaters, True, 1, rel_w32=rel_reps != 1, ent_i8=e8,
-                            pad=self._pad)
+        self._tables(model, updaters, True, 1, rel_w32=rel_reps != 1, ent_i8=e8, pad=self._pad)
         self.rec_bytes = int(L.lib().skge_pipe_dp_record_bytes(self.d))
         share_max = -(-bs // self.G)
         self.recv = torch.zeros((self.G * max(share_max, 1) + 1) * self.rec_bytes,
                                 dtype=torch.uint8, device=dev)
-        self.nviol_total = torch.zeros(1, dtype=torch.int32, device=dev)   # this rank's slices
-        self.epoch_key = torch.zeros(1, dtype=torch.int64, device=dev)
-        torch.cuda.current_stream(dev).synchronize()   # the zero fills, before the runner's stream
-        h = L.lib().skge_pipe_runner_create_ex(
-            self.sp, self.te, self.tr, self.d, L.ptr(kg.trip), kg.T, L.ptr(kg.slots), kg.capacity,
-            int(nbatches), self.seed, L.ptr(self.epoch_key), self.margin, self.ntries,
-            L.ptr(self.nviol_total), SKGE_PIPE_DP)
-        if not h:
-            raise L.SkgeError("data-parallel runner: %s" % L.lib().skge_last_error().decode())
-        self.handle = h
+        self.nviol_total = self._total(None, torch.int32)   # this rank's slices
+        self._create("skge_pipe_runner", self.te, self.tr, self.d, *self._epoch_args(), self.margin,
+                     self.ntries, L.ptr(self.nviol_total), SKGE_PIPE_DP,
+                     create="skge_pipe_runner_create_ex")
         self.ops = DPOps(self)
         if capture is None:
             capture = self.ex.backend in (None, "nccl")
@@ -245,24 +237,7 @@ class DataParallelRunner(object):
     def _epoch(self):
         dp_epoch(self.ops, self.ex, self.batches)
 
-    def _pad_in(self):
-        from .device import EpochRunner
-        EpochRunner._pad_in(self)
-
-    def _pad_out(self):
-        from .device import EpochRunner
-        EpochRunner._pad_out(self)
-
-    def run(self, nepochs=1):
-        # ordered after the caller's stream (parameters it wrote), and its later
-        # work after the epochs
-        self.stream.wait_stream(torch.cuda.current_stream())
-        self._pad_in()
-        self._run(nepochs)
-        self._pad_out()
-        torch.cuda.current_stream().wait_stream(self.stream)
-
-    def _run(self, nepochs):
+    def _launch(self, nepochs):
         with torch.cuda.stream(self.stream):
             for _ in range(int(nepochs)):
                 if not self.capture:
@@ -280,29 +255,6 @@ class DataParallelRunner(object):
                     continue
                 self.graph.replay()
 
-    def synchronize(self):
-        self.stream.synchronize()
-        rc = L.lib().skge_pipe_runner_error(self.handle, self.sp)
-        if rc < 0:
-            raise L.SkgeError("data-parallel runner: %s" % L.lib().skge_last_error().decode())
-        if rc & 1:
-            raise L.SkgeError("data-parallel runner: a cross-workgroup wait timed out; the "
-                              "runner refuses further runs")
-        if rc & 2:
-            raise L.SkgeError("data-parallel runner: a row's per-batch count exceeded 32767 "
-                              "(packed sums may have wrapped); the runner refuses further runs")
-
     def total_violations(self):
         """Violating pairs of all ranks (every pair is scored by one rank)."""
         return self.ex.sum_int(int(self.nviol_total.item()))
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            try:
-                self.graph = None
-                self.stream.synchronize()
-                L.lib().skge_pipe_runner_destroy(h)
-            except Exception:
-                pass
-            self.handle = None

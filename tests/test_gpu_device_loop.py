@@ -497,3 +497,95 @@ def test_pipelined_padded_width_equals_aligned_model(n_ent, n_rel, T, d, nb):
     for k in ("E", "R", "pE", "pR"):
         assert np.array_equal(a[k], b[k]), k
 
+
+
+# ---- the runners' shared core (csrc/skge_graph_runner.h): ownership, geometry ----
+
+CORE_KG = dict(n_ent=11, n_rel=3, T=37, d=8)
+CORE_RUNNERS = ["epoch", "hole_pipe", "pairs", "logistic"]
+
+
+def _core_make(which, nb, seed=5, **kw):
+    """A fresh model (fixed initial parameters), its updaters and a factory of
+    the runner class `which`."""
+    import skge_amd as S
+    from skge_amd import device as D
+    c = CORE_KG
+    np.random.seed(31)
+    cls = S.TransE if which in ("epoch", "pairs") else S.HolE
+    m = cls((c["n_ent"], c["n_ent"], c["n_rel"]), c["d"])
+    if which != "logistic":
+        m.add_hyperparam("margin", 2.0)
+    # SGD for the float-atomic runner: its tolerance below is argued for linear steps
+    U = S.SGD if which == "hole_pipe" else S.AdaGrad
+    upd = {pid: U(p, 0.1) for pid, p in m.params.items()}
+    kg = D.DeviceKG(make_kg(c["n_ent"], c["n_rel"], c["T"], seed=4)[0], m.device)
+    rcls = {"epoch": D.EpochRunner, "hole_pipe": D.HolePipeRunner, "pairs": D.PairLoopRunner,
+            "logistic": D.LogisticLoopRunner}[which]
+    return m, upd, lambda: rcls(m, upd, kg, nb, seed=seed, **kw)
+
+
+def _core_train(m, upd, r):
+    r.run(2)
+    r.synchronize()
+    out = {pid: p.data.cpu().numpy().copy() for pid, p in m.params.items()}
+    for pid, u in upd.items():
+        if u.state() is not None:
+            out[pid + "_state"] = u.state().cpu().numpy().copy()
+    return out
+
+
+@pytest.mark.parametrize("which", CORE_RUNNERS)
+def test_runner_made_after_twenty_destroyed_trains_like_the_first(which):
+    """Create and destroy a runner 20 times, then one more: it trains a fresh
+    model to what a runner made first trains it to (a buffer dropped from the
+    core's ownership list, or freed twice, would show here).  Bitwise for the
+    TransE-L1 runners (integer sign sums) and for the logistic loop under
+    set_deterministic (fixed-point sums).  HolePipeRunner adds fp32 atomics in
+    any order: a row's per-batch sum has <= 4 * 7 = 28 terms, so two orders
+    differ by <= 28 * 2^-24 = 1.7e-6 of the terms' magnitude (O(1)); an SGD
+    step (lr 0.1) carries 1.7e-7 of that, 12 steps (2 epochs x 6 batches)
+    with the feedback through the O(1)-Lipschitz gradient (e^1.2 = 3.3) stay
+    below 12 * 1.7e-7 * 3.3 = 6.7e-6; bound 1e-5."""
+    import skge_amd as S
+    prev = S.deterministic()
+    S.set_deterministic(which == "logistic")
+    try:
+        m, upd, make = _core_make(which, 5)
+        want = _core_train(m, upd, make())
+        m, upd, make = _core_make(which, 5)
+        for _ in range(20):
+            r = make()
+            del r
+        got = _core_train(m, upd, make())
+    finally:
+        S.set_deterministic(prev)
+    for k in want:
+        if which == "hole_pipe":
+            assert float(np.max(np.abs(got[k] - want[k]))) <= 1e-5, k
+        else:
+            assert np.array_equal(got[k], want[k]), k
+
+
+# nlaunches at T = 37, nbatches = 5 (bs = 7: five batches of 7 and a remainder
+# of 2), as the runners reported before they shared epoch_batches: the
+# two-launch runner ("epoch2") counts 2 launches per batch + the epoch end, the
+# pipelined ones a launch per batch + the flush + the draw + the end, the pair
+# and logistic loops their graph's nodes
+CORE_NLAUNCHES = {"epoch": 9, "epoch2": 13, "hole_pipe": 9, "pairs": 15, "logistic": 14}
+
+
+def test_remainder_batch_geometry_is_the_runners():
+    from skge_amd import device as D
+    c = CORE_KG
+    sizes = D.batch_sizes(c["T"], 5)
+    assert sizes == [7, 7, 7, 7, 7, 2]
+    got = {}
+    for which in CORE_RUNNERS:
+        got[which] = _core_make(which, 5)[2]().nlaunches
+    two = _core_make("epoch", 5, pipelined=False)[2]()
+    assert not two.pipelined
+    got["epoch2"] = two.nlaunches
+    print("nlaunches", got)
+    assert got == CORE_NLAUNCHES
+    assert len(sizes) == (got["epoch2"] - 1) // 2 == got["epoch"] - 3 == got["hole_pipe"] - 3
