@@ -485,7 +485,10 @@ __global__ __launch_bounds__(SKGE_PIPE_WG) void k_hole_pipe(PipeArgs a) {
     const int nR = a.R.rows;
     const int wa = blk_a * wpb + wave;
     const unsigned long long ta0 = a.trace ? now_10ns() : 0ull;
-    if (a.b == a.nb1 && wa == 0) fold_shards(a.nviol_shards, a.nviol_total);
+    if (a.b == a.nb1 && wa == 0) {
+      fold_shards(a.nviol_shards, a.nviol_total);
+      advance_key(a);
+    }
     // items w = wa, wa + S, ...: relation rows w < nR, hot rows, then entity
     // slots w - nR - nH
     const int S = a.nA * wpb;

@@ -105,7 +105,11 @@ struct PipeArgs {
   uint32_t* dprec;             // data-parallel: one record per scored positive (pipe_dp_record_words)
   int prev_slots;              // A role: entity slots of the previous batch
   int b, nb1;                  // batch index in the epoch (nb1: the flush), batches per epoch
-  const uint64_t* epoch_key;
+  const uint64_t* epoch_key;   // the key word the launches read: the runner's own copy, which
+                               // k_epoch_sample fills from the caller's word at the head of
+                               // every epoch (the data-parallel form: the caller's word)
+  uint64_t* key_next;          // the flush of a graph runner: the caller's word, which gets
+                               // key + 1 -- a word no wave of the launch reads; else nullptr
   int d, nA;                   // nA: workgroups of the A role
   int af;                      // HolE: activation (skge/actfun.py)
   float margin;
@@ -139,6 +143,14 @@ __device__ __forceinline__ float4 untern4q(uint32_t b) {
 // zero-initialised marks never look pending.
 __device__ __forceinline__ int launch_id(const PipeArgs& a) {
   return (int)(*a.epoch_key * (uint64_t)(a.nb1 + 1)) + a.b + 2;
+}
+
+// The key advance, by the first wave of the flush launch (no launch of its
+// own): the caller's word gets key + 1.  Every wave of the epoch's launches,
+// the flush's included, reads the runner's copy, so nothing reads what this
+// writes before the next epoch's k_epoch_sample does.
+__device__ __forceinline__ void advance_key(const PipeArgs& a) {
+  if (a.key_next && lane_id() == 0) *a.key_next = *a.epoch_key + 1;
 }
 
 // 16-B write-through (sc1) row accesses through a buffer descriptor over one

@@ -54,10 +54,13 @@ namespace skge {
 #define SKGE_HPIPE_HOT 1
 #endif
 
-// k_pipe_batch (every runner but the one k_pipe_fused below takes: batches of
-// up to 16k slot records with rows of up to 64 floats, one GPU; see
-// pipe_create's r->fused): nA apply workgroups (dispatched first: they
-// start the hand-offs the scoring waves may wait on), then the scoring ones.
+// k_pipe_batch: the runners k_pipe_fused (below) does not take.  pipe_create's
+// r->fused is the rule: the fused kernel by default for one-GPU TransE with
+// batches of up to 16k slot records and rows of up to 64 floats
+// (SKGE_PIPE_FUSED=0 / 1 forces either, up to 256 floats); this kernel for
+// wider rows, larger batches and the data-parallel form.  nA apply workgroups
+// (dispatched first: they start the hand-offs the scoring waves may wait on),
+// then the scoring ones.
 // GRP: owner marks, GRP_ROWS owner rows per apply round trip.
 // DP: the data-parallel form (a slice [lo, hi) of the batch scored, records
 // written); its own instance, so the one-GPU kernel keeps round 5's code (the
@@ -91,8 +94,10 @@ __global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG) void k_pipe_batch
     const unsigned long long ta0 = a.trace ? now_10ns() : 0ull;
     // the flush scores nothing: plain stores (WN18 nb = 2, same box: 496 -> 539 M)
     const bool wt = a.b < a.nb1;
-    if (a.b == a.nb1 && wa == 0)   // the flush: fold the epoch's violation count
+    if (a.b == a.nb1 && wa == 0) {   // the flush: fold the epoch's violation count, advance the key
       fold_shards(a.nviol_shards, a.nviol_total);
+      advance_key(a);
+    }
     for (int w = wa; w < total; w += a.nA * wpb) {
       if (w < nR) {
         rel_publish<KQ, W32>(a, w, rd, rw, ra_prev, ra_old);
@@ -418,7 +423,10 @@ __global__ __launch_bounds__(SKGE_PIPE_WG) void k_pipe_fused(PipeArgs a) {
   const int nR = a.R.rows;
   const int w0 = (int)blockIdx.x * wpb + (int)(threadIdx.x >> 6);
   const int nwv = (int)gridDim.x * wpb;
-  if (flush && w0 == 0) fold_shards(a.nviol_shards, a.nviol_total);   // the epoch's violations
+  if (flush && w0 == 0) {   // the epoch's violations, the key advance
+    fold_shards(a.nviol_shards, a.nviol_total);
+    advance_key(a);
+  }
   unsigned long long* const racc0 = opaque_ptr(a.R.acc[ra_cur]);
   const size_t rrep = (size_t)a.R.rows * a.R.rw;   // words per relation replica
   const int rmask = a.R.reps - 1;
@@ -650,6 +658,8 @@ __global__ __launch_bounds__(256) void k_fused_fin(FusedTab F, int rows, int d) 
   }
 }
 
+// the key advance as a launch of its own: the data-parallel form's dp_end and
+// profile()'s eager epoch (a graph runner's flush advances the key: advance_key)
 __global__ void k_pipe_advance(uint64_t* ek) { *ek += 1; }
 
 // Large TransE batches (RelTab::reps > 1): after batch launch g, fold the
@@ -762,33 +772,17 @@ __global__ __launch_bounds__(256) void k_pipe_dp_scatter(PipeArgs a, const uint3
 // once the error has been read (skge_pipe_runner_error)
 __global__ void k_epoch_sample(const int* __restrict__ trip, long long T, int half, uint64_t seed,
                                const uint64_t* ekp, TripleSet set, int n_ent, int ntries,
-                               int4* rec, int* rec_n1, const int* err) {
+                               int4* rec, int* rec_n1, const int* err, uint64_t* key_copy) {
   const uint64_t ek = *ekp;
+  // pipelined graph runners: the epoch's launches read this copy of the key,
+  // so the flush can write the caller's word (PipeArgs::key_next)
+  if (key_copy && blockIdx.x == 0 && threadIdx.x == 0) *key_copy = ek;
   if (err && *err) ntries = 0;
   const Perm pm = {(uint64_t)T, half, epoch_perm_key(seed, ek)};
   const uint64_t skey = epoch_sample_key(seed, ek);
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
-       j += (long long)gridDim.x * blockDim.x) {
-    const long long t = (long long)perm_index((uint64_t)j, pm);
-    const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
-    int neg0 = -1, neg1 = -1;
-    for (int tr = 0; tr < ntries; ++tr) {
-      const int c = draw(skey, j, 0, tr, n_ent);
-      if (!set_contains(set, c, o, p)) {
-        neg0 = c;
-        break;
-      }
-    }
-    for (int tr = 0; tr < ntries; ++tr) {
-      const int c = draw(skey, j, 1, tr, n_ent);
-      if (!set_contains(set, s, c, p)) {
-        neg1 = c;
-        break;
-      }
-    }
-    rec[j] = make_int4(s, o, p, neg0);
-    rec_n1[j] = neg1;
-  }
+       j += (long long)gridDim.x * blockDim.x)
+    sample_record(trip, pm, skey, set, n_ent, ntries, j, rec, rec_n1);
 }
 
 int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t seed,
@@ -797,7 +791,8 @@ int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t s
   long long blocks = (T + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, trip, T,
-                     perm_half(T), seed, epoch_key, set, n_ent, ntries, rec, rec_n1, nullptr);
+                     perm_half(T), seed, epoch_key, set, n_ent, ntries, rec, rec_n1, nullptr,
+                     nullptr);
   SKGE_CHECK_LAUNCH("epoch sample");
   return SKGE_OK;
 }
@@ -815,7 +810,8 @@ struct skge_pipe_runner : GraphRunnerCore {
   long long T = 0;
   int half = 0, n_ent = 0, ntries = 0, kq = 1;
   uint64_t seed = 0;
-  uint64_t* epoch_key = nullptr;
+  uint64_t* epoch_key = nullptr;   // the caller's word
+  uint64_t* key_copy = nullptr;    // graph runners: the word the epoch's launches read
   TripleSet set;
   int4* rec = nullptr;
   int* rec_n1 = nullptr;
@@ -914,8 +910,10 @@ static void launch_pipe_batch(const skge_pipe_runner* r, dim3 gr, hipStream_t st
 #undef SKGE_PB
 }
 
-// Enqueue one epoch: draw the negatives, nb1 batch launches, the flush, the
-// key advance.  ev (optional, nlaunch + 1 events) brackets every launch;
+// Enqueue one epoch: draw the negatives, nb1 batch launches, the flush (which
+// advances the key).  ev (profile(): nlaunch + 1 events) brackets every launch
+// and, in that eager epoch only, a key advance as a launch of its own (its
+// flush leaves the key alone), so us_out keeps its draw and advance entries;
 // stats (optional) collects per-launch claim / violation counts.
 static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t* ev, int* stats,
                           int trace_launch = -1, unsigned long long* trace = nullptr) {
@@ -926,7 +924,7 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, r->trip, r->T,
                        r->half, r->seed, (const uint64_t*)r->epoch_key, r->set, r->n_ent,
-                       r->ntries, r->rec, r->rec_n1, (const int*)r->err);
+                       r->ntries, r->rec, r->rec_n1, (const int*)r->err, r->key_copy);
   }
   ++i;
   if (ev) (void)hipEventRecord(ev[i], st);
@@ -939,6 +937,7 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
       a.stats_viol = stats + (3 * i + 2) * sh;
     }
     if (trace && i == trace_launch) a.trace = trace;
+    if (ev) a.key_next = nullptr;   // (k_pipe_advance below)
     if (r->hole) {
       launch_hole_pipe(km_for(a.d), r->pair, r->fft, dim3(r->grid[k]),
                        dim3(r->pair ? 128 : SKGE_PIPE_WG), r->lds, st, a);
@@ -957,8 +956,10 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
     }
     if (ev) (void)hipEventRecord(ev[i + 1], st);
   }
-  hipLaunchKernelGGL(k_pipe_advance, dim3(1), dim3(1), 0, st, r->epoch_key);
-  if (ev) (void)hipEventRecord(ev[i + 1], st);
+  if (ev) {
+    hipLaunchKernelGGL(k_pipe_advance, dim3(1), dim3(1), 0, st, r->epoch_key);
+    (void)hipEventRecord(ev[i + 1], st);
+  }
 }
 
 // Hot rows around a run: before the first launch g0 (from the epoch key) the
@@ -996,8 +997,8 @@ __global__ __launch_bounds__(256) void k_hot_io(PipeTab t, int nb1, const uint64
 static void hot_io(const skge_pipe_runner* r, hipStream_t st, bool back) {
   if (r->batch.empty() || r->batch[0].E.nhot == 0) return;
   const PipeArgs& a = r->batch[0];
-  hipLaunchKernelGGL(k_hot_io, dim3(64), dim3(256), 0, st, a.E, a.nb1, a.epoch_key, a.d,
-                     back ? 1 : 0);
+  hipLaunchKernelGGL(k_hot_io, dim3(64), dim3(256), 0, st, a.E, a.nb1,
+                     (const uint64_t*)r->epoch_key, a.d, back ? 1 : 0);
 }
 
 // fused runner: every row back into the caller's tables (buffer 0), meta cleared
@@ -1248,6 +1249,7 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), true);
   r->rec_n1 = (int*)r->alloc((size_t)T * 4, true);
   r->err = (int*)r->alloc(4, true);
+  r->key_copy = dp ? nullptr : (uint64_t*)r->alloc(8, true);
   r->stats = (int*)r->alloc((size_t)(nb1 + 3) * 3 * NSHARD * SHARD_STRIDE * 4, true);
   int* vsh = (int*)r->alloc((size_t)NSHARD * SHARD_STRIDE * 4, true);
   if (!ok || !r->alloc_ok) return fail("pipelined runner: device allocation failed");
@@ -1263,7 +1265,7 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   a.rec = r->rec;
   a.rec_n1 = r->rec_n1;
   a.nb1 = nb1;
-  a.epoch_key = epoch_key;
+  a.epoch_key = dp ? epoch_key : r->key_copy;
   a.d = d;
   a.margin = margin;
   a.nviol_total = nviol_total;
@@ -1294,6 +1296,7 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
     a.lo = 0;
     a.hi = a.count;
     a.dprec = nullptr;
+    a.key_next = !dp && b == nb1 ? epoch_key : nullptr;
     const int cprev = b >= 1 ? (int)batches[b - 1].second : 0;
     a.prev_slots = 4 * cprev;
     if (r->fused) {
@@ -1504,7 +1507,7 @@ extern "C" int skge_pipe_runner_dp_begin(skge_pipe_runner_t* r, void* stream) {
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
                      r->trip, r->T, r->half, r->seed, (const uint64_t*)r->epoch_key, r->set,
-                     r->n_ent, r->ntries, r->rec, r->rec_n1, (const int*)r->err);
+                     r->n_ent, r->ntries, r->rec, r->rec_n1, (const int*)r->err, nullptr);
   SKGE_CHECK_LAUNCH("dp epoch sample");
   return SKGE_OK;
 }

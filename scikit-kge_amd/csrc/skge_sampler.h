@@ -59,4 +59,33 @@ __device__ __forceinline__ int draw(uint64_t skey, long long j, int mode, int tr
   return (int)(((uint64_t)h * (uint32_t)n) >> 32);
 }
 
+// The record of the epoch's positive j (position j of the keyed permutation):
+// (s, o, p, s') and o', each negative the first of ntries draws that is not a
+// training triple, or -1 (skge/sample.py:41-46; ntries == 0 draws none).
+// k_epoch_sample draws a whole epoch with it; any other place that draws
+// records calls this body, so the pairs are the same bits.
+__device__ __forceinline__ void sample_record(const int* __restrict__ trip, const Perm& pm,
+                                              uint64_t skey, const TripleSet& set, int n_ent,
+                                              int ntries, long long j, int4* rec, int* rec_n1) {
+  const long long t = (long long)perm_index((uint64_t)j, pm);
+  const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
+  int neg0 = -1, neg1 = -1;
+  for (int tr = 0; tr < ntries; ++tr) {
+    const int c = draw(skey, j, 0, tr, n_ent);
+    if (!set_contains(set, c, o, p)) {
+      neg0 = c;
+      break;
+    }
+  }
+  for (int tr = 0; tr < ntries; ++tr) {
+    const int c = draw(skey, j, 1, tr, n_ent);
+    if (!set_contains(set, s, c, p)) {
+      neg1 = c;
+      break;
+    }
+  }
+  rec[j] = make_int4(s, o, p, neg0);
+  rec_n1[j] = neg1;
+}
+
 }  // namespace skge
