@@ -598,6 +598,33 @@ int skge_rank(void *stream, int model, const float *E, const float *R, int N, in
               const int *queries, int nq, const void *set, int64_t set_capacity,
               void *workspace, size_t ws_bytes, int *ranks_out);
 
+/*
+ * Top-k link prediction: for each query i = (anchor a, relation p) of
+ * queries[nq][2], the k best entities j as the tail of (a, p, j) (direction 0)
+ * or the head of (j, p, a) (direction 1), scored with the query vectors and
+ * the sequential fp32 chain of the ranking entry points above.
+ *
+ * ONE DIFFERENCE from skge_rank / skge_rank_known: those score both TransE
+ * codes with the L1 distance (the reference evaluator's form); here
+ * SKGE_TRANSE_L1 scores -sum|q - E_j| and SKGE_TRANSE_L2 scores
+ * -sum (q - E_j)^2, the model's own training score.  Pass SKGE_TRANSE_L1 for
+ * an L2-trained model to get the evaluator's order.
+ *
+ * excl_off [nq + 1] / excl_ent: per query, entity ids that are never returned
+ * (int32, ascending and unique within a query); excl_off NULL = none.
+ * Result: ent_out / score_out [nq][k], ordered by descending score, then
+ * ascending entity id among exactly equal fp32 scores; when fewer than k
+ * entities are eligible (k > N is legal) the remaining slots hold entity -1
+ * and score -inf.  1 <= k <= 128, d <= 1024; ids are not range-checked here.
+ * Caller-owned buffers, stream-ordered; workspace of
+ * skge_topk_workspace_bytes(nq, d, k, N) bytes.
+ */
+size_t skge_topk_workspace_bytes(int nq, int d, int k, int N);
+int skge_topk(void *stream, int model, const float *E, const float *R, int N, int d,
+              const int *queries, int nq, int direction, int k, const int *excl_off,
+              const int *excl_ent, void *workspace, size_t ws_bytes, int *ent_out,
+              float *score_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,4 +11,5 @@ from .rescal import RESCAL
 from .param import Parameter, SGD, AdaGrad, normalize, normless1
 from .sample import RandomModeSampler
 from .eval import FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores
+from .predict import LinkPredictor
 from .checkpoint import save_reference, load_reference, read_reference_state

@@ -58,6 +58,9 @@ SIGNATURES = {
     "skge_rank_known_workspace_bytes": (c_sz, [c_i, c_i]),
     "skge_rank_known": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p,
                               c_sz, c_p]),
+    "skge_topk_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "skge_topk": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_sz,
+                        c_p, c_p]),
     "skge_pair_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),

@@ -1,0 +1,152 @@
+"""Top-k link prediction on the device: which entities complete (s, p, ?) or
+(?, p, o).
+
+``LinkPredictor(model, known_triples).tails(s, p, k)`` / ``.heads(o, p, k)``
+score every entity against each query and return the k best in one
+``skge_topk`` call (csrc/skge_topk.hip): entity ids int64 [n, k] and scores
+float32 [n, k], ordered by descending score, then ascending id among exactly
+equal scores; when fewer than k entities are eligible the remaining slots
+hold id -1 and score -inf.
+
+scoring="eval" scores as FilteredRankingEval ranks (any TransE by the L1
+distance); scoring="model" uses the model's own score (the squared L2
+distance for ``TransE(l1=False)``).
+"""
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .eval import _model_code, check_triple_ids
+from .util import triples_array
+
+K_MAX = 128
+_CACHE_ENTRIES = 8
+
+
+def _check_ids(ids, n, what, kind):
+    """Raise ValueError naming the first of ``ids`` outside 0 .. n - 1."""
+    bad = (ids < 0) | (ids >= n)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("%s: query %d has %s %d, out of range for %d"
+                         % (what, i, kind, int(ids[i]), n))
+
+
+class LinkPredictor(object):
+    """model: a TransE, HolE or RESCAL; known_triples: every known (s, o, p),
+    the filter of ``filtered=True``."""
+
+    def __init__(self, model, known_triples=None, scoring="eval"):
+        if scoring not in ("eval", "model"):
+            raise ValueError("scoring must be 'eval' or 'model', not %r" % (scoring,))
+        self.model = model
+        self.scoring = scoring
+        self._known = None if known_triples is None else triples_array(known_triples)
+        self._answers = None   # ({(s, p): tails}, {(o, p): heads})
+        self._csr = {}         # per device and query set: the exclusion CSR
+
+    def tails(self, s, p, k=10, filtered=True, exclude=None):
+        """The k best objects of (s, p, ?)."""
+        return self._topk(s, p, k, filtered, exclude, 0)
+
+    def heads(self, o, p, k=10, filtered=True, exclude=None):
+        """The k best subjects of (?, p, o)."""
+        return self._topk(o, p, k, filtered, exclude, 1)
+
+    # ---- host side: ids, the exclusion lists ----
+
+    def _known_answers(self):
+        if self._answers is None:
+            tails, heads = defaultdict(set), defaultdict(set)
+            for s, o, p in self._known.tolist():
+                tails[(s, p)].add(o)
+                heads[(o, p)].add(s)
+            self._answers = (tails, heads)
+        return self._answers
+
+    def _exclusions(self, anchors, rels, direction, filtered, exclude, n_ent):
+        """Per query the sorted, de-duplicated union of its known answers
+        (filtered) and its ``exclude`` ids, as (offsets [n + 1], ids) int32;
+        None when every list is empty."""
+        n = len(anchors)
+        extra = [()] * n
+        if exclude is not None:
+            ex = list(exclude)
+            if n == 1 and (len(ex) != 1 or np.ndim(ex[0]) == 0):
+                ex = [ex]     # one query: a flat list of ids
+            if len(ex) != n:
+                raise ValueError("exclude: %d lists for %d queries" % (len(ex), n))
+            extra = [np.asarray(() if e is None else e, dtype=np.int64).reshape(-1) for e in ex]
+            for i, e in enumerate(extra):
+                bad = (e < 0) | (e >= n_ent)
+                if bad.any():
+                    raise ValueError("exclude: query %d has entity %d, out of range for %d"
+                                     % (i, int(e[np.argmax(bad)]), n_ent))
+        known = self._known_answers()[direction] if filtered else {}
+        off, ent = [0], []
+        for i, (a, p) in enumerate(zip(anchors.tolist(), rels.tolist())):
+            ids = set(known.get((a, p), ()))
+            ids.update(int(x) for x in extra[i])
+            ent.extend(sorted(ids))
+            off.append(len(ent))
+        if not ent:
+            return None
+        return np.asarray(off, dtype=np.int32), np.asarray(ent, dtype=np.int32)
+
+    def _device_csr(self, key, build, device):
+        if key not in self._csr:
+            if len(self._csr) >= _CACHE_ENTRIES:
+                self._csr.clear()
+            csr = build()
+            self._csr[key] = None if csr is None else tuple(
+                torch.as_tensor(x, device=device) for x in csr)
+        return self._csr[key]
+
+    # ---- the call ----
+
+    def _topk(self, anchor, p, k, filtered, exclude, direction):
+        model = self.model
+        code, rel = _model_code(model)
+        if self.scoring == "model":
+            code = model._kernel_model()
+        E = model.params["E"]
+        n_ent, n_rel = E.rows, rel.rows
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
+            raise ValueError("k must be an integer in 1 .. %d, not %r" % (K_MAX, k))
+        k = int(k)
+        if filtered and self._known is None:
+            raise ValueError("filtered=True needs known_triples (or pass filtered=False)")
+        what = "heads" if direction else "tails"
+        a = np.asarray(anchor, dtype=np.int64).reshape(-1)
+        r = np.asarray(p, dtype=np.int64).reshape(-1)
+        if len(r) == 1 and len(a) > 1:
+            r = np.repeat(r, len(a))
+        if len(a) != len(r):
+            raise ValueError("%s: %d entities for %d relations" % (what, len(a), len(r)))
+        _check_ids(a, n_ent, what, "object" if direction else "subject")
+        _check_ids(r, n_rel, what, "relation")
+        if filtered:
+            check_triple_ids(self._known, n_ent, n_rel, "known triples")
+        n = len(a)
+        if n == 0:
+            return np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
+        dev = model.device
+        q = np.stack([a, r], axis=1).astype(np.int32)
+        xkey = None if exclude is None else repr([None if e is None else np.asarray(e).tolist()
+                                                  for e in (exclude if n > 1 else [exclude])])
+        key = (str(torch.device(dev)), direction, bool(filtered), q.tobytes(), xkey)
+        csr = self._device_csr(
+            key, lambda: self._exclusions(a, r, direction, filtered, exclude, n_ent), dev)
+        queries = torch.as_tensor(q, device=dev)
+        lib = L.lib()
+        ents = torch.empty((n, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        nbytes = lib.skge_topk_workspace_bytes(n, model.d, k, n_ent)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(lib.skge_topk(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), n_ent, model.d,
+                              L.ptr(queries), n, direction, k,
+                              L.ptr(csr[0]) if csr else None, L.ptr(csr[1]) if csr else None,
+                              L.ptr(ws), nbytes, L.ptr(ents), L.ptr(scores)), "topk")
+        return ents.cpu().numpy().astype(np.int64), scores.cpu().numpy()
