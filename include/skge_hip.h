@@ -315,6 +315,9 @@ void skge_runner_destroy(skge_runner_t *r);
  * draws -> a skipped pair) and one skge_pair_step.  ent needs 8 * batch_size
  * touched slots, rel (if it records slots) 4 * batch_size.  *nviol_total
  * accumulates the violations.  nlaunches reports the graph's node count.
+ * skge_pair_runner_create_ex is the same loop with the negatives of another
+ * sampler (skge_sampler_t below: the typed or LCWA sampler); nothing after the
+ * draw differs.
  */
 typedef struct skge_pair_runner skge_pair_runner_t;
 /* The epoch's draws as the pair loop (and the pipelined TransE runner) make
@@ -329,6 +332,48 @@ skge_pair_runner_t *skge_pair_runner_create(void *stream, int model, int af,
                                             int64_t set_capacity, int nbatches, uint64_t seed,
                                             uint64_t *epoch_key, float margin, int ntries,
                                             int *nviol_total);
+/*
+ * The negative sampler of skge_epoch_sample_ex and of the pair / logistic
+ * loops' _ex constructors.  Every kind writes the same records, (s, o, p, s')
+ * and o' per positive, each negative the first of ntries keyed draws
+ * draw(key, j, mode, try, n) that passes the kind's test, else -1:
+ *   RANDOM  RandomModeSampler(1, [0, 1]) (skge/sample.py:28-46): an entity
+ *           id, accepted if the corrupted triple is not a training triple.
+ *   TYPED   CorruptedSampler(1, xs, type_index(xs)) over modes [0, 1]
+ *           (skge/sample.py:68-88): mode m draws an index into pool 2p + m
+ *           (n = the pool's length; an empty pool draws nothing), the
+ *           candidate is that pool entry, accepted as RANDOM's.
+ *   LCWA    LCWASampler(1, [0, 1], xs, sz) (skge/sample.py:91-110): mode 0
+ *           draws an entity id, accepted if it is in pool 2p (binary search:
+ *           the reference's counts[(s', p)] > 0) and the corrupted triple is
+ *           not a training triple; mode 1 keeps s, whose (s, p) the positive
+ *           itself counts, so it is RANDOM's mode-1 draw bit for bit.
+ * The pools are a CSR over 2 * n_rel lists: pool 2p + side holds the
+ * ascending unique entity ids seen as subject (side 0) or object (side 1) of
+ * relation p in the training triples; pool_off [2 * n_rel + 1] and pool_ent
+ * are device memory.  A positive whose relation is not below n_rel draws no
+ * pool negative.  The pools' CONTENTS are device data and are not checked:
+ * offsets must be non-decreasing within pool_ent and entries valid entity
+ * ids.  smp == NULL means RANDOM, as the entry points without _ex.
+ */
+#define SKGE_SAMPLER_RANDOM 0
+#define SKGE_SAMPLER_TYPED 1
+#define SKGE_SAMPLER_LCWA 2
+typedef struct {
+  int kind, n_rel;
+  const int64_t *pool_off; /* [2 * n_rel + 1]; unused for RANDOM */
+  const int *pool_ent;     /* ascending, unique within a pool */
+} skge_sampler_t;
+int skge_epoch_sample_ex(void *stream, const int *trip, int64_t T, const void *set,
+                         int64_t set_capacity, int n_ent, uint64_t seed,
+                         const uint64_t *epoch_key, int ntries, int *rec, int *rec_n1,
+                         const skge_sampler_t *smp);
+skge_pair_runner_t *skge_pair_runner_create_ex(void *stream, int model, int af,
+                                               const skge_table_t *ent, const skge_table_t *rel,
+                                               int d, const int *trip, int64_t T, const void *set,
+                                               int64_t set_capacity, int nbatches, uint64_t seed,
+                                               uint64_t *epoch_key, float margin, int ntries,
+                                               int *nviol_total, const skge_sampler_t *smp);
 int skge_pair_runner_run(skge_pair_runner_t *r, void *stream, int nepochs);
 int skge_pair_runner_nlaunches(const skge_pair_runner_t *r);
 void skge_pair_runner_destroy(skge_pair_runner_t *r);
@@ -359,6 +404,14 @@ skge_triple_runner_t *skge_triple_runner_create(void *stream, int model, const s
                                                 int64_t T, const void *set, int64_t set_capacity,
                                                 int nbatches, uint64_t seed, uint64_t *epoch_key,
                                                 int ntries, float *loss_total);
+/* the same loop drawing its negatives with smp (skge_sampler_t above) */
+skge_triple_runner_t *skge_triple_runner_create_ex(void *stream, int model,
+                                                   const skge_table_t *ent,
+                                                   const skge_table_t *rel, int d,
+                                                   const int *trip, int64_t T, const void *set,
+                                                   int64_t set_capacity, int nbatches,
+                                                   uint64_t seed, uint64_t *epoch_key, int ntries,
+                                                   float *loss_total, const skge_sampler_t *smp);
 int skge_triple_runner_run(skge_triple_runner_t *r, void *stream, int nepochs);
 int skge_triple_runner_nlaunches(const skge_triple_runner_t *r);
 void skge_triple_runner_destroy(skge_triple_runner_t *r);

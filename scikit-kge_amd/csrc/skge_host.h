@@ -128,10 +128,14 @@ inline TripleSet triple_set_view(const void* set, int64_t capacity) {
 
 // skge_pipeline.hip: draw every negative of the epoch whose key is *epoch_key
 // (rec[j] = (s, o, p, s' or -1), rec_n1[j] = o' or -1 for positive j of the
-// epoch's order)
+// epoch's order) with the sampler smp (nullptr: RANDOM, k_epoch_sample as the
+// pipelined runners launch it; check_sampler first)
 int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t seed,
                         const uint64_t* epoch_key, TripleSet set, int n_ent, int ntries,
-                        int4* rec, int* rec_n1);
+                        int4* rec, int* rec_n1, const skge_sampler_t* smp = nullptr);
+// SKGE_EINVAL (and the error text) for an unknown kind or, for a pool kind,
+// n_rel <= 0 or NULL pools; the pools' contents are not read
+int check_sampler(const skge_sampler_t* smp, const char* who);
 
 // skge_grad.hip: HolE pairwise, one positive (both of its pairs) per wave
 bool hole_pos_ok(int af, const skge_table_t* ent, const skge_table_t* rel, int d);

@@ -1,6 +1,7 @@
 // Device pair loop for every model: one epoch of PairwiseStochasticTrainer
 // with RandomModeSampler(1, [0, 1]) (skge/base.py:1242-1291, 1394-1427;
-// skge/sample.py:28-46), captured once into a hipGraph and replayed.
+// skge/sample.py:28-46) or, through skge_pair_runner_create_ex, the typed or
+// LCWA sampler (skge_sampler.h), captured once into a hipGraph and replayed.
 //
 //   k_epoch_sample (skge_pipeline.hip)  the epoch's permutation and every
 //       negative, one thread per positive: records (s, o, p, s'), o'
@@ -102,11 +103,13 @@ struct skge_pair_runner : GraphRunnerCore {
   size_t ws_bytes = 0;
 };
 
-extern "C" skge_pair_runner_t* skge_pair_runner_create(
+extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
     void* stream, int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
-    uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total) {
+    uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total,
+    const skge_sampler_t* smp) {
   if (!ent || !rel) return fail("pair runner: NULL table");
+  if (check_sampler(smp, "pair runner")) return nullptr;
   if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("pair runner: unknown model");
   if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity,
                          2 * T, ntries, stream))
@@ -150,7 +153,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create(
     return fail("pair runner: HolE FFT twiddle table allocation failed");
   if (!r->begin_capture(st)) return nullptr;
   int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
-                               r->rec, r->rec_n1);
+                               r->rec, r->rec_n1, smp);
   if (!rc) {
     const int64_t blocks = std::max((int64_t)1, std::min((T + 255) / 256, (int64_t)4096));
     hipLaunchKernelGGL(k_pairs_of_epoch, dim3((unsigned)blocks), dim3(256), 0, st, r->rec,
@@ -210,17 +213,35 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create(
   return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
-extern "C" int skge_epoch_sample(void* stream, const int* trip, int64_t T, const void* set,
-                                 int64_t set_capacity, int n_ent, uint64_t seed,
-                                 const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1) {
+extern "C" skge_pair_runner_t* skge_pair_runner_create(
+    void* stream, int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
+    uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total) {
+  return skge_pair_runner_create_ex(stream, model, af, ent, rel, d, trip, T, set, set_capacity,
+                                    nbatches, seed, epoch_key, margin, ntries, nviol_total,
+                                    nullptr);
+}
+
+extern "C" int skge_epoch_sample_ex(void* stream, const int* trip, int64_t T, const void* set,
+                                    int64_t set_capacity, int n_ent, uint64_t seed,
+                                    const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1,
+                                    const skge_sampler_t* smp) {
   SKGE_CHECK_ARG(trip && set && epoch_key && rec && rec_n1, "NULL argument");
   SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
   SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
                  "set capacity must be a power of 2 >= 2T");
   SKGE_CHECK_ARG(n_ent > 0 && ntries >= 1, "bad n_ent / ntries");
+  if (int rc = check_sampler(smp, "epoch sample")) return rc;
   return launch_epoch_sample(as_stream(stream), trip, (long long)T, seed, epoch_key,
                              triple_set_view(set, set_capacity), n_ent, ntries, (int4*)rec,
-                             rec_n1);
+                             rec_n1, smp);
+}
+
+extern "C" int skge_epoch_sample(void* stream, const int* trip, int64_t T, const void* set,
+                                 int64_t set_capacity, int n_ent, uint64_t seed,
+                                 const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1) {
+  return skge_epoch_sample_ex(stream, trip, T, set, set_capacity, n_ent, seed, epoch_key, ntries,
+                              rec, rec_n1, nullptr);
 }
 
 extern "C" int skge_pair_runner_run(skge_pair_runner_t* r, void* stream, int nepochs) {

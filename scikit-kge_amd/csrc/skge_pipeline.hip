@@ -785,14 +785,58 @@ __global__ void k_epoch_sample(const int* __restrict__ trip, long long T, int ha
     sample_record(trip, pm, skey, set, n_ent, ntries, j, rec, rec_n1);
 }
 
+// the typed / LCWA samplers' epoch (the pair and logistic loops): an instance
+// of its own per kind, so k_epoch_sample -- RANDOM, the only kind the
+// pipelined runners draw -- stays the kernel it was
+template <int KIND>
+__global__ void k_epoch_sample_pools(const int* __restrict__ trip, long long T, int half,
+                                     uint64_t seed, const uint64_t* ekp, TripleSet set, Pools pl,
+                                     int n_ent, int ntries, int4* rec, int* rec_n1) {
+  const uint64_t ek = *ekp;
+  const Perm pm = {(uint64_t)T, half, epoch_perm_key(seed, ek)};
+  const uint64_t skey = epoch_sample_key(seed, ek);
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
+       j += (long long)gridDim.x * blockDim.x)
+    sample_record_pools<KIND>(trip, pm, skey, set, pl, n_ent, ntries, j, rec, rec_n1);
+}
+
+static_assert(SAMPLER_RANDOM == SKGE_SAMPLER_RANDOM && SAMPLER_TYPED == SKGE_SAMPLER_TYPED &&
+                  SAMPLER_LCWA == SKGE_SAMPLER_LCWA,
+              "skge_sampler.h's kinds are the ABI's");
+
+int check_sampler(const skge_sampler_t* smp, const char* who) {
+  if (!smp) return SKGE_OK;
+  SKGE_CHECK_ARG(smp->kind == SKGE_SAMPLER_RANDOM || smp->kind == SKGE_SAMPLER_TYPED ||
+                     smp->kind == SKGE_SAMPLER_LCWA,
+                 "%s: unknown sampler kind %d", who, smp->kind);
+  if (smp->kind == SKGE_SAMPLER_RANDOM) return SKGE_OK;
+  SKGE_CHECK_ARG(smp->n_rel > 0 && smp->n_rel <= (INT32_MAX - 2) / 2,
+                 "%s: sampler n_rel %d must be in [1, 2^30)", who, smp->n_rel);
+  SKGE_CHECK_ARG(smp->pool_off && smp->pool_ent, "%s: sampler pools are NULL", who);
+  return SKGE_OK;
+}
+
 int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t seed,
                         const uint64_t* epoch_key, TripleSet set, int n_ent, int ntries,
-                        int4* rec, int* rec_n1) {
+                        int4* rec, int* rec_n1, const skge_sampler_t* smp) {
   long long blocks = (T + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, trip, T,
-                     perm_half(T), seed, epoch_key, set, n_ent, ntries, rec, rec_n1, nullptr,
-                     nullptr);
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
+  if (kind == SKGE_SAMPLER_RANDOM) {
+    hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, trip, T,
+                       perm_half(T), seed, epoch_key, set, n_ent, ntries, rec, rec_n1, nullptr,
+                       nullptr);
+  } else {
+    const Pools pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
+    if (kind == SKGE_SAMPLER_TYPED)
+      hipLaunchKernelGGL(k_epoch_sample_pools<SAMPLER_TYPED>, dim3((unsigned)blocks), dim3(256),
+                         0, st, trip, T, perm_half(T), seed, epoch_key, set, pl, n_ent, ntries,
+                         rec, rec_n1);
+    else
+      hipLaunchKernelGGL(k_epoch_sample_pools<SAMPLER_LCWA>, dim3((unsigned)blocks), dim3(256), 0,
+                         st, trip, T, perm_half(T), seed, epoch_key, set, pl, n_ent, ntries, rec,
+                         rec_n1);
+  }
   SKGE_CHECK_LAUNCH("epoch sample");
   return SKGE_OK;
 }

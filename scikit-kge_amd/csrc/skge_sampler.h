@@ -1,6 +1,7 @@
 // Counter-based randomness of the device batch loop: the keyed epoch
-// permutation (the stand-in for numpy's shuffle, skge/base.py:1257) and the
-// RandomModeSampler draws (skge/sample.py:41-46).
+// permutation (the stand-in for numpy's shuffle, skge/base.py:1257), the
+// RandomModeSampler draws (skge/sample.py:41-46) and, over the type index'
+// pools, the CorruptedSampler and LCWASampler draws (skge/sample.py:68-120).
 #pragma once
 #include "skge_device.h"
 
@@ -82,6 +83,104 @@ __device__ __forceinline__ void sample_record(const int* __restrict__ trip, cons
     if (!set_contains(set, s, c, p)) {
       neg1 = c;
       break;
+    }
+  }
+  rec[j] = make_int4(s, o, p, neg0);
+  rec_n1[j] = neg1;
+}
+
+// ---- the typed and local-closed-world samplers (skge/sample.py:68-120) ----
+//
+// The type index as a CSR over 2 * n_rel pools: pool 2p + side holds the
+// ascending unique entities seen as subject (side 0) or object (side 1) of
+// relation p (include/skge_hip.h, skge_sampler_t).
+struct Pools {
+  const long long* off;   // [2 * n_rel + 1]
+  const int* ent;
+  int n_rel;
+};
+
+enum { SAMPLER_RANDOM = 0, SAMPLER_TYPED = 1, SAMPLER_LCWA = 2 };
+
+// `c in pool [lo, end)` (ascending, unique): for pool 2p the reference's
+// counts[(c, p)] > 0 (skge/sample.py:107).  Every load is inside the pool.
+__device__ __forceinline__ bool pool_contains(const int* __restrict__ ent, long long lo,
+                                              long long end, int c) {
+  long long hi = end;
+  while (lo < hi) {
+    const long long mid = lo + ((hi - lo) >> 1);
+    if (ent[mid] < c) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && ent[lo] == c;
+}
+
+// sample_record for the typed (KIND == SAMPLER_TYPED) and LCWA samplers: the
+// same record, counter use and first-accepted-try rule; only what a try draws
+// and what accepts it differ.
+//   TYPED, mode m: c = pool[2p + m][draw(skey, j, m, tr, L)], L the pool's
+//     length (L == 0 draws nothing), accepted if the corrupted triple is not
+//     a training triple (skge/sample.py:82-85).
+//   LCWA, mode 0: c = draw(skey, j, 0, tr, n_ent), accepted if c is in pool 2p
+//     and (c, o, p) is not a training triple; mode 1 leaves (s, p), which the
+//     positive itself counts, so it is sample_record's mode-1 loop.
+// One lane per positive, as sample_record: an LCWA try is accepted with
+// probability ~|subj(p)| / n_ent, so lanes of a wave leave the loop at
+// different tries and the wave runs its slowest lane's count.  The
+// wave-cooperative form (lanes test 64 consecutive tries of one positive, a
+// ballot picks the lowest) has NOT been built or measured; the choice rests
+// on a count of dependent searches only, and the LCWA launch is
+// the slow one of the three kinds.
+// A relation id outside [0, n_rel) has no pools: no pool negative is drawn.
+template <int KIND>
+__device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip, const Perm& pm,
+                                                    uint64_t skey, const TripleSet& set,
+                                                    const Pools& pl, int n_ent, int ntries,
+                                                    long long j, int4* rec, int* rec_n1) {
+  const long long t = (long long)perm_index((uint64_t)j, pm);
+  const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
+  const bool has = p >= 0 && p < pl.n_rel;
+  long long b0 = 0, e0 = 0, b1 = 0, e1 = 0;
+  if (has) {
+    b0 = pl.off[2 * p];
+    e0 = b1 = pl.off[2 * p + 1];
+    if (KIND == SAMPLER_TYPED) e1 = pl.off[2 * p + 2];
+  }
+  int neg0 = -1, neg1 = -1;
+  if (e0 > b0) {
+    const int L = (int)(e0 - b0);
+    for (int tr = 0; tr < ntries; ++tr) {
+      int c;
+      if (KIND == SAMPLER_TYPED) {
+        c = pl.ent[b0 + draw(skey, j, 0, tr, L)];
+      } else {
+        c = draw(skey, j, 0, tr, n_ent);
+        if (!pool_contains(pl.ent, b0, e0, c)) continue;
+      }
+      if (!set_contains(set, c, o, p)) {
+        neg0 = c;
+        break;
+      }
+    }
+  }
+  if (KIND == SAMPLER_TYPED) {
+    if (e1 > b1) {
+      const int L = (int)(e1 - b1);
+      for (int tr = 0; tr < ntries; ++tr) {
+        const int c = pl.ent[b1 + draw(skey, j, 1, tr, L)];
+        if (!set_contains(set, s, c, p)) {
+          neg1 = c;
+          break;
+        }
+      }
+    }
+  } else {
+    for (int tr = 0; tr < ntries; ++tr) {
+      const int c = draw(skey, j, 1, tr, n_ent);
+      if (!set_contains(set, s, c, p)) {
+        neg1 = c;
+        break;
+      }
     }
   }
   rec[j] = make_int4(s, o, p, neg0);

@@ -194,11 +194,12 @@ struct skge_triple_runner : GraphRunnerCore {
   size_t ws_bytes = 0;
 };
 
-extern "C" skge_triple_runner_t* skge_triple_runner_create(
+extern "C" skge_triple_runner_t* skge_triple_runner_create_ex(
     void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
-    uint64_t* epoch_key, int ntries, float* loss_total) {
+    uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp) {
   if (!ent || !rel) return fail("triple runner: NULL table");
+  if (check_sampler(smp, "triple runner")) return nullptr;
   if (model != SKGE_HOLE && model != SKGE_RESCAL)
     return fail("triple runner: logistic loss is defined for HolE and RESCAL only");
   if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / 3, nbatches,
@@ -242,7 +243,7 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create(
     return fail("triple runner: HolE FFT twiddle table allocation failed");
   if (!r->begin_capture(st)) return nullptr;
   int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
-                               r->rec, r->rec_n1);
+                               r->rec, r->rec_n1, smp);
   if (!rc && !hpos) {
     const int64_t blocks = std::max((int64_t)1, std::min((T + 255) / 256, (int64_t)4096));
     hipLaunchKernelGGL(k_triples_of_epoch, dim3((unsigned)blocks), dim3(256), 0, st, r->rec,
@@ -269,6 +270,14 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create(
   }
   if (!rc) rc = skge_epoch_advance(stream, epoch_key);
   return r->end_capture(st, rc) ? r.release() : nullptr;
+}
+
+extern "C" skge_triple_runner_t* skge_triple_runner_create(
+    void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
+    uint64_t* epoch_key, int ntries, float* loss_total) {
+  return skge_triple_runner_create_ex(stream, model, ent, rel, d, trip, T, set, set_capacity,
+                                      nbatches, seed, epoch_key, ntries, loss_total, nullptr);
 }
 
 extern "C" int skge_triple_runner_run(skge_triple_runner_t* r, void* stream, int nepochs) {

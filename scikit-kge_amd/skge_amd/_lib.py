@@ -19,6 +19,7 @@ SKGE_AF_LINEAR, SKGE_AF_SIGMOID, SKGE_AF_TANH, SKGE_AF_RELU = 0, 1, 2, 3
 SKGE_SGD, SKGE_ADAGRAD = 0, 1
 SKGE_POST_NONE, SKGE_POST_NORMALIZE, SKGE_POST_NORMLESS1 = 0, 1, 2
 SKGE_ACC_F32, SKGE_ACC_I16X4, SKGE_ACC_I32X2, SKGE_ACC_FX64, SKGE_ACC_I8X4 = 0, 1, 2, 3, 4
+SKGE_SAMPLER_RANDOM, SKGE_SAMPLER_TYPED, SKGE_SAMPLER_LCWA = 0, 1, 2
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -38,6 +39,14 @@ class SkgeTable(ctypes.Structure):
 
 
 T_P = ctypes.POINTER(SkgeTable)
+
+
+class SkgeSampler(ctypes.Structure):
+    """Mirror of skge_sampler_t."""
+    _fields_ = [("kind", c_i), ("n_rel", c_i), ("pool_off", c_p), ("pool_ent", c_p)]
+
+
+S_P = ctypes.POINTER(SkgeSampler)
 
 # name -> (restype, argtypes); the exact set declared in include/skge_hip.h
 SIGNATURES = {
@@ -77,12 +86,18 @@ SIGNATURES = {
     "skge_runner_destroy": (None, [c_p]),
     "skge_pair_runner_create": (c_p, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i,
                                       c_u64, c_p, c_f, c_i, c_p]),
+    "skge_pair_runner_create_ex": (c_p, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,
+                                         c_i, c_u64, c_p, c_f, c_i, c_p, S_P]),
     "skge_pair_runner_run": (c_i, [c_p, c_p, c_i]),
     "skge_epoch_sample": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p]),
+    "skge_epoch_sample_ex": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p,
+                                   S_P]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
                                         c_p, c_i, c_p]),
+    "skge_triple_runner_create_ex": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i,
+                                           c_u64, c_p, c_i, c_p, S_P]),
     "skge_triple_runner_run": (c_i, [c_p, c_p, c_i]),
     "skge_triple_runner_nlaunches": (c_i, [c_p]),
     "skge_triple_runner_destroy": (None, [c_p]),

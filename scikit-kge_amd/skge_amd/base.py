@@ -345,12 +345,14 @@ class StochasticTrainer(object):
             if self.samplef is None:
                 use_device, ntries, why = False, self.ntries, "samplef is None (no negatives)"
             else:
-                use_device, ntries, why = device_sampler_args(self, xs, ys)
+                args = device_sampler_args(self, xs, ys)
+                use_device, ntries, why = args
             if use_device:
-                logistic_device_optim(self, xs, ntries=ntries)
+                logistic_device_optim(self, xs, ntries=ntries, sampler=args.kind)
                 return
-            # the device loop draws RandomModeSampler(1, [0, 1]) negatives
-            # itself; anything else trains on the per-batch path instead
+            # the device loop draws the negatives of RandomModeSampler,
+            # CorruptedSampler or LCWASampler over (1, [0, 1]) itself;
+            # anything else trains on the per-batch path instead
             warnings.warn("device_loop: %s; training on the per-batch path" % why)
         self._optim(list(zip(xs, ys)))
 
@@ -453,15 +455,17 @@ class PairwiseStochasticTrainer(StochasticTrainer):
         use_device = False
         if self.device_loop:
             from .device import device_sampler_args
-            use_device, ntries, why = device_sampler_args(self, xs, ys)
+            args = device_sampler_args(self, xs, ys)
+            use_device, ntries, why = args
             if not use_device:
-                # the device loop draws RandomModeSampler(1, [0, 1]) negatives
-                # itself; anything else trains on the per-batch path instead
+                # the device loop draws the negatives of RandomModeSampler,
+                # CorruptedSampler or LCWASampler over (1, [0, 1]) itself;
+                # anything else trains on the per-batch path instead
                 warnings.warn("device_loop: %s; training on the per-batch path" % why)
         self._on_device = use_device
         if use_device:
             from .device import device_optim
-            device_optim(self, xs, ntries=ntries)
+            device_optim(self, xs, ntries=ntries, sampler=args.kind)
         elif self.samplef is None:
             pidx = np.where(np.array(ys) == 1)[0]
             nidx = np.where(np.array(ys) != 1)[0]

@@ -37,6 +37,42 @@ class DeviceKG(object):
         self.slots = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         L.check(L.lib().skge_triple_set_build(L.stream_ptr(stream), L.ptr(self.trip), self.T,
                                               L.ptr(self.slots), self.capacity), "triple set build")
+        self._pools = {}
+
+    def pools(self, n_rel):
+        """The type index of the triples as a CSR of 2 * n_rel pools
+        (include/skge_hip.h, skge_sampler_t), built on first use: pool
+        2p + side holds the ascending unique entity ids seen as subject
+        (side 0) or object (side 1) of relation p.  Returns (pool_off int64
+        [2 * n_rel + 1], pool_ent int32); a relation that never occurs has two
+        empty pools.  The typed and LCWA device samplers draw from it."""
+        n_rel = int(n_rel)
+        if n_rel not in self._pools:
+            t = self.trip.long()
+            p = t[:, 2]
+            if n_rel < 1 or int(p.min().item()) < 0 or int(p.max().item()) >= n_rel:
+                raise ValueError("type index: relation ids must be in [0, %d)" % n_rel)
+            if int(t[:, :2].min().item()) < 0:
+                raise ValueError("type index: negative entity id")
+            n = int(t[:, :2].max().item()) + 1
+            keys = torch.unique(torch.cat([(2 * p) * n + t[:, 0], (2 * p + 1) * n + t[:, 1]]))
+            bounds = torch.arange(2 * n_rel + 1, dtype=torch.int64, device=t.device) * n
+            off = torch.searchsorted(keys, bounds).to(torch.int64).contiguous()
+            ent = (keys % n).to(torch.int32).contiguous()
+            self._pools[n_rel] = (off, ent)
+        return self._pools[n_rel]
+
+    def sampler(self, kind, n_rel=None):
+        """skge_sampler_t for `kind` (None: RANDOM, the entry points' NULL);
+        the struct holds pointers into pools(n_rel), which this object keeps."""
+        if kind == L.SKGE_SAMPLER_RANDOM:
+            return None
+        if kind not in (L.SKGE_SAMPLER_TYPED, L.SKGE_SAMPLER_LCWA):
+            raise ValueError("unknown sampler kind %r" % (kind,))
+        if n_rel is None:
+            raise ValueError("the typed and LCWA samplers need the model's relation count")
+        off, ent = self.pools(n_rel)
+        return L.SkgeSampler(int(kind), int(n_rel), off.data_ptr(), ent.data_ptr())
 
 
 PACKED_MAX = 32767   # a 16-bit packed field's bound (csrc/skge_pipeline.hip PACKED_MAX)
@@ -140,8 +176,12 @@ class _Runner(object):
     _pad = False
     graph = None       # dp.DataParallelRunner: the torch graph of its captured epoch
 
-    def _setup(self, model, kg, nbatches, seed, ntries, stream):
+    def _setup(self, model, kg, nbatches, seed, ntries, stream, sampler=L.SKGE_SAMPLER_RANDOM):
         dev = model.device
+        # the negative sampler's kind (include/skge_hip.h SKGE_SAMPLER_*) and,
+        # for the pool kinds, its view of the kg's type index
+        self.sampler = int(sampler)
+        self._smp = kg.sampler(self.sampler, model.sz[2]) if self.sampler else None
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
         self.kg, self.model, self.nbatches = kg, model, nbatches
         self.seed, self.ntries = int(seed) & (2 ** 64 - 1), int(ntries)
@@ -152,13 +192,22 @@ class _Runner(object):
         return given if given is not None else torch.zeros(1, dtype=dtype,
                                                            device=self.model.device)
 
-    def _hold_captured(self):
+    def _hold_state(self, updaters):
+        """The graph captures raw pointers to the parameters and to the
+        updaters' state (AdaGrad's p2): hold the tensors, so a caller that
+        drops its updaters while the runner lives cannot free what the graph
+        still reads and writes."""
+        self._state_held = [(u.param.data, u.state()) for u in updaters.values()]
+
+    def _hold_captured(self, updaters):
         """The graph captures raw pointers to the model's accumulators and
         counters: hold the tensors, so a later per-batch call that grows the
-        model's slot arrays cannot free what this runner still writes."""
+        model's slot arrays cannot free what this runner still writes; and
+        the updaters' state (_hold_state)."""
         m = self.model
         self._captured = [(a.sum, a.cnt, a.touched) for a in m._acc.values()] + \
             [p._counters.copy() for p in m.params.values()]
+        self._hold_state(updaters)
 
     def _epoch_args(self):
         kg = self.kg
@@ -364,6 +413,7 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         dev = model.device
         self._setup(model, kg, nbatches, seed, ntries, stream)
         self.nviol_total = self._total(nviol_total, torch.int32)
+        self._hold_state(updaters)
         bs = kg.T // nbatches
         self.hot_rows = 0   # pipelined TransE: entity rows with replicated sums (skewed KGs)
         # d % 4 != 0 (e.g. the reference's d = 50): the packed / pipelined
@@ -484,6 +534,7 @@ class HolePipeRunner(_PipeRunner):
         dev = model.device
         self._setup(model, kg, nbatches, seed, ntries, stream)
         self.nviol_total = self._total(nviol_total, torch.int32)
+        self._hold_state(updaters)
         E, R = model.params["E"], model.params["R"]
         bs = kg.T // nbatches
         self.accE = Accumulator(E.rows, E.width, dev, slots=4 * bs)
@@ -529,15 +580,15 @@ class PairLoopRunner(_Runner):
     _who = "pair-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 nviol_total=None):
-        self._setup(model, kg, nbatches, seed, ntries, stream)
+                 nviol_total=None, sampler=L.SKGE_SAMPLER_RANDOM):
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
         self.nviol_total = self._total(nviol_total, torch.int32)
         P = 2 * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("pairwise", updaters, slots=model._pair_slots(P))
-        self._hold_captured()
+        self._hold_captured(updaters)
         self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te, self.tr,
                      model.d, *self._epoch_args(), float(model.margin), self.ntries,
-                     L.ptr(self.nviol_total))
+                     L.ptr(self.nviol_total), self._smp, create="skge_pair_runner_create_ex")
 
 
 def _require_logistic_model(model):
@@ -567,15 +618,16 @@ class LogisticLoopRunner(_Runner):
     _who = "logistic-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 loss_total=None):
+                 loss_total=None, sampler=L.SKGE_SAMPLER_RANDOM):
         _require_logistic_model(model)
-        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
         self.loss_total = self._total(loss_total, torch.float32)
         T3 = 3 * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("logistic", updaters, slots=model._triple_slots(T3))
-        self._hold_captured()
+        self._hold_captured(updaters)
         self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
-                     *self._epoch_args(), self.ntries, L.ptr(self.loss_total))
+                     *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp,
+                     create="skge_triple_runner_create_ex")
 
 
 def _fit_epochs(trainer, runner):
@@ -594,10 +646,11 @@ def _fit_epochs(trainer, runner):
                     break
 
 
-def logistic_device_optim(trainer, xs, ntries=None):
+def logistic_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM):
     """StochasticTrainer.fit with device_loop=True: per epoch _pre_epoch, one
     graph replay, the runner's error word, then the post_epoch callbacks (which
-    read the epoch's loss through trainer.loss as on the per-batch path)."""
+    read the epoch's loss through trainer.loss as on the per-batch path).
+    sampler: the kind device_sampler_args reported."""
     model = trainer.model
     dev = model.device
     if trainer._loss_dev is None:
@@ -605,32 +658,43 @@ def logistic_device_optim(trainer, xs, ntries=None):
     kg = DeviceKG(xs, dev)
     runner = LogisticLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                                 ntries=trainer.ntries if ntries is None else ntries,
-                                loss_total=trainer._loss_dev)
+                                loss_total=trainer._loss_dev, sampler=sampler)
     trainer.batch_size = kg.T // trainer.nbatches
     _fit_epochs(trainer, runner)
 
 
-def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None):
+def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None,
+                  sampler=L.SKGE_SAMPLER_RANDOM, n_rel=None):
     """The epoch's positives and draws as the device loops make them:
-    (rec [T, 4] = (s, o, p, s' or -1), rec_n1 [T] = o' or -1) on the device."""
+    (rec [T, 4] = (s, o, p, s' or -1), rec_n1 [T] = o' or -1) on the device.
+    sampler: the kind (the typed and LCWA kinds need n_rel, the model's
+    relation count)."""
     dev = kg.trip.device
     rec = torch.empty((kg.T, 4), dtype=torch.int32, device=dev)
     rec_n1 = torch.empty(kg.T, dtype=torch.int32, device=dev)
     ek = torch.tensor([int(epoch_key)], dtype=torch.int64, device=dev)
-    L.check(L.lib().skge_epoch_sample(L.stream_ptr(stream), L.ptr(kg.trip), kg.T, L.ptr(kg.slots),
-                                      kg.capacity, int(n_ent), int(seed) & (2 ** 64 - 1),
-                                      L.ptr(ek), int(ntries), L.ptr(rec), L.ptr(rec_n1)),
+    L.check(L.lib().skge_epoch_sample_ex(L.stream_ptr(stream), L.ptr(kg.trip), kg.T,
+                                         L.ptr(kg.slots), kg.capacity, int(n_ent),
+                                         int(seed) & (2 ** 64 - 1), L.ptr(ek), int(ntries),
+                                         L.ptr(rec), L.ptr(rec_n1), kg.sampler(sampler, n_rel)),
             "epoch sample")
     return rec, rec_n1
 
 
 def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=None,
-                runner="auto"):
+                runner="auto", sampler=L.SKGE_SAMPLER_RANDOM):
     """runner: 'auto' (TransE -> EpochRunner, the fused sampler/score runners;
     HolE -> HolePipeRunner where it applies, RESCAL -> PairLoopRunner),
-    'epoch', 'hole_pipe' or 'pairs'."""
+    'epoch', 'hole_pipe' or 'pairs'.  sampler: the kind of negatives
+    (SKGE_SAMPLER_*); the fused and pipelined runners draw RANDOM only, so the
+    typed and LCWA kinds run the pair loop for every model."""
     from .transe import TransE
     from .base import deterministic
+    if sampler != L.SKGE_SAMPLER_RANDOM:
+        if runner not in ("auto", "pairs"):
+            raise ValueError("device runner %r draws RandomModeSampler negatives only; the typed "
+                             "and LCWA samplers need 'pairs' (or 'auto')" % (runner,))
+        runner = "pairs"
     if runner == "auto":
         runner = "epoch" if isinstance(model, TransE) else \
             ("hole_pipe" if HolePipeRunner.eligible(model) and not deterministic() else "pairs")
@@ -642,48 +706,102 @@ def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=N
                            nviol_total=nviol_total)
     if runner == "pairs":
         return PairLoopRunner(model, updaters, kg, nbatches, seed=seed, ntries=ntries,
-                              nviol_total=nviol_total)
+                              nviol_total=nviol_total, sampler=sampler)
     raise ValueError("unknown device runner %r" % (runner,))
 
 
+class SamplerArgs(tuple):
+    """device_sampler_args' result: unpacks as (eligible, ntries, reason), as
+    it always has; ``kind`` is the device sampler's kind (SKGE_SAMPLER_*)."""
+
+    def __new__(cls, eligible, ntries, reason, kind=L.SKGE_SAMPLER_RANDOM):
+        self = super(SamplerArgs, cls).__new__(cls, (eligible, ntries, reason))
+        self.kind = kind
+        return self
+
+
+def _pools_match(index, xs3):
+    """Whether a CorruptedSampler's type_index lists, per relation and side,
+    exactly the entities type_index(xs) does, each once (a repeated entry
+    would be drawn more often than the device's unique pools draw it)."""
+    from .sample import type_index
+    want = type_index(xs3)
+    try:
+        if set(index.keys()) != set(want.keys()):
+            return False
+        for k, sides in want.items():
+            for side in (0, 1):
+                got = [int(v) for v in index[k][side]]
+                if len(got) != len(sides[side]) or set(got) != set(sides[side]):
+                    return False
+    except (AttributeError, KeyError, TypeError, ValueError):
+        return False
+    return True
+
+
 def device_sampler_args(trainer, xs, ys):
-    """(eligible, ntries, reason): whether PairwiseStochasticTrainer.fit with
-    device_loop=True may run the device loop, whose sampler draws what
-    RandomModeSampler(1, [0, 1], xs, sz).sample would (skge/sample.py:28-46,
-    skge/base.py:426).  Needed: every y is +1, samplef is such a sampler's
-    sample, and the sampler rejects against the same training triples the
-    device loop does (its xs == the fit's xs).  samplef None is the
-    reference's labelled-negatives branch (skge/base.py:1350-1357: positives
-    paired with the given y != 1 rows; with none it builds no pairs), which
-    the device loop does not mirror."""
+    """(eligible, ntries, reason), with the device sampler's kind as the
+    result's ``kind``: whether a trainer's fit with device_loop=True may run
+    the device loop, whose samplers draw what
+      RandomModeSampler(1, [0, 1], xs, sz)               (kind RANDOM),
+      CorruptedSampler(1, xs, type_index(xs), modes=[0, 1])  (kind TYPED) or
+      LCWASampler(1, [0, 1], xs, sz)                     (kind LCWA)
+    would (skge/sample.py:28-120, skge/base.py:422-428).  Needed: every y is
+    +1, samplef is such a sampler's own sample method, n == 1 and modes ==
+    [0, 1], sizes equal to the model's, and a sampler that rejects against the
+    same training triples the device loop does (its xs == the fit's xs); the
+    typed sampler's type_index must be the one of xs and the LCWA sampler's
+    counts those of xs.  samplef None is the reference's labelled-negatives
+    branch (skge/base.py:1350-1357: positives paired with the given y != 1
+    rows; with none it builds no pairs), which the device loop does not
+    mirror."""
     if ys is not None and not np.all(np.asarray(ys) == 1):
-        return False, trainer.ntries, "labelled negatives (y != 1)"
+        return SamplerArgs(False, trainer.ntries, "labelled negatives (y != 1)")
     f = trainer.samplef
     if f is None:
-        return False, trainer.ntries, ("samplef is None (the labelled-negatives branch, "
-                                       "skge/base.py:1350-1357); pass samplef="
-                                       "RandomModeSampler(1, [0, 1], xs, sz).sample")
-    from .sample import RandomModeSampler
+        return SamplerArgs(False, trainer.ntries,
+                           "samplef is None (the labelled-negatives branch, "
+                           "skge/base.py:1350-1357); pass samplef="
+                           "RandomModeSampler(1, [0, 1], xs, sz).sample")
+    from .sample import CorruptedSampler, LCWASampler, RandomModeSampler, Sampler
     smp = getattr(f, "__self__", None)
-    if not isinstance(smp, RandomModeSampler) or getattr(f, "__func__", None) is not \
-            RandomModeSampler.sample:
-        return False, trainer.ntries, "samplef is not RandomModeSampler.sample"
+    cls = next((c for c in (LCWASampler, CorruptedSampler, RandomModeSampler)
+                if isinstance(smp, c)), None)   # LCWASampler is a RandomModeSampler: first
+    if cls is None or getattr(f, "__func__", None) is not Sampler.sample:
+        return SamplerArgs(False, trainer.ntries, "samplef is not RandomModeSampler.sample (nor "
+                           "CorruptedSampler's or LCWASampler's)")
+    name = cls.__name__
+    kind = {RandomModeSampler: L.SKGE_SAMPLER_RANDOM, CorruptedSampler: L.SKGE_SAMPLER_TYPED,
+            LCWASampler: L.SKGE_SAMPLER_LCWA}[cls]
+    if type(smp)._sample is not cls._sample:
+        return SamplerArgs(False, trainer.ntries, "%s._sample is overridden" % name)
     if smp.n != 1 or list(smp.modes) != [0, 1]:
-        return False, trainer.ntries, "RandomModeSampler(n=%r, modes=%r) is not (1, [0, 1])" % (
-            smp.n, smp.modes)
+        return SamplerArgs(False, trainer.ntries, "%s(n=%r, modes=%r) is not (1, [0, 1])" % (
+            name, smp.n, smp.modes))
     n_ent = trainer.model.E.rows
-    if tuple(smp.sz[:2]) != (n_ent, n_ent):
-        return False, trainer.ntries, "sampler sizes %r differ from the model's" % (smp.sz,)
-    fit_set = set(tuple(int(v) for v in x) for x in
-                  np.asarray(xs, dtype=np.int64).reshape(-1, 3).tolist())
+    if cls is not CorruptedSampler and tuple(smp.sz[:2]) != (n_ent, n_ent):
+        return SamplerArgs(False, trainer.ntries,
+                           "sampler sizes %r differ from the model's" % (smp.sz,))
+    xs3 = np.asarray(xs, dtype=np.int64).reshape(-1, 3).tolist()
+    fit_set = set(tuple(int(v) for v in x) for x in xs3)
     if fit_set != smp.xs:
-        return False, trainer.ntries, ("the sampler's rejection set differs from the fit's "
-                                       "triples (the device sampler rejects against xs)")
-    return True, smp.ntries, ""
+        return SamplerArgs(False, trainer.ntries,
+                           "the sampler's rejection set differs from the fit's "
+                           "triples (the device sampler rejects against xs)")
+    if cls is CorruptedSampler and not _pools_match(smp.type_index, xs3):
+        return SamplerArgs(False, trainer.ntries,
+                           "CorruptedSampler.type_index differs from type_index(xs) (the device "
+                           "sampler draws from the fit's triples' type index)")
+    if cls is LCWASampler and set(k for k, c in smp.counts.items() if c > 0) != \
+            set((s, p) for s, _, p in fit_set):
+        return SamplerArgs(False, trainer.ntries,
+                           "LCWASampler.counts differ from the fit's triples' (s, p) counts")
+    return SamplerArgs(True, smp.ntries, "", kind)
 
 
-def device_optim(trainer, xs, ntries=None):
-    """PairwiseStochasticTrainer.fit with device_loop=True.  The runner's
+def device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM):
+    """PairwiseStochasticTrainer.fit with device_loop=True (sampler: the kind
+    device_sampler_args reported).  The runner's
     error word (packed-sum overflow, cross-workgroup wait timeout) is read
     after every epoch, before the post_epoch callbacks, so no callback ever
     sees parameters from a failed epoch."""
@@ -700,5 +818,5 @@ def device_optim(trainer, xs, ntries=None):
         which = "pairs"
     runner = make_runner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                          ntries=trainer.ntries if ntries is None else ntries,
-                         nviol_total=trainer._nviol_dev, runner=which)
+                         nviol_total=trainer._nviol_dev, runner=which, sampler=sampler)
     _fit_epochs(trainer, runner)
