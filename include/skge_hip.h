@@ -678,6 +678,50 @@ int skge_topk(void *stream, int model, const float *E, const float *R, int N, in
               const int *excl_ent, void *workspace, size_t ws_bytes, int *ent_out,
               float *score_out);
 
+/* ---------------- subgraph embeddings and ranking ---------------- */
+
+/*
+ * Subgraph embeddings: Experiment.make_subgraphs (skge/base.py:122-202), the
+ * sub_algo == "transe" branch.  Subgraph i has the members
+ * mem_ent[mem_off[i] .. mem_off[i+1]) (entity ids, int32; mem_off int64
+ * [S + 1]).  SA[i] = the mean of E[m] over its members; when SV is given,
+ * SV[i] = sum (E[m] - SA[i])^2 / (count - 1) for count > 2 and SA[i]
+ * otherwise (the reference's quirk, base.py:154-157), by two passes (the
+ * mean, then the squared differences).  A group with more members than the
+ * split threshold (256) is summed in pieces that are added in
+ * piece order: no float atomics, the same bits on every run.
+ * E [N][d], SA / SV [S][d], d <= 1024, S > 0; member ids are not
+ * range-checked here.  The workspace function takes the CSR's member total,
+ * mem_off[S]; a smaller workspace (at least that of 0 members) is legal and
+ * leaves the groups whose pieces do not fit unsplit.
+ */
+size_t skge_subgraph_embed_workspace_bytes(int S, int d, int64_t n_members);
+int skge_subgraph_embed(void *stream, const float *E, int N, int d, const int64_t *mem_off,
+                        const int *mem_ent, int S, float *SA, float *SV, void *workspace,
+                        size_t ws_bytes);
+
+/*
+ * Subgraph ranks: FilteredRankingEval.subgraph_positions (skge/base.py:
+ * 828-911) with the model's own score in both directions.  For test triple
+ * i = (s, o, p) of queries[nq][3] every row x of X [S][d] (SA or SV) scores
+ * as the object of (s, p, x) (tail) and as the subject of (x, p, o) (head),
+ * with the query vectors and the sequential fp32 chain of the ranking entry
+ * points above.  skip_tail[i] / skip_head[i]: a subgraph id that is not
+ * ranked, or -1.  ans_off int64 [N + 1] / ans_sub int32: per entity the
+ * ascending ids of the subgraphs whose members contain it.
+ * ranks_out[2i], [2i+1] = 1 + #{eligible subgraphs scoring strictly above the
+ * best-scoring eligible subgraph that contains o (tail) or s (head)}, ties in
+ * the answer's favour; when no eligible subgraph contains the answer, the
+ * number of eligible subgraphs + 1 and found_out = 0 (else 1).
+ * d <= 1024, S > 0; ids are not range-checked here.  Workspace:
+ * skge_subgraph_rank_workspace_bytes(nq, d).
+ */
+size_t skge_subgraph_rank_workspace_bytes(int nq, int d);
+int skge_subgraph_rank(void *stream, int model, const float *E, const float *R, int N, int d,
+                       const float *X, int S, const int *queries, int nq, const int *skip_tail,
+                       const int *skip_head, const int64_t *ans_off, const int *ans_sub,
+                       void *workspace, size_t ws_bytes, int *ranks_out, int *found_out);
+
 #ifdef __cplusplus
 }
 #endif

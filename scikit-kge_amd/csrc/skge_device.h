@@ -455,4 +455,17 @@ __device__ __forceinline__ bool set_contains(const TripleSet& ts, int s, int o, 
   return false;
 }
 
+// One row's score under a query vector, as the ranking kernels' counting
+// passes compute it (skge_eval.hip k_rank_count2): a sequential-k fp32 chain,
+// the L1 distance (negated) or the dot product.  A score that is compared
+// with the counting pass's scores comes from here, so that a row never
+// outranks itself.
+template <bool L1>
+__device__ __forceinline__ float rank_score(const float* __restrict__ q,
+                                            const float* __restrict__ e, int d) {
+  float acc = 0.0f;
+  for (int k = 0; k < d; ++k) acc = L1 ? acc - fabsf(q[k] - e[k]) : fmaf(e[k], q[k], acc);
+  return acc;
+}
+
 }  // namespace skge

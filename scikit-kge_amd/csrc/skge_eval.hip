@@ -377,13 +377,54 @@ __global__ __launch_bounds__(256) void k_rank_known(const float* __restrict__ E,
   const float t = tgt[v];
   int dec = 0;
   for (int i = off[qi]; i < off[qi + 1]; ++i) {
-    const float* e = E + (size_t)ent[i] * d;
-    float acc = 0.0f;
-    for (int k = 0; k < d; ++k) acc = L1 ? acc - fabsf(q[k] - e[k]) : fmaf(e[k], q[k], acc);
-    if (acc > t) ++dec;
+    if (rank_score<L1>(q, E + (size_t)ent[i] * d, d) > t) ++dec;
   }
   ranks[4 * qi + 2 * dir] = 1 + raw[v];
   ranks[4 * qi + 2 * dir + 1] = 1 + raw[v] - dec;
+}
+
+// the query vectors of nq test triples into Q [2 nq][d] (2i: tail, 2i + 1:
+// head) and the true entities' scores into tgt [2 nq] (skge_host.h)
+void launch_rank_query(hipStream_t st, int model, const float* E, const float* R, int N, int d,
+                       const int* queries, int nq, float* Q, float* tgt) {
+  RankArgs a = {};
+  a.E = E;
+  a.R = R;
+  a.N = N;
+  a.d = d;
+  a.model = model;
+  a.nq = nq;
+  a.queries = queries;
+  a.Q = Q;
+  a.tgt = tgt;
+  const int qblocks = std::max(1, std::min((nq + 1) / 2, 16384));
+  hipLaunchKernelGGL(k_rank_query, dim3(qblocks), dim3(128), (size_t)2 * 5 * d * sizeof(float), st,
+                     a);
+}
+
+// raw[v] += #{rows j of T [rows][d] scoring strictly above tgt[v] under query
+// vector Q[v]}, v < nv (skge_host.h)
+void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d, const float* Q,
+                       const float* tgt, int nv, int* raw) {
+  RankArgs2 b;
+  b.E = T;
+  b.N = rows;
+  b.d = d;
+  b.nv = nv;
+  b.Q = Q;
+  b.tgt = tgt;
+  b.raw = raw;
+  // enough workgroups to fill the chip: query blocks x entity slices
+  const int qb = (nv + QB2 - 1) / QB2;
+  const int tiles = (rows + EB2 - 1) / EB2;
+  const int want = std::max(1, std::min(tiles, (2048 + qb - 1) / qb));
+  const int per = (tiles + want - 1) / want;
+  b.eslice = per * EB2;
+  const int ns = (tiles + per - 1) / per;
+  if (l1)
+    hipLaunchKernelGGL((k_rank_count2<true>), dim3(qb, ns), dim3(256), 0, st, b);
+  else
+    hipLaunchKernelGGL((k_rank_count2<false>), dim3(qb, ns), dim3(256), 0, st, b);
 }
 
 }  // namespace skge
@@ -404,51 +445,21 @@ extern "C" int skge_rank_known(void* stream, int model, const float* E, const fl
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_rank_known_workspace_bytes(nq, d),
                  "rank workspace needs %zu bytes", skge_rank_known_workspace_bytes(nq, d));
-  RankArgs a = {};
-  a.E = E;
-  a.R = R;
-  a.N = N;
-  a.d = d;
-  a.model = model;
-  a.nq = nq;
-  a.queries = queries;
-  a.has_set = 0;
-  a.Q = (float*)workspace;
-  a.tgt = a.Q + (size_t)2 * nq * d;
-  int* raw = (int*)(a.tgt + 2 * (size_t)nq);
-  a.ranks = ranks_out;
+  float* Q = (float*)workspace;
+  float* tgt = Q + (size_t)2 * nq * d;
+  int* raw = (int*)(tgt + 2 * (size_t)nq);
   hipStream_t st = as_stream(stream);
   SKGE_CHECK_HIP(hipMemsetAsync(raw, 0, (size_t)2 * nq * sizeof(int), st));
-  const int qblocks = std::max(1, std::min((nq + 1) / 2, 16384));
-  hipLaunchKernelGGL(k_rank_query, dim3(qblocks), dim3(128), (size_t)2 * 5 * d * sizeof(float), st,
-                     a);
-  RankArgs2 b;
-  b.E = E;
-  b.N = N;
-  b.d = d;
-  b.nv = 2 * nq;
-  b.Q = a.Q;
-  b.tgt = a.tgt;
-  b.raw = raw;
-  // enough workgroups to fill the chip: query blocks x entity slices
-  const int qb = (2 * nq + QB2 - 1) / QB2;
-  const int tiles = (N + EB2 - 1) / EB2;
-  const int want = std::max(1, std::min(tiles, (2048 + qb - 1) / qb));
-  const int per = (tiles + want - 1) / want;
-  b.eslice = per * EB2;
-  const int ns = (tiles + per - 1) / per;
+  launch_rank_query(st, model, E, R, N, d, queries, nq, Q, tgt);
   const bool l1 = model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2;
-  if (l1)
-    hipLaunchKernelGGL((k_rank_count2<true>), dim3(qb, ns), dim3(256), 0, st, b);
-  else
-    hipLaunchKernelGGL((k_rank_count2<false>), dim3(qb, ns), dim3(256), 0, st, b);
+  launch_rank_count(st, l1, E, N, d, Q, tgt, 2 * nq, raw);
   const int kb = (2 * nq + 255) / 256;
   if (l1)
-    hipLaunchKernelGGL((k_rank_known<true>), dim3(kb), dim3(256), 0, st, E, d, nq, a.Q, a.tgt, raw,
+    hipLaunchKernelGGL((k_rank_known<true>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
                        tail_off, tail_ent, head_off, head_ent, ranks_out);
   else
-    hipLaunchKernelGGL((k_rank_known<false>), dim3(kb), dim3(256), 0, st, E, d, nq, a.Q, a.tgt,
-                       raw, tail_off, tail_ent, head_off, head_ent, ranks_out);
+    hipLaunchKernelGGL((k_rank_known<false>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
+                       tail_off, tail_ent, head_off, head_ent, ranks_out);
   SKGE_CHECK_LAUNCH("rank (known answers)");
   return SKGE_OK;
 }

@@ -126,6 +126,17 @@ inline TripleSet triple_set_view(const void* set, int64_t capacity) {
   return ts;
 }
 
+// skge_eval.hip: the ranking entry points' steps, for callers that rank rows
+// of another table (skge_subgraph.hip).  launch_rank_query: the query vectors
+// of nq test triples (s, o, p) into Q [2 nq][d] (2i: tail, 2i + 1: head) and
+// the true entities' scores into tgt [2 nq].  launch_rank_count: raw[v] +=
+// #{rows of T [rows][d] scoring strictly above tgt[v] under Q[v]}, v < nv
+// (l1: the L1 distance, else the dot product; rank_score's chain).
+void launch_rank_query(hipStream_t st, int model, const float* E, const float* R, int N, int d,
+                       const int* queries, int nq, float* Q, float* tgt);
+void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d, const float* Q,
+                       const float* tgt, int nv, int* raw);
+
 // skge_pipeline.hip: draw every negative of the epoch whose key is *epoch_key
 // (rec[j] = (s, o, p, s' or -1), rec_n1[j] = o' or -1 for positive j of the
 // epoch's order) with the sampler smp (nullptr: RANDOM, k_epoch_sample as the
