@@ -722,6 +722,36 @@ int skge_subgraph_rank(void *stream, int model, const float *E, const float *R, 
                        const int *skip_head, const int64_t *ans_off, const int *ans_sub,
                        void *workspace, size_t ws_bytes, int *ranks_out, int *found_out);
 
+/* ---------------- nearest neighbours in embedding space ---------------- */
+
+#define SKGE_SIM_COSINE 0
+#define SKGE_SIM_DOT 1
+
+/*
+ * Nearest neighbours: for each of nq queries the k rows of T [N][d] (any fp32
+ * table with finite values) most similar to it; cosineMatrix + similarity of
+ * the reference's eval-embeddings.py.  Exactly one query form:
+ *   rows [nq]     query i is row rows[i] of T; the id rows[i] itself is never
+ *                 returned (other rows with an equal vector are);
+ *   Q [nq][d]     external vectors; nothing is excluded;
+ *   both NULL     needs nq == N: every row in order, itself excluded.
+ * Arithmetic: dot(q, j) is the fp32 fma chain over kk = 0 .. d - 1 from 0.0f
+ * (what v_mfma_f32_32x32x2_f32 computes); n2_j the same chain of row j with
+ * itself; r_j = n2_j == 0 ? 0 : 1 / sqrtf(n2_j), correctly rounded; SKGE_SIM_DOT
+ * returns dot, SKGE_SIM_COSINE (dot * r_q) * r_j -- so a zero row has cosine
+ * 0 with everything.
+ * Result: ids_out / sim_out [nq][k], ordered by descending similarity, then
+ * ascending id among exactly equal fp32 values (skge_topk's order); slots
+ * beyond the eligible rows (k > N - 1) hold id -1 and -inf.  1 <= k <= 128,
+ * d >= 1; row ids are not range-checked here.  Caller-owned buffers,
+ * stream-ordered; workspace of skge_neighbours_workspace_bytes(nq, N, d, k)
+ * bytes.
+ */
+size_t skge_neighbours_workspace_bytes(int nq, int N, int d, int k);
+int skge_neighbours(void *stream, const float *T, int N, int d, const float *Q, const int *rows,
+                    int nq, int metric, int k, void *workspace, size_t ws_bytes, int *ids_out,
+                    float *sim_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,4 +13,5 @@ from .sample import RandomModeSampler, CorruptedSampler, LCWASampler, type_index
 from .eval import FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores
 from .predict import LinkPredictor
 from .subgraphs import SUBTYPE, Subgraphs, SubgraphRankingEval, subgraph_ranking_scores
+from .neighbours import Neighbours, shared_role
 from .checkpoint import save_reference, load_reference, read_reference_state
