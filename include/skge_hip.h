@@ -417,6 +417,69 @@ int skge_triple_runner_nlaunches(const skge_triple_runner_t *r);
 void skge_triple_runner_destroy(skge_triple_runner_t *r);
 
 /*
+ * n negatives per positive over any modes: the reference's Sampler(n, modes)
+ * (skge/sample.py:10-25) for the three kinds above.  A positive has K = n *
+ * nmodes SLOTS, slot k = rep * nmodes + mi corrupting position modes[mi]
+ * (0: s, 1: o, 2: p) -- rep-major, then the order of modes, the order
+ * Sampler.sample appends.  Slot k's candidates are draw(key, j, k, try,
+ * range): the draw's field is the slot, so (1, {0, 1}) draws the records of
+ * skge_epoch_sample_ex bit for bit.  Modes 0 and 1 draw and accept as
+ * skge_sampler_t describes.  Mode 2 draws a relation id p' -- RANDOM and LCWA
+ * from [0, n_rel), TYPED from [0, rel_range), rel_range being the number of
+ * relations that occur (the reference uses len(type_index) as an id range,
+ * skge/sample.py:80) -- accepted if (s, o, p') is not a training triple and,
+ * LCWA, s is in pool 2p' (skge/sample.py:106-107).
+ * Needed: n >= 1, nmodes in [1, 8], every mode in {0, 1, 2}, K <= 64, and
+ * rel_range in [1, n_rel] when a mode is 2; a pool kind's smp->n_rel must be
+ * n_rel.
+ *
+ * skge_epoch_sample_multi writes, for position j of the epoch's order,
+ * pos [T][3] = the positive (s, o, p) and neg [T][K] = slot k's corrupted id
+ * (an entity for modes 0 and 1, a relation for mode 2) or -1 if none of ntries
+ * candidates was accepted.
+ *
+ * skge_pair_runner_create_multi / skge_triple_runner_create_multi are the pair
+ * loop and the logistic loop over those draws (run, nlaunches and destroy are
+ * the ones above).  Every batch's explicit input is built once per epoch in
+ * the reference's order -- pair loop: positive j gives pairs jK .. jK + K - 1
+ * (skge/base.py:1394-1427); logistic loop: a batch of c positives is the c
+ * positives, then the negative of (j, k) at c + jK + k (`xys +=
+ * samplef(xys)`); a slot holding -1 is a skipped pair / triple in place -- and
+ * each batch is one skge_pair_step on K * c pairs or one skge_triple_step on
+ * (1 + K) * c triples (every model runs its explicit-pair / explicit-triple
+ * kernels here).  ent needs 4 * K * batch_size touched slots for pairs and
+ * 2 * (1 + K) * batch_size for triples, rel (if it records slots) half that
+ * (RESCAL's W: rel->rows); a smaller table is refused.
+ */
+typedef struct {
+  int n, nmodes;
+  int modes[8];
+  int rel_range; /* TYPED with a mode 2: len(type_index); else n_rel */
+} skge_negatives_t;
+int skge_epoch_sample_multi(void *stream, const int *trip, int64_t T, const void *set,
+                            int64_t set_capacity, int n_ent, int n_rel, uint64_t seed,
+                            const uint64_t *epoch_key, int ntries, int *pos, int *neg,
+                            const skge_sampler_t *smp, const skge_negatives_t *negs);
+skge_pair_runner_t *skge_pair_runner_create_multi(void *stream, int model, int af,
+                                                  const skge_table_t *ent,
+                                                  const skge_table_t *rel, int d, const int *trip,
+                                                  int64_t T, const void *set,
+                                                  int64_t set_capacity, int nbatches,
+                                                  uint64_t seed, uint64_t *epoch_key, float margin,
+                                                  int ntries, int *nviol_total,
+                                                  const skge_sampler_t *smp,
+                                                  const skge_negatives_t *negs);
+skge_triple_runner_t *skge_triple_runner_create_multi(void *stream, int model,
+                                                      const skge_table_t *ent,
+                                                      const skge_table_t *rel, int d,
+                                                      const int *trip, int64_t T, const void *set,
+                                                      int64_t set_capacity, int nbatches,
+                                                      uint64_t seed, uint64_t *epoch_key,
+                                                      int ntries, float *loss_total,
+                                                      const skge_sampler_t *smp,
+                                                      const skge_negatives_t *negs);
+
+/*
  * Pipelined epoch runner for TransE-L1 with packed accumulators (the
  * throughput path).  Same result, bit for bit, as skge_runner_create's loop
  * with the same tables and arguments: all negatives of an epoch are drawn in

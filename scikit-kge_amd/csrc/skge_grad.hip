@@ -17,6 +17,7 @@
 #include "skge_hole.h"
 #include "skge_hole_fft.h"
 #include "skge_host.h"
+#include "skge_sampler.h"
 
 namespace skge {
 
@@ -1144,6 +1145,203 @@ __global__ __launch_bounds__(256) void k_rescal_wgrad(const float* __restrict__ 
       if (r < d && c < d) out[(size_t)r * d + c] = acc[x][y];
     }
   if (tt == 0 && t == 0) accW.cnt[p] = total;
+}
+
+// ---------------------------------------------------------------------------
+// TransE, one wave per positive and its K negatives (the device pair loop with
+// n negatives per positive, skge_pairloop.hip).  Slot k of positive (s, o, p)
+// holds the id c that replaces s (mode 0), o (mode 1) or p (mode 2), or -1:
+// the pairs (s, o, p) / (c, o, p), (s, c, p), (s, o, c) of the explicit path.
+// The wave loads E[s], R[p], E[o] once and scores the positive once; per slot
+// it loads ONE row (E[c] or R[c]; the next slot's row is requested before the
+// current slot's reduction), scores the negative with the explicit kernel's
+// expression ((E[sn] + R[pn]) - E[on], the same wave_sum) and applies the
+// strict margin test, so the decisions are transe_pair's.  Of a violating
+// pair's six contribution rows (transe.py:128-136, 158-160: sp +gp, op -gp,
+// pp +gp, sn +gn, on -gn, pn +gn) only the corrupted position's goes to a row
+// of its own; the five that land on s, o or p are summed in registers and
+// added once per positive, with the number of occurrences as the count, so
+// the segment mean (util.py:53-101) has the explicit path's sums and counts:
+//   E[s]: V gp + sum gn (modes 1, 2)     count V + #(modes 1, 2)
+//   E[o]: -V gp - sum gn (modes 0, 2)    count V + #(modes 0, 2)
+//   R[p]: V gp + sum gn (modes 0, 1)     count V + #(modes 0, 1)
+// (V = the positive's violating slots).  L1's rows are signs: every sum is a
+// small integer, exact in fp32 in any order, so the tables come out bit for
+// bit as on the explicit path; L2's differ by float summation order.
+// Slots: entity (2 + K) j + {0: s, 1: o, 2 + k: slot k's entity}, relation
+// (1 + K) j + {0: p, 1 + k: slot k's relation}; a slot that adds nothing is -1.
+// E.violations (transe.py:78-83: +1 per violating pair per distinct id of
+// {sn, on, sp, op}): s once per violating slot, o likewise unless o == s, the
+// corrupted entity unless it is s or o.
+// ---------------------------------------------------------------------------
+struct PosMultiArgs {
+  const float* E;
+  const float* R;
+  Accum accE, accR;
+  const int* pos3;   // [T][3]
+  const int* negK;   // [T][K]
+  long long start;   // this batch: positives [start, start + count)
+  int count, d;
+  Negatives ng;
+  float margin;
+  int* nviol;
+  int* eviol;
+};
+
+template <int KM, bool L1>
+__global__ __launch_bounds__(256) void k_transe_pos_multi(PosMultiArgs a) {
+  const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6, l = lane_id();
+  const int d = a.d, K = a.ng.K;
+  int nv = 0;
+  for (int j = blockIdx.x * wpb + wave; j < a.count; j += gridDim.x * wpb) {
+    const long long g = a.start + j;
+    const int* nk = a.negK + g * K;
+    const int s = uni(a.pos3[3 * g]), o = uni(a.pos3[3 * g + 1]), p = uni(a.pos3[3 * g + 2]);
+    float es[KM], rp[KM], eo[KM], gp[KM], as[KM], ao[KM], ap[KM], cur[KM], nxt[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, o, d, eo);
+    int c = uni(nk[0]), mode = slot_mode(a.ng, 0);
+#pragma unroll
+    for (int k = 0; k < KM; ++k) nxt[k] = 0.0f;   // (a skipped slot's row is never read)
+    if (c >= 0) load_row<KM>(mode == 2 ? a.R : a.E, c, d, nxt);
+    float ps = 0.0f;
+#pragma unroll
+    for (int k = 0; k < KM; ++k) {
+      const float vp = (es[k] + rp[k]) - eo[k];   // transe.py:32
+      ps += L1 ? fabsf(vp) : vp * vp;
+      const float tp = (eo[k] - rp[k]) - es[k];   // transe.py:103
+      gp[k] = L1 ? signf_np(-tp) : -tp;           // transe.py:115 / 120
+      as[k] = ao[k] = ap[k] = 0.0f;
+    }
+    const float pscore = -wave_sum(ps);
+    const Accum aR = replica(a.accR, g);
+    const long long eb = (long long)(2 + K) * j, rb = (long long)(1 + K) * j;
+    int V = 0, cs = 0, co = 0, cp = 0;
+    for (int k = 0; k < K; ++k) {
+      const int ck = c, mk = mode;
+#pragma unroll
+      for (int q = 0; q < KM; ++q) cur[q] = nxt[q];
+      if (k + 1 < K) {   // the next slot's row, ahead of this slot's reduction
+        c = uni(nk[k + 1]);
+        mode = slot_mode(a.ng, k + 1);
+        if (c >= 0) load_row<KM>(mode == 2 ? a.R : a.E, c, d, nxt);
+      }
+      bool viol = false;
+      float gn[KM];
+      if (ck >= 0) {
+        float ns = 0.0f;
+#pragma unroll
+        for (int q = 0; q < KM; ++q) {
+          const float fs = mk == 0 ? cur[q] : es[q], fo = mk == 1 ? cur[q] : eo[q];
+          const float rn = mk == 2 ? cur[q] : rp[q];
+          const float vn = (fs + rn) - fo;
+          ns += L1 ? fabsf(vn) : vn * vn;
+          const float tn = (fo - rn) - fs;        // transe.py:103
+          gn[q] = L1 ? signf_np(tn) : tn;         // transe.py:117 / 121
+        }
+        const float nscore = -wave_sum(ns);
+        viol = nscore + a.margin > pscore;        // strict >  (transe.py:73)
+      }
+      // the corrupted position's own row and slot (the other table's slot is -1)
+      if (l == 0) commit_slot(a.accE, ck, viol && mk != 2 ? 1 : 0, (int)(eb + 2 + k));
+      if (l == 1) commit_slot(aR, ck, viol && mk == 2 ? 1 : 0, (int)(rb + 1 + k));
+      if (!viol) continue;
+      ++V;
+      if (mk == 0) {          // (c, o, p): sn = c
+        acc_row<KM>(a.accE, ck, gn, d);
+        ++co;
+        ++cp;
+      } else if (mk == 1) {   // (s, c, p): on = c
+        float ngn[KM];
+#pragma unroll
+        for (int q = 0; q < KM; ++q) ngn[q] = -gn[q];
+        acc_row<KM>(a.accE, ck, ngn, d);
+        ++cs;
+        ++cp;
+      } else {                // (s, o, c): pn = c
+        acc_row<KM>(aR, ck, gn, d);
+        ++cs;
+        ++co;
+      }
+#pragma unroll
+      for (int q = 0; q < KM; ++q) {
+        if (mk != 0) as[q] += gn[q];
+        if (mk != 1) ao[q] -= gn[q];
+        if (mk != 2) ap[q] += gn[q];
+      }
+      if (a.eviol && l == 0 && mk != 2 && ck != s && ck != o) atomicAdd(a.eviol + ck, 1);
+    }
+    if (V > 0) {
+      const float fv = (float)V;
+#pragma unroll
+      for (int q = 0; q < KM; ++q) {
+        as[q] += fv * gp[q];
+        ao[q] -= fv * gp[q];
+        ap[q] += fv * gp[q];
+      }
+      acc_row<KM>(a.accE, s, as, d);
+      acc_row<KM>(a.accE, o, ao, d);
+      acc_row<KM>(aR, p, ap, d);
+      if (a.eviol && l < 2 && (l == 0 || o != s)) atomicAdd(a.eviol + (l == 0 ? s : o), V);
+    }
+    if (l == 0) commit_slot(a.accE, s, V > 0 ? V + cs : 0, (int)eb);
+    if (l == 1) commit_slot(a.accE, o, V > 0 ? V + co : 0, (int)(eb + 1));
+    if (l == 2) commit_slot(aR, p, V > 0 ? V + cp : 0, (int)rb);
+    nv += V;
+  }
+  __shared__ int lds_nv;
+  if (a.nviol) block_count_add(a.nviol, nv, &lds_nv);   // one atomic per workgroup
+}
+
+int launch_transe_pos_multi(hipStream_t st, int l1, const skge_table_t* ent,
+                            const skge_table_t* rel, int d, const int* pos3, const int* negK,
+                            long long start, int count, const Negatives& ng, float margin,
+                            int* nviol) {
+  int rc;
+  if ((rc = check_table(ent, "ent", true)) || (rc = check_table(rel, "rel", true)) ||
+      (rc = check_f32(ent, "ent")) || (rc = check_f32(rel, "rel")) ||
+      (rc = check_single(ent, "ent")))
+    return rc;
+  SKGE_CHECK_ARG(d > 0 && ent->width == d && rel->width == d, "table widths differ from d %d", d);
+  SKGE_CHECK_ARG(km_for(d) != 0, "d=%d > 1024 unsupported", d);
+  SKGE_CHECK_ARG(pos3 && negK && nviol && count >= 0 && ng.K >= 1 && ng.K <= 64, "bad argument");
+  if ((rc = check_slots(ent, (long long)(2 + ng.K) * count, "ent")) ||
+      (rc = check_slots(rel, (long long)(1 + ng.K) * count, "rel")))
+    return rc;
+  if (count == 0) return SKGE_OK;
+  PosMultiArgs a = {};
+  a.E = ent->param;
+  a.R = rel->param;
+  a.accE = accum_of(ent);
+  a.accR = accum_of(rel);
+  a.pos3 = pos3;
+  a.negK = negK;
+  a.start = start;
+  a.count = count;
+  a.d = d;
+  a.ng = ng;
+  a.margin = margin;
+  a.nviol = nviol;
+  a.eviol = ent->violations;
+  const int blocks = std::max(1, std::min((count + 3) / 4, 8192));
+#define SKGE_TPM(KM)                                                                        \
+  case KM:                                                                                  \
+    if (l1) hipLaunchKernelGGL((k_transe_pos_multi<KM, true>), dim3(blocks), dim3(256), 0, st, a);  \
+    else hipLaunchKernelGGL((k_transe_pos_multi<KM, false>), dim3(blocks), dim3(256), 0, st, a);    \
+    break;
+  switch (km_for(d)) {
+    SKGE_TPM(1)
+    SKGE_TPM(2)
+    SKGE_TPM(3)
+    SKGE_TPM(4)
+    SKGE_TPM(8)
+    default:
+    SKGE_TPM(16)
+  }
+#undef SKGE_TPM
+  SKGE_CHECK_LAUNCH("transe positive (multi) launch");
+  return SKGE_OK;
 }
 
 // ---------------------------------------------------------------------------

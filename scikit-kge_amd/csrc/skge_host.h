@@ -147,6 +147,26 @@ int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t s
 // SKGE_EINVAL (and the error text) for an unknown kind or, for a pool kind,
 // n_rel <= 0 or NULL pools; the pools' contents are not read
 int check_sampler(const skge_sampler_t* smp, const char* who);
+// skge_pipeline.hip: the n-negatives draw (include/skge_hip.h,
+// skge_negatives_t).  check_negatives: SKGE_EINVAL (and the error text) for
+// the refusals listed there; *K = n * nmodes.  launch_epoch_sample_multi:
+// pos [T][3], neg [T][K] of the epoch whose key is *epoch_key (both checks
+// first).
+int check_negatives(const skge_negatives_t* negs, const skge_sampler_t* smp, int n_rel,
+                    const char* who, int* K);
+int launch_epoch_sample_multi(hipStream_t st, const int* trip, long long T, uint64_t seed,
+                              const uint64_t* epoch_key, TripleSet set, int n_ent, int n_rel,
+                              int ntries, int* pos, int* neg, const skge_sampler_t* smp,
+                              const skge_negatives_t* negs);
+// skge_grad.hip: TransE with K negatives per positive, one wave per positive
+// (k_transe_pos_multi): batch positives [start, start + count) of pos3 [T][3]
+// / negK [T][K] scored, margin-tested and accumulated; slots per positive:
+// 2 + K entity, 1 + K relation.  *nviol += the violating pairs.
+struct Negatives;
+int launch_transe_pos_multi(hipStream_t st, int l1, const skge_table_t* ent,
+                            const skge_table_t* rel, int d, const int* pos3, const int* negK,
+                            long long start, int count, const Negatives& ng, float margin,
+                            int* nviol);
 
 // skge_grad.hip: HolE pairwise, one positive (both of its pairs) per wave
 bool hole_pos_ok(int af, const skge_table_t* ent, const skge_table_t* rel, int d);

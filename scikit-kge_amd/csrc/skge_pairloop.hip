@@ -76,6 +76,40 @@ __global__ __launch_bounds__(256) void k_pairs_of_epoch(const int4* __restrict__
   }
 }
 
+// The explicit pairs of an epoch drawn with n negatives per positive over any
+// modes (k_epoch_sample_multi's pos3 [T][3], negK [T][K]): one lane per
+// (positive j, slot k) writes pair jK + k, the order
+// PairwiseStochasticTrainer._process_batch appends (skge/base.py:1394-1427:
+// per positive, every negative its sampler returned).  Slot k's id replaces s
+// (mode 0), o (mode 1) or p (mode 2); a slot holding -1 is a skipped pair in
+// place, as k_pairs_of_epoch's.  Clears the batches' gate words.
+__global__ __launch_bounds__(256) void k_pairs_of_epoch_multi(const int* __restrict__ pos3,
+                                                              const int* __restrict__ negK,
+                                                              long long T, Negatives ng,
+                                                              int* __restrict__ pos,
+                                                              int* __restrict__ neg,
+                                                              int* __restrict__ gates, int nb) {
+  const long long total = T * ng.K;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    if (i < nb) gates[i] = 0;
+    if (pos == nullptr) continue;   // TransE per-positive kernel: the records are its input
+    const long long j = i / ng.K;
+    const int mode = slot_mode(ng, (int)(i - j * ng.K));
+    const int s = pos3[3 * j], o = pos3[3 * j + 1], p = pos3[3 * j + 2];
+    const int c = negK[i];
+    const bool keep = c >= 0;
+    int* pp = pos + 3 * (size_t)i;
+    int* nn = neg + 3 * (size_t)i;
+    pp[0] = s;
+    pp[1] = o;
+    pp[2] = keep ? p : -1;
+    nn[0] = !keep ? -1 : mode == 0 ? c : s;
+    nn[1] = !keep ? -1 : mode == 1 ? c : o;
+    nn[2] = !keep ? -1 : mode == 2 ? c : p;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_pairs_epoch_end(const int* __restrict__ gates, int nb,
                                                          int* nviol_total, uint64_t* ek) {
   __shared__ int part[4];
@@ -93,6 +127,8 @@ __global__ __launch_bounds__(256) void k_pairs_epoch_end(const int* __restrict__
 }  // namespace skge
 
 using namespace skge;
+
+constexpr int TRANSE_POS_MIN_K = 10;   // k_transe_pos_multi is the default from here on
 
 struct skge_pair_runner : GraphRunnerCore {
   int4* rec = nullptr;
@@ -220,6 +256,119 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create(
   return skge_pair_runner_create_ex(stream, model, af, ent, rel, d, trip, T, set, set_capacity,
                                     nbatches, seed, epoch_key, margin, ntries, nviol_total,
                                     nullptr);
+}
+
+// The pair loop with n negatives per positive over any modes: the same epoch
+// (draw, build, one skge_pair_step per batch on K * count pairs, epoch end)
+// and the same runner struct, so run / nlaunches / destroy are shared.  HolE
+// and RESCAL run their explicit-pair kernels (k_hole_pos and RESCAL's rpos
+// path are two-negative forms by construction).  TransE scores a positive and
+// its K negatives in one wave straight from the records (k_transe_pos_multi,
+// skge_grad.hip: the same pairs, decisions, sums and counts; 2 + K entity and
+// 1 + K relation slots per positive) from K = 10 on; SKGE_TRANSE_PAIRS=1 / =0
+// force the explicit pairs / the per-positive kernel.
+extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
+    void* stream, int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
+    uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total,
+    const skge_sampler_t* smp, const skge_negatives_t* negs) {
+  if (!ent || !rel) return fail("pair runner: NULL table");
+  if (check_sampler(smp, "pair runner")) return nullptr;
+  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("pair runner: unknown model");
+  int K = 0;
+  if (check_negatives(negs, smp, rel->rows, "pair runner", &K)) return nullptr;
+  // pairs, their 3 ids and their 4 entity slots are indexed with ints
+  if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX / (4 * K), nbatches,
+                         set_capacity, 2 * T, ntries, stream))
+    return nullptr;
+  hipStream_t st = as_stream(stream);
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  const int Pmax = (int)(K * batches.maxb);
+  if (ent->acc_touched && (long long)4 * Pmax > ent->touched_cap)
+    return fail("pair runner: entity accumulator needs 4 * K * batch_size = %lld touched slots, "
+                "has %lld", (long long)4 * Pmax, (long long)ent->touched_cap);
+  if (rel->acc_touched) {
+    const long long need = model == SKGE_RESCAL ? rel->rows : (long long)2 * Pmax;
+    if (need > rel->touched_cap)
+      return fail("pair runner: relation accumulator needs %lld touched slots, has %lld", need,
+                  (long long)rel->touched_cap);
+  }
+  const int nb = batches.size();
+  // TransE: the per-positive kernel from K = 10 on, where it was measured to
+  // win (1.9x at K = 10, 2.2x at K = 20; at K = 2 the two forms tie and the
+  // explicit pairs stay).  SKGE_TRANSE_PAIRS=1 forces the explicit
+  // pairs, =0 the per-positive kernel, at any K.
+  const char* tp = getenv("SKGE_TRANSE_PAIRS");
+  const bool tpos = (model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2) &&
+                    (tp ? atoi(tp) == 0 : K >= TRANSE_POS_MIN_K) && ent->acc_replicas <= 1;
+  std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
+  r->ws_bytes = skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
+  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
+  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
+  if (!tpos) r->pairs = (int*)r->alloc((size_t)T * K * 6 * sizeof(int), false);
+  r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  if (!r->alloc_ok) return fail("pair runner: device allocation failed");
+  int* pos = r->pairs;
+  int* neg = r->pairs ? r->pairs + (size_t)T * K * 3 : nullptr;
+  const Negatives ng = negatives_of(negs);
+  const TripleSet ts = triple_set_view(set, set_capacity);
+  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
+    return fail("pair runner: HolE FFT twiddle table allocation failed");
+  if (!r->begin_capture(st)) return nullptr;
+  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
+                                     rel->rows, ntries, pos3, negK, smp, negs);
+  if (!rc) {
+    const int64_t blocks = std::max((int64_t)1, std::min((T * K + 255) / 256, (int64_t)4096));
+    hipLaunchKernelGGL(k_pairs_of_epoch_multi, dim3((unsigned)blocks), dim3(256), 0, st, pos3,
+                       negK, (long long)T, ng, pos, neg, r->nviol, nb);
+    if (hipGetLastError() != hipSuccess) {
+      set_error("pairs launch failed");
+      rc = SKGE_EHIP;
+    }
+  }
+  for (int k = 0; k < nb && !rc; ++k) {
+    const int count = (int)batches[k].second;
+    int* gate = r->nviol + k;
+    if (tpos) {
+      rc = launch_transe_pos_multi(st, model == SKGE_TRANSE_L1, ent, rel, d, pos3, negK,
+                                   batches[k].first, count, ng, margin, gate);
+      if (!rc) {
+        skge_table_t t[2] = {*ent, *rel};
+        t[0].gate = gate;
+        t[1].gate = gate;
+        const int ns[2] = {(2 + K) * count, (1 + K) * count};
+        rc = skge_accum_apply(stream, t, 2, ns);
+      }
+      continue;
+    }
+    const size_t at = (size_t)3 * K * batches[k].first;
+    rc = skge_pair_step(stream, model, af, ent, rel, d, pos + at, neg + at, K * count, margin,
+                        r->ws, r->ws_bytes, gate);
+  }
+  if (!rc) {
+    hipLaunchKernelGGL(k_pairs_epoch_end, dim3(1), dim3(256), 0, st, r->nviol, nb, nviol_total,
+                       epoch_key);
+    if (hipGetLastError() != hipSuccess) {
+      set_error("epoch end launch failed");
+      rc = SKGE_EHIP;
+    }
+  }
+  return r->end_capture(st, rc) ? r.release() : nullptr;
+}
+
+extern "C" int skge_epoch_sample_multi(void* stream, const int* trip, int64_t T, const void* set,
+                                       int64_t set_capacity, int n_ent, int n_rel, uint64_t seed,
+                                       const uint64_t* epoch_key, int ntries, int* pos, int* neg,
+                                       const skge_sampler_t* smp, const skge_negatives_t* negs) {
+  SKGE_CHECK_ARG(trip && set && epoch_key && pos && neg, "NULL argument");
+  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
+  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
+                 "set capacity must be a power of 2 >= 2T");
+  SKGE_CHECK_ARG(n_ent > 0 && ntries >= 1, "bad n_ent / ntries");
+  return launch_epoch_sample_multi(as_stream(stream), trip, (long long)T, seed, epoch_key,
+                                   triple_set_view(set, set_capacity), n_ent, n_rel, ntries, pos,
+                                   neg, smp, negs);
 }
 
 extern "C" int skge_epoch_sample_ex(void* stream, const int* trip, int64_t T, const void* set,

@@ -841,6 +841,86 @@ int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t s
   return SKGE_OK;
 }
 
+// n negatives per positive over any modes (skge_sampler.h sample_slot): one
+// lane per (positive, slot).  The rejection loops of a wave's lanes end at
+// different tries and the wave runs its slowest lane's count either way; with
+// one lane per positive that lane would also run its K slots one after the
+// other, K times the dependent loads per lane, and write neg [T][K] with a
+// stride of K ints.  Per slot, consecutive lanes write consecutive ints, the K
+// lanes of a positive read the same 12 bytes of trip (one line), and each
+// redoes the Feistel walk (ALU only).  The slot-0 lane writes the positive.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_epoch_sample_multi(
+    const int* __restrict__ trip, long long T, int half, uint64_t seed, const uint64_t* ekp,
+    TripleSet set, Pools pl, int n_ent, int n_rel, int ntries, Negatives ng,
+    int* __restrict__ pos, int* __restrict__ neg) {
+  const uint64_t ek = *ekp;
+  const Perm pm = {(uint64_t)T, half, epoch_perm_key(seed, ek)};
+  const uint64_t skey = epoch_sample_key(seed, ek);
+  const long long total = T * ng.K;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long j = i / ng.K;
+    const int k = (int)(i - j * ng.K);
+    const long long t = (long long)perm_index((uint64_t)j, pm);
+    const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
+    if (k == 0) {
+      pos[3 * j] = s;
+      pos[3 * j + 1] = o;
+      pos[3 * j + 2] = p;
+    }
+    neg[i] = sample_slot<KIND>(skey, set, pl, n_ent, n_rel, ng, ntries, j, k, s, o, p);
+  }
+}
+
+int check_negatives(const skge_negatives_t* negs, const skge_sampler_t* smp, int n_rel,
+                    const char* who, int* K) {
+  SKGE_CHECK_ARG(negs != nullptr, "%s: negatives are NULL", who);
+  SKGE_CHECK_ARG(negs->n >= 1, "%s: n = %d negatives per mode, must be >= 1", who, negs->n);
+  SKGE_CHECK_ARG(negs->nmodes >= 1 && negs->nmodes <= 8, "%s: nmodes %d must be in [1, 8]", who,
+                 negs->nmodes);
+  bool rel = false;
+  for (int i = 0; i < negs->nmodes; ++i) {
+    SKGE_CHECK_ARG(negs->modes[i] >= 0 && negs->modes[i] <= 2, "%s: mode %d is not 0, 1 or 2", who,
+                   negs->modes[i]);
+    rel = rel || negs->modes[i] == 2;
+  }
+  SKGE_CHECK_ARG(negs->n <= 64 && negs->n * negs->nmodes <= 64,
+                 "%s: K = n * nmodes = %lld slots per positive, at most 64", who,
+                 (long long)negs->n * negs->nmodes);
+  SKGE_CHECK_ARG(n_rel >= 1, "%s: n_rel %d must be >= 1", who, n_rel);
+  SKGE_CHECK_ARG(!rel || (negs->rel_range >= 1 && negs->rel_range <= n_rel),
+                 "%s: rel_range %d must be in [1, n_rel = %d]", who, negs->rel_range, n_rel);
+  SKGE_CHECK_ARG(!smp || smp->kind == SKGE_SAMPLER_RANDOM || smp->n_rel == n_rel,
+                 "%s: the sampler's n_rel %d is not n_rel = %d", who, smp ? smp->n_rel : 0, n_rel);
+  *K = negs->n * negs->nmodes;
+  return SKGE_OK;
+}
+
+int launch_epoch_sample_multi(hipStream_t st, const int* trip, long long T, uint64_t seed,
+                              const uint64_t* epoch_key, TripleSet set, int n_ent, int n_rel,
+                              int ntries, int* pos, int* neg, const skge_sampler_t* smp,
+                              const skge_negatives_t* negs) {
+  int K = 0;
+  if (int rc = check_sampler(smp, "epoch sample")) return rc;
+  if (int rc = check_negatives(negs, smp, n_rel, "epoch sample", &K)) return rc;
+  const Negatives ng = negatives_of(negs);
+  long long blocks = (T * K + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
+  Pools pl = {nullptr, nullptr, 0};
+  if (kind != SKGE_SAMPLER_RANDOM) pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
+#define SKGE_SAMPLE_MULTI(KIND)                                                                 \
+  hipLaunchKernelGGL(k_epoch_sample_multi<KIND>, dim3((unsigned)blocks), dim3(256), 0, st, trip, \
+                     T, perm_half(T), seed, epoch_key, set, pl, n_ent, n_rel, ntries, ng, pos, neg)
+  if (kind == SKGE_SAMPLER_RANDOM) SKGE_SAMPLE_MULTI(SAMPLER_RANDOM);
+  else if (kind == SKGE_SAMPLER_TYPED) SKGE_SAMPLE_MULTI(SAMPLER_TYPED);
+  else SKGE_SAMPLE_MULTI(SAMPLER_LCWA);
+#undef SKGE_SAMPLE_MULTI
+  SKGE_CHECK_LAUNCH("epoch sample (multi)");
+  return SKGE_OK;
+}
+
 }  // namespace skge
 
 using namespace skge;

@@ -3,6 +3,7 @@
 // RandomModeSampler draws (skge/sample.py:41-46) and, over the type index'
 // pools, the CorruptedSampler and LCWASampler draws (skge/sample.py:68-120).
 #pragma once
+#include "../../include/skge_hip.h"
 #include "skge_device.h"
 
 namespace skge {
@@ -185,6 +186,76 @@ __device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip
   }
   rec[j] = make_int4(s, o, p, neg0);
   rec_n1[j] = neg1;
+}
+
+// ---- n negatives per positive over any modes (skge/sample.py:10-25) ----
+//
+// Sampler(n, modes).sample appends, per positive, n repetitions of one
+// negative per entry of modes: K = n * nmodes slots, slot k = rep * nmodes +
+// mi corrupting position modes[mi] (0: s, 1: o, 2: p).  The device form of
+// skge_negatives_t: the modes packed two bits each, so that a lane picks its
+// slot's mode with a shift instead of indexing a kernel-argument array.
+struct Negatives {
+  int K, nmodes;
+  uint32_t modes;   // mode of entry mi in bits [2 mi, 2 mi + 2)
+  int rel_range;    // TYPED's mode-2 range (skge/sample.py:80)
+};
+
+// the device form of a checked skge_negatives_t (check_negatives, skge_host.h)
+inline Negatives negatives_of(const skge_negatives_t* negs) {
+  uint32_t m = 0;
+  for (int i = 0; i < negs->nmodes; ++i) m |= (uint32_t)negs->modes[i] << (2 * i);
+  return {negs->n * negs->nmodes, negs->nmodes, m, negs->rel_range};
+}
+
+__device__ __forceinline__ int slot_mode(const Negatives& ng, int k) {
+  return (int)((ng.modes >> (2 * (k % ng.nmodes))) & 3u);
+}
+
+// The corrupted id of slot k of positive (s, o, p) at position j of the
+// epoch's order: the first of ntries candidates draw(skey, j, k, tr, range)
+// that its kind accepts, or -1.  The draw's field is the SLOT, not the mode:
+// at (1, [0, 1]) the two coincide and this is sample_record's (KIND ==
+// SAMPLER_RANDOM) or sample_record_pools' draw, bit for bit.
+//   mode 0 / 1: as those two draw and accept.
+//   mode 2: a relation id p' from [0, n_rel) -- TYPED: from [0, rel_range),
+//     the number of relations that occur used as an id range, the reference's
+//     quirk -- accepted if (s, o, p') is not a training triple and, LCWA, s is
+//     in pool 2p' (counts[(s, p')] > 0, skge/sample.py:106-107).
+template <int KIND>
+__device__ __forceinline__ int sample_slot(uint64_t skey, const TripleSet& set, const Pools& pl,
+                                           int n_ent, int n_rel, const Negatives& ng, int ntries,
+                                           long long j, int k, int s, int o, int p) {
+  const int mode = slot_mode(ng, k);
+  if (mode == 2) {
+    const int range = KIND == SAMPLER_TYPED ? ng.rel_range : n_rel;
+    for (int tr = 0; tr < ntries; ++tr) {
+      const int c = draw(skey, j, k, tr, range);
+      if (KIND == SAMPLER_LCWA &&
+          !(c < pl.n_rel && pool_contains(pl.ent, pl.off[2 * c], pl.off[2 * c + 1], s)))
+        continue;
+      if (!set_contains(set, s, o, c)) return c;
+    }
+    return -1;
+  }
+  // the pool this slot draws from (TYPED) or tests against (LCWA mode 0)
+  long long b = 0, e = 0;
+  const bool pooled = KIND == SAMPLER_TYPED || (KIND == SAMPLER_LCWA && mode == 0);
+  if (pooled) {
+    if (p >= 0 && p < pl.n_rel) {
+      b = pl.off[2 * p + (KIND == SAMPLER_TYPED ? mode : 0)];
+      e = pl.off[2 * p + (KIND == SAMPLER_TYPED ? mode : 0) + 1];
+    }
+    if (e <= b) return -1;
+  }
+  const int range = KIND == SAMPLER_TYPED ? (int)(e - b) : n_ent;
+  for (int tr = 0; tr < ntries; ++tr) {
+    int c = draw(skey, j, k, tr, range);
+    if (KIND == SAMPLER_TYPED) c = pl.ent[b + c];
+    else if (pooled && !pool_contains(pl.ent, b, e, c)) continue;
+    if (!(mode == 0 ? set_contains(set, c, o, p) : set_contains(set, s, c, p))) return c;
+  }
+  return -1;
 }
 
 }  // namespace skge

@@ -28,6 +28,7 @@
 
 #include "skge_graph_runner.h"
 #include "skge_hole_fft.h"
+#include "skge_sampler.h"
 
 namespace skge {
 
@@ -58,6 +59,47 @@ __global__ __launch_bounds__(256) void k_triples_of_epoch(const int4* __restrict
       o[2] = tr[t][2];
       ys[at[t]] = t == 0 ? 1.0f : -1.0f;
     }
+  }
+}
+
+// The labelled triples of an epoch drawn with n negatives per positive over any
+// modes (k_epoch_sample_multi's pos3 [T][3], negK [T][K]): batch b of c
+// positives owns (1 + K) c positions -- the c positives (y = +1), then the
+// negative of (positive j, slot k) at c + jK + k (y = -1), the order `xys +=
+// samplef(xys)` gives with Sampler.sample's rep-major slots.  One lane per
+// (positive, slot); the slot-0 lane writes the positive.  A slot holding -1 is
+// a skipped triple in place (it keeps the positive's ids, which are not read).
+__global__ __launch_bounds__(256) void k_triples_of_epoch_multi(const int* __restrict__ pos3,
+                                                                const int* __restrict__ negK,
+                                                                long long T, long long bs,
+                                                                Negatives ng,
+                                                                int* __restrict__ trip,
+                                                                float* __restrict__ ys) {
+  const long long total = T * ng.K;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long j = i / ng.K;
+    const int k = (int)(i - j * ng.K);
+    const long long s0 = (j / bs) * bs;                       // the batch's first positive
+    const long long c = s0 + bs <= T ? bs : T - s0, jj = j - s0;
+    const size_t base = (size_t)(1 + ng.K) * s0;
+    const int s = pos3[3 * j], o = pos3[3 * j + 1], p = pos3[3 * j + 2];
+    if (k == 0) {
+      int* w = trip + 3 * (base + jj);
+      w[0] = s;
+      w[1] = o;
+      w[2] = p;
+      ys[base + jj] = 1.0f;
+    }
+    const int mode = slot_mode(ng, k);
+    const int id = negK[i];
+    const bool keep = id >= 0;
+    const size_t at = base + c + jj * ng.K + k;
+    int* w = trip + 3 * at;
+    w[0] = keep && mode == 0 ? id : s;
+    w[1] = keep && mode == 1 ? id : o;
+    w[2] = !keep ? -1 : mode == 2 ? id : p;
+    ys[at] = -1.0f;
   }
 }
 
@@ -278,6 +320,73 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create(
     uint64_t* epoch_key, int ntries, float* loss_total) {
   return skge_triple_runner_create_ex(stream, model, ent, rel, d, trip, T, set, set_capacity,
                                       nbatches, seed, epoch_key, ntries, loss_total, nullptr);
+}
+
+// The logistic loop with n negatives per positive over any modes: the same
+// epoch (draw, build, one skge_triple_step per batch on (1 + K) * count
+// triples, key + 1) and the same runner struct, so run / nlaunches / destroy
+// are shared.  HolE runs its explicit-triple kernels: k_hole_logistic_pos is a
+// two-negative form by construction.
+extern "C" skge_triple_runner_t* skge_triple_runner_create_multi(
+    void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
+    uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp,
+    const skge_negatives_t* negs) {
+  if (!ent || !rel) return fail("triple runner: NULL table");
+  if (check_sampler(smp, "triple runner")) return nullptr;
+  if (model != SKGE_HOLE && model != SKGE_RESCAL)
+    return fail("triple runner: logistic loss is defined for HolE and RESCAL only");
+  int K = 0;
+  if (check_negatives(negs, smp, rel->rows, "triple runner", &K)) return nullptr;
+  // triples, their 3 ids and their 2 entity slots are indexed with ints
+  if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / (3 * (1 + K)),
+                         nbatches, set_capacity, 2 * T, ntries, stream))
+    return nullptr;
+  hipStream_t st = as_stream(stream);
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  const int64_t bs = batches.bs, maxb = batches.maxb;
+  const long long Tmax = (long long)(1 + K) * maxb;
+  if (ent->acc_touched && 2 * Tmax > ent->touched_cap)
+    return fail("triple runner: entity accumulator needs 2 * (1 + K) * batch_size = %lld touched "
+                "slots, has %lld", 2 * Tmax, (long long)ent->touched_cap);
+  if (rel->acc_touched) {
+    const long long need = model == SKGE_RESCAL ? rel->rows : Tmax;
+    if (need > rel->touched_cap)
+      return fail("triple runner: relation accumulator needs %lld touched slots, has %lld", need,
+                  (long long)rel->touched_cap);
+  }
+  const int nb = batches.size();
+  std::unique_ptr<skge_triple_runner_t> r(new skge_triple_runner_t());
+  r->ws_bytes = skge_triple_step_workspace_bytes(model, (int)Tmax, rel->rows, d);
+  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
+  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
+  r->trip = (int*)r->alloc((size_t)T * (1 + K) * 3 * sizeof(int), false);
+  r->ys = (float*)r->alloc((size_t)T * (1 + K) * sizeof(float), false);
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  if (!r->alloc_ok) return fail("triple runner: device allocation failed");
+  const TripleSet ts = triple_set_view(set, set_capacity);
+  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
+    return fail("triple runner: HolE FFT twiddle table allocation failed");
+  if (!r->begin_capture(st)) return nullptr;
+  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
+                                     rel->rows, ntries, pos3, negK, smp, negs);
+  if (!rc) {
+    const Negatives ng = negatives_of(negs);
+    const int64_t blocks = std::max((int64_t)1, std::min((T * K + 255) / 256, (int64_t)4096));
+    hipLaunchKernelGGL(k_triples_of_epoch_multi, dim3((unsigned)blocks), dim3(256), 0, st, pos3,
+                       negK, (long long)T, (long long)bs, ng, r->trip, r->ys);
+    if (hipGetLastError() != hipSuccess) {
+      set_error("triples launch failed");
+      rc = SKGE_EHIP;
+    }
+  }
+  for (int k = 0; k < nb && !rc; ++k) {
+    const size_t at = (size_t)(1 + K) * batches[k].first;
+    rc = skge_triple_step(stream, model, ent, rel, d, r->trip + 3 * at, r->ys + at,
+                          (1 + K) * (int)batches[k].second, r->ws, r->ws_bytes, loss_total);
+  }
+  if (!rc) rc = skge_epoch_advance(stream, epoch_key);
+  return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 
 extern "C" int skge_triple_runner_run(skge_triple_runner_t* r, void* stream, int nepochs) {

@@ -48,6 +48,14 @@ class SkgeSampler(ctypes.Structure):
 
 S_P = ctypes.POINTER(SkgeSampler)
 
+
+class SkgeNegatives(ctypes.Structure):
+    """Mirror of skge_negatives_t."""
+    _fields_ = [("n", c_i), ("nmodes", c_i), ("modes", c_i * 8), ("rel_range", c_i)]
+
+
+N_P = ctypes.POINTER(SkgeNegatives)
+
 # name -> (restype, argtypes); the exact set declared in include/skge_hip.h
 SIGNATURES = {
     "skge_abi_version": (c_i, []),
@@ -99,6 +107,12 @@ SIGNATURES = {
     "skge_epoch_sample": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p]),
     "skge_epoch_sample_ex": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p,
                                    S_P]),
+    "skge_epoch_sample_multi": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_u64, c_p, c_i, c_p,
+                                      c_p, S_P, N_P]),
+    "skge_pair_runner_create_multi": (c_p, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,
+                                            c_i, c_u64, c_p, c_f, c_i, c_p, S_P, N_P]),
+    "skge_triple_runner_create_multi": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,
+                                              c_i, c_u64, c_p, c_i, c_p, S_P, N_P]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,

@@ -318,6 +318,11 @@ class StochasticTrainer(object):
         # device-resident epochs (PairwiseStochasticTrainer pops its own before
         # this runs: what it set stays)
         self.device_loop = kwargs.pop("device_loop", getattr(self, "device_loop", False))
+        # device_loop only: let the device loops draw Sampler(n, modes) for any
+        # n and modes from {0, 1, 2} (off: anything but (1, [0, 1]) trains on
+        # the per-batch path, as it always has)
+        self.device_negatives = kwargs.pop("device_negatives",
+                                           getattr(self, "device_negatives", False))
         self.seed = kwargs.pop("seed", getattr(self, "seed", 0))
         self.ntries = kwargs.pop("ntries", getattr(self, "ntries", 100))
         self._runner = None
@@ -348,11 +353,13 @@ class StochasticTrainer(object):
                 args = device_sampler_args(self, xs, ys)
                 use_device, ntries, why = args
             if use_device:
-                logistic_device_optim(self, xs, ntries=ntries, sampler=args.kind)
+                logistic_device_optim(self, xs, ntries=ntries, sampler=args.kind,
+                                      negatives=args.negatives)
                 return
             # the device loop draws the negatives of RandomModeSampler,
-            # CorruptedSampler or LCWASampler over (1, [0, 1]) itself;
-            # anything else trains on the per-batch path instead
+            # CorruptedSampler or LCWASampler over (1, [0, 1]) itself -- with
+            # device_negatives=True over any (n, modes), modes from {0, 1, 2},
+            # n * len(modes) <= 64; anything else trains on the per-batch path
             warnings.warn("device_loop: %s; training on the per-batch path" % why)
         self._optim(list(zip(xs, ys)))
 
@@ -414,12 +421,15 @@ class StochasticTrainer(object):
 class PairwiseStochasticTrainer(StochasticTrainer):
     """Stochastic gradient descent trainer with pairwise ranking loss
     (skge/base.py:1320-1427).  Extra kwargs: ``fused`` (default True),
-    ``device_loop`` (device-resident epochs, see module doc), ``device_runner``
+    ``device_loop`` (device-resident epochs, see module doc), ``device_negatives``
+    (with device_loop: n negatives per positive over any modes from {0, 1, 2}
+    drawn on the device; off, only (1, [0, 1]) is), ``device_runner``
     ('auto', 'epoch': TransE's fused runners, 'pairs': the any-model pair
     loop), ``seed`` (device sampler / permutation key), ``ntries``."""
 
     def __init__(self, *args, **kwargs):
         self.device_loop = kwargs.pop("device_loop", False)
+        self.device_negatives = kwargs.pop("device_negatives", False)
         self.device_runner = kwargs.pop("device_runner", "auto")
         self.seed = kwargs.pop("seed", 0)
         self.ntries = kwargs.pop("ntries", 100)
@@ -459,13 +469,15 @@ class PairwiseStochasticTrainer(StochasticTrainer):
             use_device, ntries, why = args
             if not use_device:
                 # the device loop draws the negatives of RandomModeSampler,
-                # CorruptedSampler or LCWASampler over (1, [0, 1]) itself;
-                # anything else trains on the per-batch path instead
+                # CorruptedSampler or LCWASampler over (1, [0, 1]) itself --
+                # with device_negatives=True over any (n, modes), modes from
+                # {0, 1, 2}, n * len(modes) <= 64; anything else trains on the
+                # per-batch path
                 warnings.warn("device_loop: %s; training on the per-batch path" % why)
         self._on_device = use_device
         if use_device:
             from .device import device_optim
-            device_optim(self, xs, ntries=ntries, sampler=args.kind)
+            device_optim(self, xs, ntries=ntries, sampler=args.kind, negatives=args.negatives)
         elif self.samplef is None:
             pidx = np.where(np.array(ys) == 1)[0]
             nidx = np.where(np.array(ys) != 1)[0]

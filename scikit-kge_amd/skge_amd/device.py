@@ -176,8 +176,18 @@ class _Runner(object):
     _pad = False
     graph = None       # dp.DataParallelRunner: the torch graph of its captured epoch
 
-    def _setup(self, model, kg, nbatches, seed, ntries, stream, sampler=L.SKGE_SAMPLER_RANDOM):
+    def _setup(self, model, kg, nbatches, seed, ntries, stream, sampler=L.SKGE_SAMPLER_RANDOM,
+               negatives=None):
         dev = model.device
+        # (n, modes[, rel_range]) of the sampler; anything but (1, [0, 1]) runs
+        # the _multi entry points (include/skge_hip.h, skge_negatives_t)
+        self.n, self.modes, self._neg = 1, [0, 1], None
+        if negatives is not None:
+            self.n, self.modes = int(negatives[0]), [int(m) for m in negatives[1]]
+            if (self.n, self.modes) != (1, [0, 1]):
+                self._neg = negatives_struct(self.n, self.modes, model.sz[2],
+                                             negatives[2] if len(negatives) > 2 else None)
+        self.K = self.n * len(self.modes)
         # the negative sampler's kind (include/skge_hip.h SKGE_SAMPLER_*) and,
         # for the pool kinds, its view of the kg's type index
         self.sampler = int(sampler)
@@ -261,6 +271,16 @@ class _Runner(object):
             except Exception:
                 pass
             self.handle = None
+
+
+def negatives_struct(n, modes, n_rel, rel_range=None):
+    """skge_negatives_t for Sampler(n, modes); rel_range: the TYPED sampler's
+    len(type_index) (None: n_rel, what the other kinds draw a relation from)."""
+    modes = [int(m) for m in modes]
+    if not 1 <= len(modes) <= 8:
+        raise ValueError("modes %r: 1 to 8 entries" % (modes,))
+    return L.SkgeNegatives(int(n), len(modes), (L.c_i * 8)(*modes),
+                           int(n_rel if rel_range is None else rel_range))
 
 
 class _PaddedTables(object):
@@ -580,12 +600,20 @@ class PairLoopRunner(_Runner):
     _who = "pair-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 nviol_total=None, sampler=L.SKGE_SAMPLER_RANDOM):
-        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
+                 nviol_total=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler, negatives)
         self.nviol_total = self._total(nviol_total, torch.int32)
-        P = 2 * max(batch_sizes(kg.T, nbatches))
+        P = self.K * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("pairwise", updaters, slots=model._pair_slots(P))
         self._hold_captured(updaters)
+        if self._neg is not None:
+            # n negatives per positive over any modes: K pairs per positive,
+            # every model on its explicit-pair kernels
+            self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te,
+                         self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
+                         L.ptr(self.nviol_total), self._smp, self._neg,
+                         create="skge_pair_runner_create_multi")
+            return
         self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te, self.tr,
                      model.d, *self._epoch_args(), float(model.margin), self.ntries,
                      L.ptr(self.nviol_total), self._smp, create="skge_pair_runner_create_ex")
@@ -618,13 +646,18 @@ class LogisticLoopRunner(_Runner):
     _who = "logistic-loop runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 loss_total=None, sampler=L.SKGE_SAMPLER_RANDOM):
+                 loss_total=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
         _require_logistic_model(model)
-        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler, negatives)
         self.loss_total = self._total(loss_total, torch.float32)
-        T3 = 3 * max(batch_sizes(kg.T, nbatches))
+        T3 = (1 + self.K) * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("logistic", updaters, slots=model._triple_slots(T3))
         self._hold_captured(updaters)
+        if self._neg is not None:   # (1 + K) triples per positive, explicit-triple kernels
+            self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
+                         *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp,
+                         self._neg, create="skge_triple_runner_create_multi")
+            return
         self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
                      *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp,
                      create="skge_triple_runner_create_ex")
@@ -646,11 +679,13 @@ def _fit_epochs(trainer, runner):
                     break
 
 
-def logistic_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM):
+def logistic_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM,
+                          negatives=None):
     """StochasticTrainer.fit with device_loop=True: per epoch _pre_epoch, one
     graph replay, the runner's error word, then the post_epoch callbacks (which
     read the epoch's loss through trainer.loss as on the per-batch path).
-    sampler: the kind device_sampler_args reported."""
+    sampler: the kind device_sampler_args reported; negatives: its (n, modes,
+    rel_range) (None: (1, [0, 1]))."""
     model = trainer.model
     dev = model.device
     if trainer._loss_dev is None:
@@ -658,7 +693,8 @@ def logistic_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDO
     kg = DeviceKG(xs, dev)
     runner = LogisticLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                                 ntries=trainer.ntries if ntries is None else ntries,
-                                loss_total=trainer._loss_dev, sampler=sampler)
+                                loss_total=trainer._loss_dev, sampler=sampler,
+                                negatives=negatives)
     trainer.batch_size = kg.T // trainer.nbatches
     _fit_epochs(trainer, runner)
 
@@ -681,19 +717,48 @@ def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None,
     return rec, rec_n1
 
 
+def epoch_records_multi(kg, n_ent, n_rel, seed, epoch_key, n, modes, ntries=100, stream=None,
+                        sampler=L.SKGE_SAMPLER_RANDOM, rel_range=None):
+    """The epoch's positives and draws as the _multi device loops make them,
+    for Sampler(n, modes): (pos [T, 3] = (s, o, p), neg [T, K]) on the device,
+    K = n * len(modes), slot k = rep * len(modes) + mi holding the id that
+    replaces position modes[mi] (a relation for mode 2), or -1.  rel_range: the
+    TYPED sampler's len(type_index) (None: n_rel)."""
+    dev = kg.trip.device
+    negs = negatives_struct(n, modes, n_rel, rel_range)
+    K = max(int(n) * len(modes), 1)
+    pos = torch.empty((kg.T, 3), dtype=torch.int32, device=dev)
+    neg = torch.empty((kg.T, K), dtype=torch.int32, device=dev)
+    ek = torch.tensor([int(epoch_key)], dtype=torch.int64, device=dev)
+    L.check(L.lib().skge_epoch_sample_multi(L.stream_ptr(stream), L.ptr(kg.trip), kg.T,
+                                            L.ptr(kg.slots), kg.capacity, int(n_ent), int(n_rel),
+                                            int(seed) & (2 ** 64 - 1), L.ptr(ek), int(ntries),
+                                            L.ptr(pos), L.ptr(neg), kg.sampler(sampler, n_rel),
+                                            negs), "epoch sample (multi)")
+    return pos, neg
+
+
 def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=None,
-                runner="auto", sampler=L.SKGE_SAMPLER_RANDOM):
+                runner="auto", sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
     """runner: 'auto' (TransE -> EpochRunner, the fused sampler/score runners;
     HolE -> HolePipeRunner where it applies, RESCAL -> PairLoopRunner),
     'epoch', 'hole_pipe' or 'pairs'.  sampler: the kind of negatives
     (SKGE_SAMPLER_*); the fused and pipelined runners draw RANDOM only, so the
-    typed and LCWA kinds run the pair loop for every model."""
+    typed and LCWA kinds run the pair loop for every model.  negatives: the
+    sampler's (n, modes, rel_range) (None: (1, [0, 1])); the fused and
+    pipelined runners draw (1, [0, 1]) only, so any other runs the pair loop."""
     from .transe import TransE
     from .base import deterministic
     if sampler != L.SKGE_SAMPLER_RANDOM:
         if runner not in ("auto", "pairs"):
             raise ValueError("device runner %r draws RandomModeSampler negatives only; the typed "
                              "and LCWA samplers need 'pairs' (or 'auto')" % (runner,))
+        runner = "pairs"
+    if negatives is not None and (int(negatives[0]), list(negatives[1])) != (1, [0, 1]):
+        if runner not in ("auto", "pairs"):
+            raise ValueError("device runner %r draws one negative per mode of [0, 1] only; "
+                             "n = %r, modes = %r need 'pairs' (or 'auto')"
+                             % (runner, negatives[0], list(negatives[1])))
         runner = "pairs"
     if runner == "auto":
         runner = "epoch" if isinstance(model, TransE) else \
@@ -706,18 +771,47 @@ def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=N
                            nviol_total=nviol_total)
     if runner == "pairs":
         return PairLoopRunner(model, updaters, kg, nbatches, seed=seed, ntries=ntries,
-                              nviol_total=nviol_total, sampler=sampler)
+                              nviol_total=nviol_total, sampler=sampler, negatives=negatives)
     raise ValueError("unknown device runner %r" % (runner,))
 
 
 class SamplerArgs(tuple):
     """device_sampler_args' result: unpacks as (eligible, ntries, reason), as
-    it always has; ``kind`` is the device sampler's kind (SKGE_SAMPLER_*)."""
+    it always has; ``kind`` is the device sampler's kind (SKGE_SAMPLER_*),
+    ``n`` and ``modes`` the sampler's, ``rel_range`` the range a mode 2 draws
+    its relation from (None: the model's relation count), and ``negatives``
+    the three as the runners take them."""
 
-    def __new__(cls, eligible, ntries, reason, kind=L.SKGE_SAMPLER_RANDOM):
+    def __new__(cls, eligible, ntries, reason, kind=L.SKGE_SAMPLER_RANDOM, n=1, modes=(0, 1),
+                rel_range=None):
         self = super(SamplerArgs, cls).__new__(cls, (eligible, ntries, reason))
-        self.kind = kind
+        self.kind, self.n, self.modes, self.rel_range = kind, n, list(modes), rel_range
         return self
+
+    @property
+    def negatives(self):
+        return (self.n, self.modes, self.rel_range)
+
+
+MAX_SLOTS = 64   # K = n * len(modes) slots per positive (skge_negatives_t)
+
+
+def _negatives_reason(name, n, modes):
+    """Why Sampler(n, modes) is outside what the device loops draw ('': it is
+    inside): n >= 1, 1 to 8 modes from {0, 1, 2}, n * len(modes) <= 64."""
+    try:
+        modes = list(modes)
+        ok = isinstance(n, (int, np.integer)) and n >= 1 and 1 <= len(modes) <= 8 and \
+            all(isinstance(m, (int, np.integer)) and 0 <= m <= 2 for m in modes)
+    except TypeError:
+        ok = False
+    if not ok:
+        return ("%s(n=%r, modes=%r): the device loops draw n >= 1 negatives over 1 to 8 modes "
+                "from {0, 1, 2}" % (name, n, modes))
+    if n * len(modes) > MAX_SLOTS:
+        return ("%s(n=%r, modes=%r): %d negatives per positive, the device loops draw at most %d"
+                % (name, n, modes, n * len(modes), MAX_SLOTS))
+    return ""
 
 
 def _pools_match(index, xs3):
@@ -746,9 +840,13 @@ def device_sampler_args(trainer, xs, ys):
       RandomModeSampler(1, [0, 1], xs, sz)               (kind RANDOM),
       CorruptedSampler(1, xs, type_index(xs), modes=[0, 1])  (kind TYPED) or
       LCWASampler(1, [0, 1], xs, sz)                     (kind LCWA)
-    would (skge/sample.py:28-120, skge/base.py:422-428).  Needed: every y is
-    +1, samplef is such a sampler's own sample method, n == 1 and modes ==
-    [0, 1], sizes equal to the model's, and a sampler that rejects against the
+    would (skge/sample.py:28-120, skge/base.py:422-428) -- or, for a trainer
+    built with device_negatives=True, what the three classes draw with any
+    n >= 1 over 1 to 8 modes from {0, 1, 2} (mode 2 corrupts the relation),
+    n * len(modes) <= 64, reported as the result's ``n``, ``modes`` and
+    ``rel_range``.  Needed: every y is +1, samplef is such a sampler's own
+    sample method, n == 1 and modes == [0, 1] (without device_negatives),
+    sizes equal to the model's, and a sampler that rejects against the
     same training triples the device loop does (its xs == the fit's xs); the
     typed sampler's type_index must be the one of xs and the LCWA sampler's
     counts those of xs.  samplef None is the reference's labelled-negatives
@@ -775,11 +873,19 @@ def device_sampler_args(trainer, xs, ys):
             LCWASampler: L.SKGE_SAMPLER_LCWA}[cls]
     if type(smp)._sample is not cls._sample:
         return SamplerArgs(False, trainer.ntries, "%s._sample is overridden" % name)
-    if smp.n != 1 or list(smp.modes) != [0, 1]:
-        return SamplerArgs(False, trainer.ntries, "%s(n=%r, modes=%r) is not (1, [0, 1])" % (
-            name, smp.n, smp.modes))
-    n_ent = trainer.model.E.rows
-    if cls is not CorruptedSampler and tuple(smp.sz[:2]) != (n_ent, n_ent):
+    if not getattr(trainer, "device_negatives", False):
+        # as it always was: one negative per mode of [0, 1], or the per-batch path
+        if smp.n != 1 or list(smp.modes) != [0, 1]:
+            return SamplerArgs(False, trainer.ntries, "%s(n=%r, modes=%r) is not (1, [0, 1]) "
+                               "(device_negatives=True draws n negatives over modes from "
+                               "{0, 1, 2} on the device)" % (name, smp.n, smp.modes))
+    why = _negatives_reason(name, smp.n, smp.modes)
+    if why:
+        return SamplerArgs(False, trainer.ntries, why)
+    n, modes = int(smp.n), [int(m) for m in smp.modes]
+    n_ent, n_rel = trainer.model.E.rows, int(trainer.model.sz[2])
+    if cls is not CorruptedSampler and (
+            tuple(smp.sz[:2]) != (n_ent, n_ent) or (2 in modes and smp.sz[2] != n_rel)):
         return SamplerArgs(False, trainer.ntries,
                            "sampler sizes %r differ from the model's" % (smp.sz,))
     xs3 = np.asarray(xs, dtype=np.int64).reshape(-1, 3).tolist()
@@ -796,12 +902,16 @@ def device_sampler_args(trainer, xs, ys):
             set((s, p) for s, _, p in fit_set):
         return SamplerArgs(False, trainer.ntries,
                            "LCWASampler.counts differ from the fit's triples' (s, p) counts")
-    return SamplerArgs(True, smp.ntries, "", kind)
+    # a typed mode 2 draws randint(len(type_index)) as a relation id
+    # (skge/sample.py:80); type_index is the one of xs, so it is <= n_rel
+    rel_range = len(smp.type_index) if cls is CorruptedSampler and 2 in modes else None
+    return SamplerArgs(True, smp.ntries, "", kind, n, modes, rel_range)
 
 
-def device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM):
+def device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
     """PairwiseStochasticTrainer.fit with device_loop=True (sampler: the kind
-    device_sampler_args reported).  The runner's
+    device_sampler_args reported; negatives: its (n, modes, rel_range), None:
+    (1, [0, 1])).  The runner's
     error word (packed-sum overflow, cross-workgroup wait timeout) is read
     after every epoch, before the post_epoch callbacks, so no callback ever
     sees parameters from a failed epoch."""
@@ -818,5 +928,6 @@ def device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM):
         which = "pairs"
     runner = make_runner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
                          ntries=trainer.ntries if ntries is None else ntries,
-                         nviol_total=trainer._nviol_dev, runner=which, sampler=sampler)
+                         nviol_total=trainer._nviol_dev, runner=which, sampler=sampler,
+                         negatives=negatives)
     _fit_epochs(trainer, runner)
