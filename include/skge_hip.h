@@ -249,6 +249,23 @@ int skge_triple_step(void *stream, int model, const skge_table_t *ent, const skg
                      int d, const int *trip, const float *ys, int T, void *workspace,
                      size_t ws_bytes, float *loss);
 
+/*
+ * Which kernels skge_pair_step (logistic == 0, n_items = P) or
+ * skge_triple_step (logistic != 0, n_items = T) runs for a model of width d
+ * with n_rel relations: SKGE_PATH_* | KM << 8, KM the registers per lane that
+ * hold a row (1, 2, 3, 4, 8 or 16).  A query only -- nothing is launched --
+ * answered by the predicates the launchers themselves branch on, so a test can
+ * pin the path a shape is meant to reach.  SKGE_EINVAL for an unknown model, a
+ * logistic TransE, or d outside 1..1024.
+ */
+#define SKGE_PATH_GENERIC 0            /* k_pair_grad / k_triple_grad */
+#define SKGE_PATH_HOLE_FAST 1          /* register-tiled correlations */
+#define SKGE_PATH_HOLE_FFT 2           /* wave FFT correlations */
+#define SKGE_PATH_RESCAL_MFMA_SMALL 3  /* MFMA GEMMs, one-workgroup bucketing */
+#define SKGE_PATH_RESCAL_MFMA_SORT 4   /* MFMA GEMMs, count / scan / scatter bucketing */
+#define SKGE_PATH_RESCAL_VALU 5        /* per-pair GEMVs + k_rescal_wgrad */
+int skge_step_path(int model, int logistic, int d, int n_rel, int n_items);
+
 /* ---------------- device-resident batch loop (throughput path) ---------------- */
 
 /*

@@ -104,7 +104,7 @@ __device__ __forceinline__ void cconv_lds(const float* sa, const float* sb, int 
 // cconv(a, b) = ccorr(a', b) with a'_m = a_{(-m) mod d} (stored reversed).
 // The quad result goes through a wave-private LDS row back to the lane-
 // strided layout of the rest of the kernel.
-__device__ __forceinline__ bool hole_fast(int d) { return (d & 3) == 0 && d >= 4 && d <= 256; }
+__host__ __device__ __forceinline__ bool hole_fast(int d) { return (d & 3) == 0 && d >= 4 && d <= 256; }
 // wave-private LDS floats of the fast HolE pair kernel: four a operands
 // (d + 4), four doubled rows (2d + 4), the output row
 __host__ __device__ __forceinline__ int hole_fast_lds_floats(int d) { return 13 * d + 32; }
@@ -796,6 +796,17 @@ bool hole_use_fft(int d) {
   return hole_fft_ok(d) && !(e && atoi(e));
 }
 
+// the kernels of a per-batch HolE step (skge_step_path's SKGE_PATH_*; what
+// launch_pair branches on): the register-tiled correlations where hole_fast(d)
+// holds (km <= 4 there), the wave FFT where that applies too -- the pair form
+// only when it records (a score-only call keeps the fast kernel) -- else the
+// direct correlations of k_pair_grad / k_triple_grad
+int hole_step_path(int d, bool logistic_mode, bool record) {
+  if (!(km_for(d) <= 4 && hole_fast(d))) return SKGE_PATH_GENERIC;
+  if (hole_use_fft(d) && (logistic_mode || record)) return SKGE_PATH_HOLE_FFT;
+  return SKGE_PATH_HOLE_FAST;
+}
+
 bool hole_pos_ok(int af, const skge_table_t* ent, const skge_table_t* rel, int d) {
   return af >= 0 && af <= 3 && d % 4 == 0 && d >= 4 && d <= 256 && ent && rel &&
          ent->width == d && rel->width == d &&
@@ -1354,9 +1365,11 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
   if (blocks > 8192) blocks = 8192;
   if (blocks < 1) blocks = 1;
   size_t lds = (MODEL == TRANSE_L1 || MODEL == TRANSE_L2) ? 0 : (size_t)4 * 6 * 64 * km * 4;
-  const bool hfast = MODEL == HOLE && km <= 4 && (a.d & 3) == 0 && a.d >= 4 && a.d <= 256;
+  const int path = MODEL == HOLE ? hole_step_path(a.d, logistic_mode, a.record != 0)
+                                 : SKGE_PATH_GENERIC;
+  const bool hfast = path != SKGE_PATH_GENERIC;
   if (hfast) lds = std::max(lds, (size_t)4 * hole_fast_lds_floats(a.d) * 4);
-  if (hfast && logistic_mode && hole_use_fft(a.d)) {
+  if (path == SKGE_PATH_HOLE_FFT && logistic_mode) {
     PairArgs af = a;
     af.tw = hole_fft_table(a.d);
     SKGE_CHECK_ARG(af.tw != nullptr, "HolE FFT twiddle table allocation failed");
@@ -1370,7 +1383,7 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
     SKGE_CHECK_LAUNCH("hole fft triple launch");
     return SKGE_OK;
   }
-  if (hfast && !logistic_mode && hole_use_fft(a.d) && a.record) {
+  if (path == SKGE_PATH_HOLE_FFT) {
     PairArgs af = a;
     af.tw = hole_fft_table(a.d);
     SKGE_CHECK_ARG(af.tw != nullptr, "HolE FFT twiddle table allocation failed");
@@ -1384,7 +1397,7 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
     SKGE_CHECK_LAUNCH("hole fft pair launch");
     return SKGE_OK;
   }
-  if (hfast && !logistic_mode) {
+  if (hfast && !logistic_mode) {   // (logistic: k_triple_grad's own fast branch, below)
     switch (km) {
       case 1: hipLaunchKernelGGL((k_hole_pair_fast<1>), dim3(blocks), dim3(threads), lds, st, a); break;
       case 2: hipLaunchKernelGGL((k_hole_pair_fast<2>), dim3(blocks), dim3(threads), lds, st, a); break;

@@ -173,6 +173,9 @@ bool hole_pos_ok(int af, const skge_table_t* ent, const skge_table_t* rel, int d
 // the per-positive HolE kernels run their correlations through the wave FFT
 // (skge_hole_fft.h) for this d (unless SKGE_HOLE_DIRECT=1)
 bool hole_use_fft(int d);
+// the kernels launch_pair runs for a HolE batch of width d (SKGE_PATH_GENERIC /
+// _HOLE_FAST / _HOLE_FFT; record: the call scatters contributions)
+int hole_step_path(int d, bool logistic_mode, bool record);
 int launch_hole_pos(hipStream_t st, int af, const skge_table_t* ent, const skge_table_t* rel,
                     int d, const int4* rec, const int* rec_n1, long long start, int count,
                     float margin, int* nviol, int* fold, int* total);
@@ -211,6 +214,9 @@ int rescal_w_sync(hipStream_t st, const WStep& w);
 
 // skge_rescal.hip / skge_update.hip: the device pair loop's RESCAL batch
 bool rescal_pair_mfma_selected(int d, int M);
+// rescal_front buckets n triples over M relations in one workgroup
+// (k_rs_bucket_small) rather than by count / scan / scatter (skge_rescal.hip)
+bool rs_small_bucket(int M, int n);
 // the device pair loop's RESCAL buckets for a whole epoch (skge_rescal.hip)
 bool rescal_epoch_ok(int M);
 size_t rescal_epoch_ws_bytes(int bs, int nb, int M, int d);

@@ -2089,6 +2089,8 @@ bool skge_rescal_mfma_ok(int d, int M) {
   return d >= 1 && d <= RS_MAX_D && M >= 1 && M <= RS_MAX_M;
 }
 
+bool rs_small_bucket(int M, int n) { return M <= SB_MAXM && n <= SB_MAXN; }
+
 // bucket the n = na + nb triples (list a, then list b) by relation and run the
 // two GEMMs (WE^T, EW, partial scores)
 static int rescal_front(hipStream_t st, const skge_table_t* ent, const skge_table_t* rel, int d,
@@ -2097,7 +2099,7 @@ static int rescal_front(hipStream_t st, const skge_table_t* ent, const skge_tabl
   const int M = rel->rows;
   if (bucketed) {
     // the epoch's buckets were built up front (rescal_epoch_bucket)
-  } else if (M <= SB_MAXM && n <= SB_MAXN) {
+  } else if (rs_small_bucket(M, n)) {
     hipLaunchKernelGGL(k_rs_bucket_small, dim3(1), dim3(1024), 0, st, a, b, na, n, M, ws);
   } else {
     const int nchunks = (n + 63) / 64;

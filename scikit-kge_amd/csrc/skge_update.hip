@@ -1081,6 +1081,26 @@ int skge_rescal_pair_grad_mfma(hipStream_t st, int af, const skge_table_t* ent,
 static bool rescal_use_mfma(int d, int M) { return skge_rescal_mfma_ok(d, M); }
 bool rescal_pair_mfma_selected(int d, int M) { return rescal_use_mfma(d, M); }
 
+extern "C" int skge_step_path(int model, int logistic, int d, int n_rel, int n_items) {
+  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_ARG(!logistic || model == SKGE_HOLE || model == SKGE_RESCAL,
+                 "logistic loss is defined for HolE and RESCAL only");
+  const int km = d > 0 ? km_for(d) : 0;
+  SKGE_CHECK_ARG(km != 0, "d=%d unsupported (1..1024)", d);
+  SKGE_CHECK_ARG(n_rel >= 1 && n_items >= 0, "n_rel %d / n_items %d", n_rel, n_items);
+  int path = SKGE_PATH_GENERIC;
+  if (model == SKGE_HOLE) {
+    path = hole_step_path(d, logistic != 0, true);   // a step always records
+  } else if (model == SKGE_RESCAL) {
+    // rescal_front's n: the positives and the negatives of a pair step
+    const int n = (int)std::min<long long>(logistic ? n_items : 2ll * n_items, 1ll << 30);
+    path = !rescal_use_mfma(d, n_rel)    ? SKGE_PATH_RESCAL_VALU
+           : rs_small_bucket(n_rel, n)   ? SKGE_PATH_RESCAL_MFMA_SMALL
+                                         : SKGE_PATH_RESCAL_MFMA_SORT;
+  }
+  return path | (km << 8);
+}
+
 extern "C" int skge_device_error(void* stream, int reset) {
   int v = 0;
   hipStream_t st = as_stream(stream);

@@ -20,6 +20,9 @@ SKGE_SGD, SKGE_ADAGRAD = 0, 1
 SKGE_POST_NONE, SKGE_POST_NORMALIZE, SKGE_POST_NORMLESS1 = 0, 1, 2
 SKGE_ACC_F32, SKGE_ACC_I16X4, SKGE_ACC_I32X2, SKGE_ACC_FX64, SKGE_ACC_I8X4 = 0, 1, 2, 3, 4
 SKGE_SAMPLER_RANDOM, SKGE_SAMPLER_TYPED, SKGE_SAMPLER_LCWA = 0, 1, 2
+# skge_step_path: path | KM << 8
+(SKGE_PATH_GENERIC, SKGE_PATH_HOLE_FAST, SKGE_PATH_HOLE_FFT, SKGE_PATH_RESCAL_MFMA_SMALL,
+ SKGE_PATH_RESCAL_MFMA_SORT, SKGE_PATH_RESCAL_VALU) = range(6)
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -89,6 +92,7 @@ SIGNATURES = {
     "skge_triple_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "skge_pair_step": (c_i, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_f, c_p, c_sz, c_p]),
+    "skge_step_path": (c_i, [c_i, c_i, c_i, c_i, c_i]),
     "skge_triple_set_build": (c_i, [c_p, c_p, c_i64, c_p, c_i64]),
     "skge_transe_sample_grad": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i64, c_i,
                                       c_u64, c_p, c_f, c_i, c_p, c_p, c_p]),

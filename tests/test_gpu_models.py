@@ -1,7 +1,8 @@
 """Fused explicit-pair steps of every model on random batches at sizes the
 golden fixtures do not reach (many relations, ragged d, duplicate rows), vs
-the oracle; RESCAL runs on the relation-grouped fp32 MFMA path for d <= 480
-(skge_rescal.hip).  Tolerances 1e-5 + 1e-5|x| plus, for the AdaGrad steps,
+the oracle; RESCAL runs on the relation-grouped fp32 MFMA path (skge_rescal.hip:
+d <= 1024 and at most 8192 relations; the wider rows, the other bucketing
+branches and the per-pair fallback are in test_gpu_widths.py).  Tolerances 1e-5 + 1e-5|x| plus, for the AdaGrad steps,
 the fp32 gradient rounding propagated through the step and the projection
 (tests/parity_util.py check_step); violation counts exact."""
 import numpy as np
@@ -27,7 +28,7 @@ def _batch(rs, n_ent, n_rel, P, diff_rel=0.1):
     return pos, neg
 
 
-def _model(name, n_ent, n_rel, d, seed=3, rparam=0.0):
+def _model(name, n_ent, n_rel, d, seed=3, rparam=0.0, margin=None, l1=True, opt="adagrad"):
     import skge_amd as S
     np.random.seed(seed)
     sz = (n_ent, n_ent, n_rel)
@@ -38,40 +39,51 @@ def _model(name, n_ent, n_rel, d, seed=3, rparam=0.0):
         m = S.HolE(sz, d, rparam=rparam)
         m.add_hyperparam("margin", 0.2)
     else:
-        m = S.TransE(sz, d)
+        m = S.TransE(sz, d, l1=l1)
         m.add_hyperparam("margin", 2.0)
-    upd = {pid: S.AdaGrad(p, 0.1) for pid, p in m.params.items()}
+    if margin is not None:
+        m.add_hyperparam("margin", margin)
+    U = S.AdaGrad if opt == "adagrad" else S.SGD
+    upd = {pid: U(p, 0.1) for pid, p in m.params.items()}
     return m, upd
 
 
-def _run(name, n_ent, n_rel, d, P, nb, rparam=0.0, seed=5):
+def _state(m, upd, opt):
+    """The updaters' state as the oracle takes it (SGD: none, zeros unused)."""
+    if opt == "adagrad":
+        return {pid: upd[pid].p2.detach().cpu().numpy().astype(np.float64) for pid in m.params}
+    return {pid: np.zeros(tuple(p.data.shape)) for pid, p in m.params.items()}
+
+
+def _run(name, n_ent, n_rel, d, P, nb, rparam=0.0, seed=5, margin=None, l1=True, opt="adagrad"):
     """nb steps; each step is compared with one oracle step taken from the
     device's own state before it (AdaGrad's first step moves an element by
     lr*sign(g), so an element whose gradient is ~0 at fp32 rounding level
     may legitimately land on either side; chaining oracle steps across
     batches would compound such an element into unrelated later errors)."""
-    m, upd = _model(name, n_ent, n_rel, d, rparam=rparam)
+    m, upd = _model(name, n_ent, n_rel, d, rparam=rparam, margin=margin, l1=l1, opt=opt)
     rs = np.random.RandomState(seed)
     nviol = torch.zeros(1, dtype=torch.int32, device=m.device)
     for b in range(nb):
         params = {pid: p.data.detach().cpu().numpy().astype(np.float64)
                   for pid, p in m.params.items()}
-        state = {pid: upd[pid].p2.detach().cpu().numpy().astype(np.float64) for pid in m.params}
+        state = _state(m, upd, opt)
         pos, neg = _batch(rs, n_ent, n_rel, P)
         nviol.zero_()
         m._pairwise_step(torch.as_tensor(pos, device=m.device), torch.as_tensor(neg, device=m.device),
                          upd, nviol)
-        kw = {"rparam": rparam} if name != "transe" else {"l1": True}
+        kw = {"rparam": rparam} if name != "transe" else {"l1": l1}
         before = {k: v.copy() for k, v in params.items()}
         _, _, nv, grads = O.pairwise_step(name, params, state, pos, neg, 0.1, float(m.margin),
-                                          "adagrad", **kw)
+                                          opt, **kw)
         assert int(nviol.item()) == nv, (name, b)
         for pid in m.params:
             parity_util.check_step(m.params[pid].data, params[pid], before[pid],
                                    grads[pid] if grads else None, state[pid], 0.1,
                                    "%s b%d %s" % (name, b, pid),
-                                   post=parity_util.POSTS[name].get(pid))
-            close(upd[pid].p2, state[pid], "%s b%d p2 %s" % (name, b, pid))
+                                   post=parity_util.POSTS[name].get(pid), opt=opt)
+            if opt == "adagrad":
+                close(upd[pid].p2, state[pid], "%s b%d p2 %s" % (name, b, pid))
     return m
 
 
@@ -102,30 +114,45 @@ def test_hole_step_vs_oracle(n_ent, n_rel, d, P):
     _run("hole", n_ent, n_rel, d, P, nb=2)
 
 
-def _run_logistic(name, n_ent, n_rel, d, B, nb, rparam=0.0, seed=9):
+def _run_logistic(name, n_ent, n_rel, d, B, nb, rparam=0.0, seed=9, opt="adagrad",
+                  projected_by_step=False):
     """StochasticTrainer-style steps (B positives y=+1 and their two sampler
     corruptions y=-1, skge/base.py:1293-1304) vs one oracle logistic step from
-    the device's state before each."""
-    m, upd = _model(name, n_ent, n_rel, d, rparam=rparam)
+    the device's state before each.  projected_by_step: a projected table
+    (HolE's E, normless1) is held to parity_util.check_step, the bar of the
+    pairwise _run, which carries an element's allowance through the row's
+    projection scale; close_adagrad allows the element alone."""
+    m, upd = _model(name, n_ent, n_rel, d, rparam=rparam, opt=opt)
     rs = np.random.RandomState(seed)
     loss = torch.zeros(1, dtype=torch.float32, device=m.device)
     for b in range(nb):
         params = {pid: p.data.detach().cpu().numpy().astype(np.float64)
                   for pid, p in m.params.items()}
-        state = {pid: upd[pid].p2.detach().cpu().numpy().astype(np.float64) for pid in m.params}
+        state = _state(m, upd, opt)
         pos, neg = _batch(rs, n_ent, n_rel, B, diff_rel=0.0)
         trip = np.concatenate([pos, neg]).astype(np.int32)
         ys = np.concatenate([np.ones(B), -np.ones(B)]).astype(np.float32)
         loss.zero_()
         m._logistic_step(torch.as_tensor(trip, device=m.device),
                          torch.as_tensor(ys, device=m.device), upd, loss)
-        _, want_loss, _ = O.logistic_step(name, params, state, trip, ys.astype(np.float64), 0.1,
-                                          "adagrad", rparam=rparam)
+        before = {k: v.copy() for k, v in params.items()}
+        _, want_loss, grads = O.logistic_step(name, params, state, trip, ys.astype(np.float64),
+                                              0.1, opt, rparam=rparam)
         np.testing.assert_allclose(float(loss.item()), want_loss, rtol=1e-5)
         for pid in m.params:
-            close_adagrad(m.params[pid].data, params[pid], state[pid], 0.1,
-                          "%s logistic b%d %s" % (name, b, pid))
+            if opt != "adagrad":
+                close(m.params[pid].data, params[pid], "%s logistic b%d %s" % (name, b, pid))
+                continue
+            post = parity_util.POSTS[name].get(pid)
+            if projected_by_step and post is not None:
+                parity_util.check_step(m.params[pid].data, params[pid], before[pid], grads[pid],
+                                       state[pid], 0.1, "%s logistic b%d %s" % (name, b, pid),
+                                       post=post)
+            else:
+                close_adagrad(m.params[pid].data, params[pid], state[pid], 0.1,
+                              "%s logistic b%d %s" % (name, b, pid))
             close(upd[pid].p2, state[pid], "%s logistic b%d p2 %s" % (name, b, pid))
+    return m
 
 
 @pytest.mark.parametrize("n_ent,n_rel,d,B", [(300, 7, 40, 300), (400, 18, 200, 350)])

@@ -20,7 +20,7 @@ def header_functions():
 def test_header_declares_expected_entry_points():
     fns = header_functions()
     for f in ["skge_pair_grad", "skge_triple_grad", "skge_rescal_wgrad", "skge_accum_collect",
-              "skge_update_rows", "skge_accum_apply", "skge_pair_step",
+              "skge_update_rows", "skge_accum_apply", "skge_pair_step", "skge_step_path",
               "skge_transe_sample_grad", "skge_runner_create"]:
         assert f in fns
 
@@ -52,3 +52,16 @@ def test_errors_are_reported_without_a_gpu():
     t = L.SkgeTable()
     rc = lib.skge_update_rows(None, ctypes.byref(t), None, None, 0)
     assert rc == -1
+
+
+def test_step_path_answers_without_a_gpu():
+    """skge_step_path is a pure query: path | KM << 8 (tests/width_cases.py
+    holds the whole table against it), SKGE_EINVAL outside the supported shapes."""
+    from skge_amd import _lib as L
+    lib = L.load()
+    assert lib.skge_step_path(L.SKGE_TRANSE_L1, 0, 200, 18, 100) == L.SKGE_PATH_GENERIC | 4 << 8
+    assert lib.skge_step_path(L.SKGE_HOLE, 1, 200, 18, 100) == L.SKGE_PATH_HOLE_FFT | 4 << 8
+    assert lib.skge_step_path(L.SKGE_RESCAL, 0, 8, 8193, 100) == L.SKGE_PATH_RESCAL_VALU | 1 << 8
+    for bad in ((L.SKGE_TRANSE_L1, 1, 8, 3, 10), (L.SKGE_HOLE, 0, 1025, 3, 10),
+                (L.SKGE_HOLE, 0, 0, 3, 10), (7, 0, 8, 3, 10)):
+        assert lib.skge_step_path(*bad) == -1, bad
