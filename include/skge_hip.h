@@ -832,6 +832,52 @@ int skge_neighbours(void *stream, const float *T, int N, int d, const float *Q, 
                     int nq, int metric, int k, void *workspace, size_t ws_bytes, int *ids_out,
                     float *sim_out);
 
+/* ---------------- relation prediction ---------------- */
+
+/*
+ * The relation slot of the triple: every relation j of 0 .. M - 1 scored for a
+ * pair (s, o),
+ *   TransE  -sum_k |E_s[k] + R_j[k] - E_o[k]|, evaluated as -sum|q - R_j| with
+ *           q = E_o - E_s (one fp32 subtract per component), the sequential
+ *           chain of the ranking entry points above on row R_j;
+ *   HolE    R_j . q, q = ccorr(E_s, E_o) (the chain of the ranking entry
+ *           points' correlation), the same dot chain on row R_j;
+ *   RESCAL  sum_a sum_b E_s[a] W_j[a][b] E_o[b]: t_b = the fp32 fma chain over
+ *           a = 0 .. d - 1 from 0.0f (what v_mfma_f32_32x32x2_f32 accumulates),
+ *           then sum_b t_b E_o[b] in a fixed order (no float atomics: the same
+ *           bits on every run).  The true relation's score comes out of the
+ *           same code as every other's.
+ * E [N][d], R [M][d] (W [M][d][d] for RESCAL), d <= 1024, M >= 1.  Ids inside
+ * device arrays are not range-checked here.
+ *
+ * skge_relrank: for test triple i = (s, o, p) of queries[nq][3],
+ * ranks_out[2i] = 1 + #{relations scoring strictly above p} (ties in p's
+ * favour) and ranks_out[2i + 1] = that rank - #{known relations of the pair
+ * scoring strictly above p}: known_rel[known_off[i] .. known_off[i + 1]) holds
+ * every p' != p with (s, o, p') known (int32, ascending, unique);
+ * known_off NULL = no filter (both columns equal).  Both TransE codes are
+ * scored with the L1 distance, as skge_rank / skge_rank_known do.
+ *
+ * skge_reltopk: for pair i = (s, o) of pairs[nq][2] the k best relations into
+ * rel_out / score_out [nq][k], in skge_topk's order (descending score, then
+ * ascending id among exactly equal fp32 scores), padding (-1, -inf; k > M is
+ * legal) and exclusion lists (excl_off [nq + 1] / excl_rel, relation ids).
+ * SKGE_TRANSE_L2 scores -sum (q - R_j)^2 here, as in skge_topk.  1 <= k <= 128.
+ *
+ * Caller-owned buffers, stream-ordered; nq == 0 launches nothing.  RESCAL's
+ * score matrix [nq][M] lives in the workspace and is filled a block of queries
+ * at a time when it would pass 256 MB; the workspace functions return what the
+ * entry points need for the given model.
+ */
+size_t skge_relrank_workspace_bytes(int nq, int d, int M, int model);
+int skge_relrank(void *stream, int model, const float *E, const float *R, int N, int M, int d,
+                 const int *queries, int nq, const int *known_off, const int *known_rel,
+                 void *workspace, size_t ws_bytes, int *ranks_out);
+size_t skge_reltopk_workspace_bytes(int nq, int d, int k, int M, int model);
+int skge_reltopk(void *stream, int model, const float *E, const float *R, int N, int M, int d,
+                 const int *pairs, int nq, int k, const int *excl_off, const int *excl_rel,
+                 void *workspace, size_t ws_bytes, int *rel_out, float *score_out);
+
 #ifdef __cplusplus
 }
 #endif

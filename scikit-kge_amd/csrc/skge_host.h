@@ -137,6 +137,18 @@ void launch_rank_query(hipStream_t st, int model, const float* E, const float* R
 void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d, const float* Q,
                        const float* tgt, int nv, int* raw);
 
+// skge_topk.hip: the top-k selection and merge, for callers that select rows
+// of another table (skge_relation.hip).  For query vectors Q [nq][d] the k best
+// rows of T [rows][d] into ent_out / score_out [nq][k] in skge_topk's order
+// and padding; model picks the score's form as skge_topk does (TRANSE_L1:
+// -sum|q - T_j|, TRANSE_L2: -sum (q - T_j)^2, else the dot product); excl_*:
+// skge_topk's exclusion CSR over row ids.  lists: topk_lists_bytes(nq, k,
+// rows) bytes of workspace.
+size_t topk_lists_bytes(int nq, int k, int rows);
+void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int d, const float* Q,
+                        int nq, int k, const int* excl_off, const int* excl_ent, void* lists,
+                        int* ent_out, float* score_out);
+
 // skge_pipeline.hip: draw every negative of the epoch whose key is *epoch_key
 // (rec[j] = (s, o, p, s' or -1), rec_n1[j] = o' or -1 for positive j of the
 // epoch's order) with the sampler smp (nullptr: RANDOM, k_epoch_sample as the

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "skge_host.h"
+#include "skge_stage.h"
 #include "skge_topk_list.h"
 
 namespace skge {
@@ -64,28 +65,6 @@ __global__ __launch_bounds__(256) void k_nb_norms(const float* __restrict__ X, i
     for (int kk = 0; kk < d; ++kk) n2 = fmaf(x[kk], x[kk], n2);
   }
   r[j] = n2 == 0.0f ? 0.0f : 1.0f / sqrtf(n2);
-}
-
-// four dims kk .. kk + 3 of a row, zeros past d and for a row past the end
-// (ok false; row is then any readable row).  Every load is issued, from a
-// clamped address, and masked afterwards: a branch around a load would make
-// the loads wait for one another.  VEC: d % 4 == 0, one 16-byte load.
-template <bool VEC>
-__device__ __forceinline__ float4 nb_load4(const float* row, bool ok, int kk, int d) {
-  float4 x;
-  if (VEC) {
-    x = *reinterpret_cast<const float4*>(row + (kk < d ? kk : 0));
-  } else {
-    x.x = row[kk < d ? kk : 0];
-    x.y = row[kk + 1 < d ? kk + 1 : 0];
-    x.z = row[kk + 2 < d ? kk + 2 : 0];
-    x.w = row[kk + 3 < d ? kk + 3 : 0];
-  }
-  x.x = ok && kk < d ? x.x : 0.0f;
-  x.y = ok && kk + 1 < d ? x.y : 0.0f;
-  x.z = ok && kk + 2 < d ? x.z : 0.0f;
-  x.w = ok && kk + 3 < d ? x.w : 0.0f;
-  return x;
 }
 
 // ---- selection: QB queries x one table slice per workgroup ----
@@ -161,11 +140,11 @@ __global__ __launch_bounds__(256, 2) void k_nb_select(NbArgs a) {
       auto load = [&](auto v4) {
         constexpr bool VEC = decltype(v4)::value;
 #pragma unroll
-        for (int u = 0; u < QB / 32; ++u) qa[u] = nb_load4<VEC>(qrow[u], qok[u], k0 + st_k, d);
+        for (int u = 0; u < QB / 32; ++u) qa[u] = stage_load4<VEC>(qrow[u], qok[u], k0 + st_k, d);
 #pragma unroll
         for (int u = 0; u < NB_TB / 32; ++u) {
           const int j = t0 + st_r + 32 * u;
-          ta[u] = nb_load4<VEC>(a.T + (size_t)(j < tend ? j : tbeg) * d, j < tend, k0 + st_k, d);
+          ta[u] = stage_load4<VEC>(a.T + (size_t)(j < tend ? j : tbeg) * d, j < tend, k0 + st_k, d);
         }
       };
       if (vec)

@@ -302,14 +302,47 @@ static void launch_select(hipStream_t st, const TopkPlan& p, const TopkArgs& a) 
     hipLaunchKernelGGL((k_topk_select<FORM, 32, TK_KMAX>), dim3(p.qb, p.ns), dim3(256), 0, st, a);
 }
 
+// the selection and the merge over any table T [rows][d] for query vectors
+// Q [nq][d] (skge_host.h): model picks the score's form as skge_topk does
+size_t topk_lists_bytes(int nq, int k, int rows) {
+  const TopkPlan p = topk_plan(nq, k, rows);
+  return (size_t)nq * p.ns * k * sizeof(tkey_t);
+}
+void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int d, const float* Q,
+                        int nq, int k, const int* excl_off, const int* excl_ent, void* lists,
+                        int* ent_out, float* score_out) {
+  const TopkPlan p = topk_plan(nq, k, rows);
+  TopkArgs a = {};
+  a.E = T;
+  a.N = rows;
+  a.d = d;
+  a.model = model;
+  a.nq = nq;
+  a.k = k;
+  a.excl_off = excl_off;
+  a.excl_ent = excl_ent;
+  a.Q = const_cast<float*>(Q);
+  a.lists = (tkey_t*)lists;
+  a.eslice = p.eslice;
+  a.ns = p.ns;
+  a.ent_out = ent_out;
+  a.score_out = score_out;
+  if (model == SKGE_TRANSE_L1)
+    launch_select<TK_L1>(st, p, a);
+  else if (model == SKGE_TRANSE_L2)
+    launch_select<TK_L2SQ>(st, p, a);
+  else
+    launch_select<TK_DOT>(st, p, a);
+  hipLaunchKernelGGL(k_topk_merge, dim3((nq + 3) / 4), dim3(256), 0, st, a);
+}
+
 }  // namespace skge
 
 using namespace skge;
 
 extern "C" size_t skge_topk_workspace_bytes(int nq, int d, int k, int N) {
   if (nq <= 0 || d <= 0 || k < 1 || k > TK_KMAX || N <= 0) return 0;
-  const TopkPlan p = topk_plan(nq, k, N);
-  return topk_q_bytes(nq, d) + (size_t)nq * p.ns * k * sizeof(tkey_t) + 256;
+  return topk_q_bytes(nq, d) + topk_lists_bytes(nq, k, N) + 256;
 }
 
 extern "C" int skge_topk(void* stream, int model, const float* E, const float* R, int N, int d,
@@ -325,35 +358,20 @@ extern "C" int skge_topk(void* stream, int model, const float* E, const float* R
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_topk_workspace_bytes(nq, d, k, N),
                  "top-k workspace needs %zu bytes", skge_topk_workspace_bytes(nq, d, k, N));
-  const TopkPlan p = topk_plan(nq, k, N);
   TopkArgs a = {};
   a.E = E;
   a.R = R;
-  a.N = N;
   a.d = d;
   a.model = model;
   a.nq = nq;
   a.direction = direction;
-  a.k = k;
   a.queries = queries;
-  a.excl_off = excl_off;
-  a.excl_ent = excl_ent;
   a.Q = (float*)workspace;
-  a.lists = (tkey_t*)((char*)workspace + topk_q_bytes(nq, d));
-  a.eslice = p.eslice;
-  a.ns = p.ns;
-  a.ent_out = ent_out;
-  a.score_out = score_out;
   hipStream_t st = as_stream(stream);
   const int qblocks = std::max(1, std::min((nq + 1) / 2, 16384));
   hipLaunchKernelGGL(k_topk_query, dim3(qblocks), dim3(128), 0, st, a);
-  if (model == SKGE_TRANSE_L1)
-    launch_select<TK_L1>(st, p, a);
-  else if (model == SKGE_TRANSE_L2)
-    launch_select<TK_L2SQ>(st, p, a);
-  else
-    launch_select<TK_DOT>(st, p, a);
-  hipLaunchKernelGGL(k_topk_merge, dim3((nq + 3) / 4), dim3(256), 0, st, a);
+  launch_topk_select(st, model, E, N, d, a.Q, nq, k, excl_off, excl_ent,
+                     (char*)workspace + topk_q_bytes(nq, d), ent_out, score_out);
   SKGE_CHECK_LAUNCH("top-k");
   return SKGE_OK;
 }

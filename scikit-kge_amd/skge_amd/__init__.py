@@ -10,7 +10,8 @@ from .hole import HolE
 from .rescal import RESCAL
 from .param import Parameter, SGD, AdaGrad, normalize, normless1
 from .sample import RandomModeSampler, CorruptedSampler, LCWASampler, type_index
-from .eval import FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores
+from .eval import (FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores,
+                   relation_ranking_scores)
 from .predict import LinkPredictor
 from .subgraphs import SUBTYPE, Subgraphs, SubgraphRankingEval, subgraph_ranking_scores
 from .neighbours import Neighbours, shared_role

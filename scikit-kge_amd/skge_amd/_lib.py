@@ -88,6 +88,11 @@ SIGNATURES = {
                                  c_p, c_p, c_sz, c_p, c_p]),
     "skge_neighbours_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_neighbours": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_p]),
+    "skge_relrank_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "skge_relrank": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "skge_reltopk_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "skge_reltopk": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_sz,
+                           c_p, c_p]),
     "skge_pair_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),

@@ -68,7 +68,9 @@ class FilteredRankingEval(object):
         self._true = triples_array(true_triples)
         self._kg = {}        # per device: the known-triple set
         self._answers = {}   # per device: the known-answer CSR
+        self._relations = {}   # per device: the known-relation CSR
         self.last_ranks = None
+        self.last_relation_ranks = None
 
     def _known_set(self, device):
         key = str(torch.device(device))
@@ -144,6 +146,65 @@ class FilteredRankingEval(object):
             k += n
         return pos, fpos
 
+    # ---- the relation slot: the position of p among all relations of (s, ?, o) ----
+
+    def _known_relations(self, q, device):
+        """Per query (s, o, p) its other known relations {p' != p: (s, o, p')
+        known}, ascending, as int32 CSR on the device."""
+        key = str(torch.device(device))
+        if key not in self._relations:
+            rels = defaultdict(set)
+            for s, o, p in self._true.tolist():
+                rels[(s, o)].add(p)
+            off, rel = [0], []
+            for s, o, p in q:
+                rel.extend(sorted(x for x in rels.get((s, o), ()) if x != p))
+                off.append(len(rel))
+            as_dev = lambda v: torch.as_tensor(np.asarray(v if v else [0], dtype=np.int32),
+                                               device=device)
+            self._relations[key] = (as_dev(off), as_dev(rel))
+        return self._relations[key]
+
+    def relation_ranks(self, model):
+        """[n, 2] int64 array: raw and filtered rank of the true relation p
+        among all relations of (s, ?, o), for the test triples in the
+        evaluator's order (as ranks()).  A rank is 1 + #relations scoring
+        strictly higher; the filtered rank skips every other p' with
+        (s, o, p') known.  One ``skge_relrank`` call (csrc/skge_relation.hip)."""
+        code, rel = _model_code(model)
+        dev = model.device
+        q = [(s, o, p) for p, sos in self.idx.items() for (s, o) in sos]
+        E = model.params["E"]
+        check_triple_ids(q, E.rows, rel.rows, "test triples")
+        check_triple_ids(self._true, E.rows, rel.rows, "known triples")
+        if not q:
+            self.last_relation_ranks = np.zeros((0, 2), dtype=np.int64)
+            return self.last_relation_ranks
+        queries = torch.as_tensor(np.asarray(q, dtype=np.int32), device=dev)
+        off, known = self._known_relations(q, dev)
+        lib = L.lib()
+        out = torch.empty((len(q), 2), dtype=torch.int32, device=dev)
+        nbytes = lib.skge_relrank_workspace_bytes(len(q), model.d, rel.rows, code)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(lib.skge_relrank(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), E.rows,
+                                 rel.rows, model.d, L.ptr(queries), len(q), L.ptr(off),
+                                 L.ptr(known), L.ptr(ws), nbytes, L.ptr(out)), "relrank")
+        self.last_relation_ranks = out.cpu().numpy().astype(np.int64)
+        return self.last_relation_ranks
+
+    def relation_positions(self, model):
+        """(pos, fpos) = {p: {'rel': [...]}} (raw, filtered): positions()'s
+        structure for the relation slot."""
+        r = self.relation_ranks(model)
+        pos, fpos = {}, {}
+        k = 0
+        for p, sos in self.idx.items():
+            n = len(sos)
+            pos[p] = {"rel": r[k:k + n, 0].tolist()}
+            fpos[p] = {"rel": r[k:k + n, 1].tolist()}
+            k += n
+        return pos, fpos
+
 
 class TransEEval(FilteredRankingEval):
     """skge/run_transe.py:13-29 (scores -sum|E[s] + R[p] - E|, either norm)."""
@@ -165,3 +226,11 @@ def ranking_scores(pos, fpos):
     raw = [x for k in pos for x in pos[k]["head"] + pos[k]["tail"]]
     filt = [x for k in fpos for x in fpos[k]["head"] + fpos[k]["tail"]]
     return compute_scores(raw), compute_scores(filt)
+
+
+def relation_ranking_scores(pos, fpos, hits=1):
+    """Raw and filtered (MRR, mean position, hits@``hits`` in percent) over the
+    relation positions of every relation (relation_positions' structures)."""
+    raw = [x for k in pos for x in pos[k]["rel"]]
+    filt = [x for k in fpos for x in fpos[k]["rel"]]
+    return compute_scores(raw, hits), compute_scores(filt, hits)

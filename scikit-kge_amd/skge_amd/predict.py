@@ -6,7 +6,8 @@ score every entity against each query and return the k best in one
 ``skge_topk`` call (csrc/skge_topk.hip): entity ids int64 [n, k] and scores
 float32 [n, k], ordered by descending score, then ascending id among exactly
 equal scores; when fewer than k entities are eligible the remaining slots
-hold id -1 and score -inf.
+hold id -1 and score -inf.  ``.relations(s, o, k)`` asks for the relation slot
+of (s, ?, o) the same way (``skge_reltopk``, csrc/skge_relation.hip).
 
 scoring="eval" scores as FilteredRankingEval ranks (any TransE by the L1
 distance); scoring="model" uses the model's own score (the squared L2
@@ -44,7 +45,7 @@ class LinkPredictor(object):
         self.model = model
         self.scoring = scoring
         self._known = None if known_triples is None else triples_array(known_triples)
-        self._answers = None   # ({(s, p): tails}, {(o, p): heads})
+        self._answers = None   # ({(s, p): tails}, {(o, p): heads}, {(s, o): relations})
         self._csr = {}         # per device and query set: the exclusion CSR
 
     def tails(self, s, p, k=10, filtered=True, exclude=None):
@@ -55,21 +56,70 @@ class LinkPredictor(object):
         """The k best subjects of (?, p, o)."""
         return self._topk(o, p, k, filtered, exclude, 1)
 
+    def relations(self, s, o, k=10, filtered=True, exclude=None):
+        """The k best relations of (s, ?, o): relation ids int64 [n, k] and
+        scores float32 [n, k] in one ``skge_reltopk`` call
+        (csrc/skge_relation.hip), ordered and padded as tails().
+        filtered=True excludes every known relation of (s, o); exclude: per
+        query an iterable of further relation ids."""
+        model = self.model
+        code, rel = _model_code(model)
+        if self.scoring == "model":
+            code = model._kernel_model()
+        E = model.params["E"]
+        n_ent, n_rel = E.rows, rel.rows
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
+            raise ValueError("k must be an integer in 1 .. %d, not %r" % (K_MAX, k))
+        k = int(k)
+        if filtered and self._known is None:
+            raise ValueError("filtered=True needs known_triples (or pass filtered=False)")
+        a = np.asarray(s, dtype=np.int64).reshape(-1)
+        b = np.asarray(o, dtype=np.int64).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("relations: %d subjects for %d objects" % (len(a), len(b)))
+        _check_ids(a, n_ent, "relations", "subject")
+        _check_ids(b, n_ent, "relations", "object")
+        if filtered:
+            check_triple_ids(self._known, n_ent, n_rel, "known triples")
+        n = len(a)
+        if n == 0:
+            return np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
+        dev = model.device
+        q = np.stack([a, b], axis=1).astype(np.int32)
+        xkey = None if exclude is None else repr([None if e is None else np.asarray(e).tolist()
+                                                  for e in (exclude if n > 1 else [exclude])])
+        key = (str(torch.device(dev)), "rel", bool(filtered), q.tobytes(), xkey)
+        csr = self._device_csr(
+            key, lambda: self._exclusions(a, b, 2, filtered, exclude, n_rel), dev)
+        pairs = torch.as_tensor(q, device=dev)
+        lib = L.lib()
+        rels = torch.empty((n, k), dtype=torch.int32, device=dev)
+        scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        nbytes = lib.skge_reltopk_workspace_bytes(n, model.d, k, n_rel, code)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(lib.skge_reltopk(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), n_ent, n_rel,
+                                 model.d, L.ptr(pairs), n, k,
+                                 L.ptr(csr[0]) if csr else None, L.ptr(csr[1]) if csr else None,
+                                 L.ptr(ws), nbytes, L.ptr(rels), L.ptr(scores)), "reltopk")
+        return rels.cpu().numpy().astype(np.int64), scores.cpu().numpy()
+
     # ---- host side: ids, the exclusion lists ----
 
     def _known_answers(self):
         if self._answers is None:
-            tails, heads = defaultdict(set), defaultdict(set)
+            tails, heads, rels = defaultdict(set), defaultdict(set), defaultdict(set)
             for s, o, p in self._known.tolist():
                 tails[(s, p)].add(o)
                 heads[(o, p)].add(s)
-            self._answers = (tails, heads)
+                rels[(s, o)].add(p)
+            self._answers = (tails, heads, rels)
         return self._answers
 
     def _exclusions(self, anchors, rels, direction, filtered, exclude, n_ent):
         """Per query the sorted, de-duplicated union of its known answers
         (filtered) and its ``exclude`` ids, as (offsets [n + 1], ids) int32;
-        None when every list is empty."""
+        None when every list is empty.  direction 2: the queries are (s, o)
+        pairs and the ids relations, n_ent their range."""
         n = len(anchors)
         extra = [()] * n
         if exclude is not None:
@@ -82,8 +132,9 @@ class LinkPredictor(object):
             for i, e in enumerate(extra):
                 bad = (e < 0) | (e >= n_ent)
                 if bad.any():
-                    raise ValueError("exclude: query %d has entity %d, out of range for %d"
-                                     % (i, int(e[np.argmax(bad)]), n_ent))
+                    raise ValueError("exclude: query %d has %s %d, out of range for %d"
+                                     % (i, "relation" if direction == 2 else "entity",
+                                        int(e[np.argmax(bad)]), n_ent))
         known = self._known_answers()[direction] if filtered else {}
         off, ent = [0], []
         for i, (a, p) in enumerate(zip(anchors.tolist(), rels.tolist())):
