@@ -878,6 +878,67 @@ int skge_reltopk(void *stream, int model, const float *E, const float *R, int N,
                  const int *pairs, int nq, int k, const int *excl_off, const int *excl_rel,
                  void *workspace, size_t ws_bytes, int *rel_out, float *score_out);
 
+/* ---------------- type-constrained ranking: candidate pools ---------------- */
+
+/*
+ * skge_rank_known and skge_topk restricted to CANDIDATE POOLS: each query
+ * vector is ranked against, or selects among, the members of one pool instead
+ * of all N entities -- the type-constrained protocol (a relation's range or
+ * domain), or any explicit or sampled candidate list.
+ *
+ * The pools are a CSR as DeviceKG.pools builds it for the typed samplers
+ * (skge_sampler_t): pool_off int64 [n_pools + 1], pool_ent int32, the ids
+ * ASCENDING AND UNIQUE within a pool.  Pools may be empty and may overlap.
+ * Pool id -1 means every entity 0 .. N - 1 (n_pools == 0 with NULL pool
+ * arrays is legal: every id must then be -1).  The library groups the
+ * vectors by pool on the device; they may come in any order.
+ *
+ * skge_rank_pools: vec_pool [2 nq], vector 2i = the tail query of test triple
+ * i = (s, o, p) of queries[nq][3], vector 2i + 1 its head query.  Query
+ * vectors, the true entity's score (recomputed with the counting pass's
+ * arithmetic, so the true entity never outranks itself), the strict >
+ * comparison and both TransE codes scored by L1 are skge_rank_known's.
+ *   ranks_out[4i + 2 dir]     = 1 + #{pool members scoring strictly above the
+ *                               true entity}; the true entity is a candidate
+ *                               whether its pool holds it or not (it adds 0);
+ *                               an empty pool gives 1;
+ *   ranks_out[4i + 2 dir + 1] = that rank - #{known answers of the query that
+ *                               are members of the vector's pool and score
+ *                               strictly above the true entity}.
+ * tail_off / tail_ent / head_off / head_ent: skge_rank_known's known-answer
+ * CSR, unchanged (every known answer, true entity excluded); answers outside
+ * the pool are ignored here (a binary search in the ascending pool), and
+ * under pool -1 every answer counts.  With vec_pool all -1, or one explicit
+ * pool 0 .. N - 1, the result equals skge_rank_known's integer for integer.
+ *
+ * skge_topk_pools: skge_topk (its score forms, order, padding (-1, -inf),
+ * exclusion CSR, 1 <= k <= 128, k above the pool size legal) with query i
+ * selecting among the members of pool query_pool[i] that are not excluded.
+ *
+ * Refused before any launch, with an error text: NULL arguments, a model
+ * outside 0 .. 3, d > 1024, n_pools < 0, n_pools > 0 with NULL pool arrays,
+ * k out of range, a workspace below the workspace function's size.  nq == 0
+ * launches nothing.  Pool ids and entity ids inside device arrays are NOT
+ * range-checked here (skge_amd's evaluator and predictor check them on the
+ * host).  Caller-owned buffers, stream-ordered.
+ */
+size_t skge_rank_pools_workspace_bytes(int nq, int d, int n_pools);
+int skge_rank_pools(void *stream, int model, const float *E, const float *R, int N, int d,
+                    const int *queries, int nq,
+                    const int64_t *pool_off, const int *pool_ent, int n_pools,
+                    const int *vec_pool,
+                    const int *tail_off, const int *tail_ent,
+                    const int *head_off, const int *head_ent,
+                    void *workspace, size_t ws_bytes, int *ranks_out);
+
+size_t skge_topk_pools_workspace_bytes(int nq, int d, int k, int N, int n_pools);
+int skge_topk_pools(void *stream, int model, const float *E, const float *R, int N, int d,
+                    const int *queries, int nq, int direction, int k,
+                    const int64_t *pool_off, const int *pool_ent, int n_pools,
+                    const int *query_pool,
+                    const int *excl_off, const int *excl_ent,
+                    void *workspace, size_t ws_bytes, int *ent_out, float *score_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,10 +144,33 @@ void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d,
 // -sum|q - T_j|, TRANSE_L2: -sum (q - T_j)^2, else the dot product); excl_*:
 // skge_topk's exclusion CSR over row ids.  lists: topk_lists_bytes(nq, k,
 // rows) bytes of workspace.
-size_t topk_lists_bytes(int nq, int k, int rows);
+//
+// With a grouped work list over n_pools >= 0 pools (skge_pools.h), the
+// selection is GATHERED: query i selects among the rows its pool lists (the
+// ids returned are the pool's entries), the query blocks are the list's items
+// (built with topk_block_size(k) vectors per item) and every pool is cut into
+// the plan's slices (pools->ns is set here).
+// launch_topk_query: skge_topk's query vectors (anchor, p) of one direction
+// into Q [nq][d].
+struct PoolWork;
+void launch_topk_query(hipStream_t st, int model, const float* E, const float* R, int d,
+                       const int* queries, int nq, int direction, float* Q);
+int topk_block_size(int k);
+size_t topk_lists_bytes(int nq, int k, int rows, int n_pools = -1);
 void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int d, const float* Q,
                         int nq, int k, const int* excl_off, const int* excl_ent, void* lists,
-                        int* ent_out, float* score_out);
+                        int* ent_out, float* score_out, const PoolWork* pools = nullptr,
+                        int n_pools = -1);
+
+// skge_pools.hip: group nv query vectors by pool id (vec_pool [nv], -1 = all
+// entities) into items of up to bsz vectors.  pool_items_max: the bound on the
+// item count the consumers size their grids with; pool_group_bytes: the
+// workspace launch_pool_group needs (16-B aligned base).  *w: the list, its
+// arrays inside ws.
+int pool_items_max(int nv, int n_pools, int bsz);
+size_t pool_group_bytes(int nv, int n_pools, int bsz);
+int launch_pool_group(hipStream_t st, const int* vec_pool, int nv, int n_pools, int bsz,
+                      const int64_t* pool_off, const int* pool_ent, void* ws, PoolWork* w);
 
 // skge_pipeline.hip: draw every negative of the epoch whose key is *epoch_key
 // (rec[j] = (s, o, p, s' or -1), rec_n1[j] = o' or -1 for positive j of the

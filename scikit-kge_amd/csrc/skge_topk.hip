@@ -13,9 +13,13 @@
 //                   queries' sorted lists
 //   k_topk_merge    one wave per query: the slices' lists into the final k
 // The lists are 64-bit keys in one compare order: skge_topk_list.h.
+// k_topk_select<.., GATHER> is the same selection over candidate pools: query
+// blocks from a grouped work list, rows through an index (skge_pools.h;
+// skge_topk_pools, skge_pools.hip).
 #include <algorithm>
 
 #include "skge_host.h"
+#include "skge_pools.h"
 #include "skge_topk_list.h"
 
 namespace skge {
@@ -37,6 +41,7 @@ struct TopkArgs {
   int eslice, ns;        // entities per slice (multiple of TK_EB), slices
   int* ent_out;          // [nq][k]
   float* score_out;      // [nq][k]
+  PoolWork pw;           // the gathered selection's work list (k_topk_select<.., true>)
 };
 
 // ---- query vectors: one wave per query (k_rank_query's arithmetic) ----
@@ -91,7 +96,11 @@ __global__ __launch_bounds__(128) void k_topk_query(TopkArgs a) {
 // wave's registers while one of the tile's scores beats its k-th entry.
 // LDS: max(staging, scores) + lists = 33.0 + 16 KB (QB 64, k <= 32),
 // 21.0 + 32 KB (QB 32, k <= 128).
-template <int FORM, int QB, int KCAP>
+// GATHER (skge_pools.h): the workgroup's queries are item blockIdx.x of the
+// grouped work list, reached through its order array, and the candidate rows
+// are its pool's entries (row pool_ent[base + e] for candidate e, + 0.5 KB of
+// LDS for a tile's row ids); blockIdx.y is a slice of that pool.
+template <int FORM, int QB, int KCAP, bool GATHER = false>
 __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
   constexpr int PADQ = QB + 4;
   constexpr int TQ = QB / 16;               // queries per thread
@@ -106,9 +115,23 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
   float (*sS)[TK_PADE] = reinterpret_cast<float (*)[TK_PADE]>(s_buf);
   const int tid = threadIdx.x, d = a.d, k = a.k;
   const int l = tid & 63, w = tid >> 6;
-  const int v0 = blockIdx.x * QB;
-  const int ebeg = blockIdx.y * a.eslice;
-  const int eend = a.N - ebeg < a.eslice ? a.N : ebeg + a.eslice;
+  __shared__ int s_rid[GATHER ? TK_EB : 1];
+  int v0 = blockIdx.x * QB, nvec = a.nq;   // the block's vectors: slots v0 .. of [0, nvec)
+  int ebeg = blockIdx.y * a.eslice;
+  int eend = a.N - ebeg < a.eslice ? a.N : ebeg + a.eslice;
+  int pool = -1;
+  int64_t pbase = 0;
+  if constexpr (GATHER) {
+    if ((int)blockIdx.x >= *a.pw.n_items) return;
+    const int4 it = a.pw.items[blockIdx.x];
+    pool = it.x;
+    v0 = it.y;
+    nvec = it.y + it.z;
+    pool_slice(pool_size(a.pw, pool, a.N, pbase), a.pw.ns, blockIdx.y, ebeg, eend);
+  }
+  // slot -> query id, candidate -> row id
+  auto vec_of = [&](int slot) { return GATHER ? a.pw.order[slot] : slot; };
+  auto row_of = [&](int e) { return GATHER && pool >= 0 ? a.pw.pool_ent[pbase + e] : e; };
   for (int i = tid; i < QB * KCAP; i += 256) (&s_list[0][0])[i] = 0;
   __syncthreads();
   const int te = (tid & 15) * 8, tq = (tid >> 4) * TQ;
@@ -124,12 +147,12 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
       float4 qa[NQ4], ea[4];
       {
         const int v = v0 + sq_v;
-        const float* qrow = a.Q + (size_t)(v < a.nq ? v : 0) * d;
+        const float* qrow = a.Q + (size_t)(v < nvec ? vec_of(v) : 0) * d;
 #pragma unroll
         for (int u = 0; u < NQ4; ++u) {
           const int kk = k0 + sq_k + 4 * LPV * u;
           float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-          if (v < a.nq) {
+          if (v < nvec) {
             if ((d & 3) == 0 && kk + 3 < d) {
               x = *reinterpret_cast<const float4*>(qrow + kk);
             } else {
@@ -142,7 +165,7 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
           qa[u] = x;
         }
         const int e = e0 + se_e;
-        const float* erow = a.E + (size_t)(e < eend ? e : ebeg) * d;
+        const float* erow = a.E + (size_t)(e < eend ? row_of(e) : GATHER ? 0 : ebeg) * d;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int kk = k0 + se_k + 8 * u;
@@ -214,13 +237,16 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
       *reinterpret_cast<float4*>(&sS[tq + y][te + 4]) =
           make_float4(acc[4][y], acc[5][y], acc[6][y], acc[7][y]);
     }
+    if constexpr (GATHER) {
+      if (tid < TK_EB) s_rid[tid] = e0 + tid < eend ? row_of(e0 + tid) : -1;
+    }
     __syncthreads();
     for (int qq = w; qq < QB; qq += 4) {   // wave-uniform
-      const int v = v0 + qq;
-      if (v >= a.nq) break;
+      if (v0 + qq >= nvec) break;
+      const int v = vec_of(v0 + qq);
       const int ea0 = e0 + l, ea1 = e0 + 64 + l;
-      const tkey_t c0 = ea0 < eend ? make_key(sS[qq][l], ea0) : 0;
-      const tkey_t c1 = ea1 < eend ? make_key(sS[qq][64 + l], ea1) : 0;
+      const tkey_t c0 = ea0 < eend ? make_key(sS[qq][l], GATHER ? s_rid[l] : ea0) : 0;
+      const tkey_t c1 = ea1 < eend ? make_key(sS[qq][64 + l], GATHER ? s_rid[64 + l] : ea1) : 0;
       tkey_t thr = s_list[qq][k - 1];
       if (__ballot(c0 > thr || c1 > thr) == 0) continue;
       tkey_t lo = l < k ? s_list[qq][l] : 0;
@@ -241,8 +267,8 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a) {
   // this (query, slice)'s list: each wave writes the queries it owns
   __builtin_amdgcn_wave_barrier();
   for (int qq = w; qq < QB; qq += 4) {
-    const int v = v0 + qq;
-    if (v >= a.nq) break;
+    if (v0 + qq >= nvec) break;
+    const int v = vec_of(v0 + qq);
     tkey_t* out = a.lists + ((size_t)v * a.ns + blockIdx.y) * k;
     if (l < k) out[l] = s_list[qq][l];
     if (64 + l < k) out[64 + l] = s_list[qq][64 + l];
@@ -279,10 +305,13 @@ __global__ __launch_bounds__(256) void k_topk_merge(TopkArgs a) {
 struct TopkPlan {
   int qb_size, qb, eslice, ns;
 };
-static TopkPlan topk_plan(int nq, int k, int N) {
+int topk_block_size(int k) { return k <= 32 ? 64 : 32; }
+// n_pools >= 0: the gathered selection, whose query blocks are the grouped
+// work list's items (their bound; a pool has at most N entries)
+static TopkPlan topk_plan(int nq, int k, int N, int n_pools = -1) {
   TopkPlan p;
-  p.qb_size = k <= 32 ? 64 : 32;
-  p.qb = (nq + p.qb_size - 1) / p.qb_size;
+  p.qb_size = topk_block_size(k);
+  p.qb = n_pools >= 0 ? pool_items_max(nq, n_pools, p.qb_size) : (nq + p.qb_size - 1) / p.qb_size;
   const int tiles = (N + TK_EB - 1) / TK_EB;
   const int want = std::max(1, std::min(tiles, (2048 + p.qb - 1) / std::max(1, p.qb)));
   const int per = (tiles + want - 1) / want;
@@ -295,23 +324,31 @@ static size_t topk_q_bytes(int nq, int d) {
 }
 
 template <int FORM>
-static void launch_select(hipStream_t st, const TopkPlan& p, const TopkArgs& a) {
-  if (p.qb_size == 64)
-    hipLaunchKernelGGL((k_topk_select<FORM, 64, 32>), dim3(p.qb, p.ns), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((k_topk_select<FORM, 32, TK_KMAX>), dim3(p.qb, p.ns), dim3(256), 0, st, a);
+static void launch_select(hipStream_t st, const TopkPlan& p, const TopkArgs& a, bool gather) {
+  const dim3 grid(p.qb, p.ns);
+  if (gather) {
+    if (p.qb_size == 64)
+      hipLaunchKernelGGL((k_topk_select<FORM, 64, 32, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((k_topk_select<FORM, 32, TK_KMAX, true>), grid, dim3(256), 0, st, a);
+  } else if (p.qb_size == 64) {
+    hipLaunchKernelGGL((k_topk_select<FORM, 64, 32>), grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((k_topk_select<FORM, 32, TK_KMAX>), grid, dim3(256), 0, st, a);
+  }
 }
 
 // the selection and the merge over any table T [rows][d] for query vectors
 // Q [nq][d] (skge_host.h): model picks the score's form as skge_topk does
-size_t topk_lists_bytes(int nq, int k, int rows) {
-  const TopkPlan p = topk_plan(nq, k, rows);
+size_t topk_lists_bytes(int nq, int k, int rows, int n_pools) {
+  const TopkPlan p = topk_plan(nq, k, rows, n_pools);
   return (size_t)nq * p.ns * k * sizeof(tkey_t);
 }
 void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int d, const float* Q,
                         int nq, int k, const int* excl_off, const int* excl_ent, void* lists,
-                        int* ent_out, float* score_out) {
-  const TopkPlan p = topk_plan(nq, k, rows);
+                        int* ent_out, float* score_out, const PoolWork* pools, int n_pools) {
+  const bool gather = pools != nullptr;
+  const TopkPlan p = topk_plan(nq, k, rows, gather ? n_pools : -1);
   TopkArgs a = {};
   a.E = T;
   a.N = rows;
@@ -327,13 +364,33 @@ void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int
   a.ns = p.ns;
   a.ent_out = ent_out;
   a.score_out = score_out;
+  if (gather) {
+    a.pw = *pools;
+    a.pw.ns = p.ns;
+  }
   if (model == SKGE_TRANSE_L1)
-    launch_select<TK_L1>(st, p, a);
+    launch_select<TK_L1>(st, p, a, gather);
   else if (model == SKGE_TRANSE_L2)
-    launch_select<TK_L2SQ>(st, p, a);
+    launch_select<TK_L2SQ>(st, p, a, gather);
   else
-    launch_select<TK_DOT>(st, p, a);
+    launch_select<TK_DOT>(st, p, a, gather);
   hipLaunchKernelGGL(k_topk_merge, dim3((nq + 3) / 4), dim3(256), 0, st, a);
+}
+
+// the query vectors of nq queries (anchor, p) of one direction into Q [nq][d]
+void launch_topk_query(hipStream_t st, int model, const float* E, const float* R, int d,
+                       const int* queries, int nq, int direction, float* Q) {
+  TopkArgs a = {};
+  a.E = E;
+  a.R = R;
+  a.d = d;
+  a.model = model;
+  a.nq = nq;
+  a.direction = direction;
+  a.queries = queries;
+  a.Q = Q;
+  const int qblocks = std::max(1, std::min((nq + 1) / 2, 16384));
+  hipLaunchKernelGGL(k_topk_query, dim3(qblocks), dim3(128), 0, st, a);
 }
 
 }  // namespace skge
@@ -358,19 +415,10 @@ extern "C" int skge_topk(void* stream, int model, const float* E, const float* R
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_topk_workspace_bytes(nq, d, k, N),
                  "top-k workspace needs %zu bytes", skge_topk_workspace_bytes(nq, d, k, N));
-  TopkArgs a = {};
-  a.E = E;
-  a.R = R;
-  a.d = d;
-  a.model = model;
-  a.nq = nq;
-  a.direction = direction;
-  a.queries = queries;
-  a.Q = (float*)workspace;
+  float* Q = (float*)workspace;
   hipStream_t st = as_stream(stream);
-  const int qblocks = std::max(1, std::min((nq + 1) / 2, 16384));
-  hipLaunchKernelGGL(k_topk_query, dim3(qblocks), dim3(128), 0, st, a);
-  launch_topk_select(st, model, E, N, d, a.Q, nq, k, excl_off, excl_ent,
+  launch_topk_query(st, model, E, R, d, queries, nq, direction, Q);
+  launch_topk_select(st, model, E, N, d, Q, nq, k, excl_off, excl_ent,
                      (char*)workspace + topk_q_bytes(nq, d), ent_out, score_out);
   SKGE_CHECK_LAUNCH("top-k");
   return SKGE_OK;

@@ -11,7 +11,7 @@ from .rescal import RESCAL
 from .param import Parameter, SGD, AdaGrad, normalize, normless1
 from .sample import RandomModeSampler, CorruptedSampler, LCWASampler, type_index
 from .eval import (FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores,
-                   relation_ranking_scores)
+                   relation_ranking_scores, pool_csr, type_pools)
 from .predict import LinkPredictor
 from .subgraphs import SUBTYPE, Subgraphs, SubgraphRankingEval, subgraph_ranking_scores
 from .neighbours import Neighbours, shared_role

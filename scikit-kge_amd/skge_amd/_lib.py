@@ -93,6 +93,12 @@ SIGNATURES = {
     "skge_reltopk_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "skge_reltopk": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_sz,
                            c_p, c_p]),
+    "skge_rank_pools_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "skge_rank_pools": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p,
+                              c_p, c_p, c_p, c_sz, c_p]),
+    "skge_topk_pools_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "skge_topk_pools": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p,
+                              c_p, c_p, c_p, c_sz, c_p, c_p]),
     "skge_pair_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),

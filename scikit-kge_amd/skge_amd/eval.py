@@ -53,6 +53,84 @@ def check_triple_ids(triples, n_ent, n_rel, what="triples"):
                          "%d relations" % (what, i, s, o, p, n_ent, n_rel))
 
 
+def pool_csr(pools, n_ent, what="pools"):
+    """Candidate pools as the CSR the pool entry points read
+    (include/skge_hip.h, skge_rank_pools): (off int64 [n_pools + 1], ent
+    int32), every pool's ids ascending and unique.  ``pools`` is a list of id
+    collections, or a tuple ``(off, ent)`` that already is the CSR.  A pool
+    given as a Python list, tuple or set is sorted and de-duplicated; an
+    array (numpy or torch) must already be ascending and unique.  Raises
+    ValueError, naming the first offender, for an id outside 0 .. n_ent - 1,
+    for an array out of order and for offsets that are not a CSR's.  This is
+    the bounds check: the kernels index the entity table with these ids."""
+    if isinstance(pools, tuple) and len(pools) == 2:
+        off, ent = (x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in pools)
+        off = off.astype(np.int64).reshape(-1)
+        ent = ent.astype(np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or off[-1] != len(ent) or (np.diff(off) < 0).any():
+            raise ValueError("%s: offsets are not a CSR over %d ids" % (what, len(ent)))
+    else:
+        rows = []
+        for g in pools:
+            if torch.is_tensor(g):
+                g = g.cpu().numpy()
+            if isinstance(g, np.ndarray):
+                rows.append(g.astype(np.int64).reshape(-1))
+            else:
+                rows.append(np.unique(np.asarray(list(g), dtype=np.int64)))
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in rows])
+        ent = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    which = np.searchsorted(off, np.arange(len(ent)), side="right") - 1   # each id's pool
+    bad = (ent < 0) | (ent >= n_ent)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("%s: pool %d holds id %d, out of range for %d entities"
+                         % (what, int(which[i]), int(ent[i]), n_ent))
+    if len(ent) > 1:
+        bad = (ent[1:] <= ent[:-1]) & (which[1:] == which[:-1])
+        if bad.any():
+            i = int(np.argmax(bad)) + 1
+            raise ValueError("%s: pool %d is not ascending and unique (id %d after %d)"
+                             % (what, int(which[i]), int(ent[i]), int(ent[i - 1])))
+    return off, ent.astype(np.int32)
+
+
+def check_pool_ids(ids, n_pools, what):
+    """int32 array of ``ids``; ValueError naming the first one outside
+    -1 .. n_pools - 1 (-1: every entity)."""
+    a = np.asarray(ids, dtype=np.int64).reshape(-1)
+    bad = (a < -1) | (a >= n_pools)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("%s: entry %d names pool %d, outside -1 .. %d"
+                         % (what, i, int(a[i]), n_pools - 1))
+    return a.astype(np.int32)
+
+
+def type_pools(types, n_rel):
+    """The type index as a list of 2 * n_rel sorted id arrays, DeviceKG.pools'
+    layout: pool 2p holds the subjects (the domain) of relation p, pool 2p + 1
+    its objects (the range); a relation without triples has two empty pools.
+    ``types``: a ``type_index(xs)`` dict, or an array of triples (s, o, p)."""
+    sets = [set() for _ in range(2 * n_rel)]
+    if isinstance(types, dict):
+        for p, sides in types.items():
+            if not 0 <= int(p) < n_rel:
+                raise ValueError("type index: relation %d is out of range for %d relations"
+                                 % (int(p), n_rel))
+            sets[2 * int(p)].update(int(x) for x in sides[0])
+            sets[2 * int(p) + 1].update(int(x) for x in sides[1])
+    else:
+        for s, o, p in triples_array(types).tolist():
+            if not 0 <= p < n_rel:
+                raise ValueError("type index: relation %d is out of range for %d relations"
+                                 % (p, n_rel))
+            sets[2 * p].add(s)
+            sets[2 * p + 1].add(o)
+    return [np.array(sorted(g), dtype=np.int64) for g in sets]
+
+
 class FilteredRankingEval(object):
     """xs: test triples (s, o, p); true_triples: every known triple (the
     filter).  neval is accepted for signature compatibility (the reference
@@ -71,6 +149,7 @@ class FilteredRankingEval(object):
         self._relations = {}   # per device: the known-relation CSR
         self.last_ranks = None
         self.last_relation_ranks = None
+        self.last_typed_candidates = None
 
     def _known_set(self, device):
         key = str(torch.device(device))
@@ -136,7 +215,9 @@ class FilteredRankingEval(object):
         return self.last_ranks
 
     def positions(self, mdl, plot=False, pagerankMap=None):
-        r = self.ranks(mdl)
+        return self._positions_of(self.ranks(mdl))
+
+    def _positions_of(self, r):
         pos, fpos = {}, {}
         k = 0
         for p, sos in self.idx.items():
@@ -145,6 +226,80 @@ class FilteredRankingEval(object):
             fpos[p] = {"tail": r[k:k + n, 1].tolist(), "head": r[k:k + n, 3].tolist()}
             k += n
         return pos, fpos
+
+    # ---- candidate pools: ranks over a restricted candidate set ----
+
+    def candidate_ranks(self, model, pools, tail_pool, head_pool):
+        """ranks() over candidate pools: [n, 4] int64 laid out as ranks(), each
+        rank counted over the members of the query's pool (and the true
+        entity, whether the pool holds it or not) instead of all entities.
+        ``pools``: a list of id collections or a tuple ``(off, ent)``
+        (pool_csr); ``tail_pool`` / ``head_pool``: per test triple, in the
+        evaluator's order, the pool id of its tail / head query, or -1 for
+        every entity.  The filtered rank skips the known answers that are in
+        the pool.  One ``skge_rank_pools`` call (csrc/skge_pools.hip); pool
+        and member ids are checked here, on the host."""
+        code, rel = _model_code(model)
+        dev = model.device
+        q = [(s, o, p) for p, sos in self.idx.items() for (s, o) in sos]
+        E = model.params["E"]
+        check_triple_ids(q, E.rows, rel.rows, "test triples")
+        check_triple_ids(self._true, E.rows, rel.rows, "known triples")
+        off, ent = pool_csr(pools, E.rows)
+        n_pools = len(off) - 1
+        tp = check_pool_ids(tail_pool, n_pools, "tail_pool")
+        hp = check_pool_ids(head_pool, n_pools, "head_pool")
+        if len(tp) != len(q) or len(hp) != len(q):
+            raise ValueError("candidate_ranks: %d tail and %d head pool ids for %d test triples"
+                             % (len(tp), len(hp), len(q)))
+        if not q:
+            return np.zeros((0, 4), dtype=np.int64)
+        queries = torch.as_tensor(np.asarray(q, dtype=np.int32), device=dev)
+        vec_pool = torch.as_tensor(np.stack([tp, hp], axis=1).reshape(-1), device=dev)
+        d_off = torch.as_tensor(off, device=dev)
+        d_ent = torch.as_tensor(ent if len(ent) else np.zeros(1, dtype=np.int32), device=dev)
+        toff, tent, hoff, hent = self._known_answers(q, dev)
+        lib = L.lib()
+        out = torch.empty((len(q), 4), dtype=torch.int32, device=dev)
+        nbytes = lib.skge_rank_pools_workspace_bytes(len(q), model.d, n_pools)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(lib.skge_rank_pools(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), E.rows,
+                                    model.d, L.ptr(queries), len(q), L.ptr(d_off), L.ptr(d_ent),
+                                    n_pools, L.ptr(vec_pool), L.ptr(toff), L.ptr(tent),
+                                    L.ptr(hoff), L.ptr(hent), L.ptr(ws), nbytes, L.ptr(out)),
+                "rank (pools)")
+        return out.cpu().numpy().astype(np.int64)
+
+    def typed_pools(self, n_rel, types=None):
+        """(pools, tail_pool, head_pool) of the type-constrained protocol:
+        the tail query of test triple (s, o, p) ranks over the range of p
+        (pool 2p + 1), its head query over the domain (pool 2p).  types=None
+        takes the type index of ``true_triples``; a ``type_index(xs)`` dict or
+        an array of triples (the training triples, say) gives another."""
+        pools = type_pools(self._true if types is None else types, n_rel)
+        p = np.asarray([p for p, sos in self.idx.items() for _ in sos], dtype=np.int64)
+        return pools, 2 * p + 1, 2 * p
+
+    def typed_ranks(self, model, types=None):
+        """Type-constrained ranks, [n, 4] int64 laid out as ranks():
+        candidate_ranks over typed_pools.  ``last_typed_candidates`` [n, 2]
+        then holds the number of candidates each tail / head rank was taken
+        over, |pool + the true entity|."""
+        pools, tp, hp = self.typed_pools(_model_code(model)[1].rows, types)
+        r = self.candidate_ranks(model, pools, tp, hp)
+        q = [(s, o, p) for p, sos in self.idx.items() for (s, o) in sos]
+        cand = np.zeros((len(q), 2), dtype=np.int64)
+        for i, (s, o, p) in enumerate(q):
+            for col, pool, true in ((0, pools[tp[i]], o), (1, pools[hp[i]], s)):
+                j = int(np.searchsorted(pool, true))
+                cand[i, col] = len(pool) + (0 if j < len(pool) and pool[j] == true else 1)
+        self.last_typed_candidates = cand
+        return r
+
+    def typed_positions(self, model, types=None):
+        """positions()'s structures (pos, fpos) from typed_ranks;
+        ranking_scores works on them unchanged."""
+        return self._positions_of(self.typed_ranks(model, types))
 
     # ---- the relation slot: the position of p among all relations of (s, ?, o) ----
 

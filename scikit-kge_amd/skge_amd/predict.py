@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .eval import _model_code, check_triple_ids
+from .eval import _model_code, check_pool_ids, check_triple_ids, pool_csr, type_pools
 from .util import triples_array
 
 K_MAX = 128
@@ -47,14 +47,23 @@ class LinkPredictor(object):
         self._known = None if known_triples is None else triples_array(known_triples)
         self._answers = None   # ({(s, p): tails}, {(o, p): heads}, {(s, o): relations})
         self._csr = {}         # per device and query set: the exclusion CSR
+        self._types = None     # candidates="typed": the type index's pools as a CSR
 
-    def tails(self, s, p, k=10, filtered=True, exclude=None):
-        """The k best objects of (s, p, ?)."""
-        return self._topk(s, p, k, filtered, exclude, 0)
+    def tails(self, s, p, k=10, filtered=True, exclude=None, candidates=None):
+        """The k best objects of (s, p, ?).  candidates: None scores every
+        entity; "typed" only the range of p in ``known_triples`` (the objects
+        seen with p); a list of id arrays, one per query, or one array for
+        all queries, is an explicit candidate pool; a tuple ``(pools,
+        pool_ids)`` gives shared pools (pool_csr's forms) and each query's
+        pool id, -1 being every entity (``skge_topk_pools``,
+        csrc/skge_pools.hip).  Returned entities are pool members that are
+        not excluded; ids are checked on the host."""
+        return self._topk(s, p, k, filtered, exclude, 0, candidates)
 
-    def heads(self, o, p, k=10, filtered=True, exclude=None):
-        """The k best subjects of (?, p, o)."""
-        return self._topk(o, p, k, filtered, exclude, 1)
+    def heads(self, o, p, k=10, filtered=True, exclude=None, candidates=None):
+        """The k best subjects of (?, p, o); candidates as tails(), "typed"
+        being the domain of p."""
+        return self._topk(o, p, k, filtered, exclude, 1, candidates)
 
     def relations(self, s, o, k=10, filtered=True, exclude=None):
         """The k best relations of (s, ?, o): relation ids int64 [n, k] and
@@ -155,9 +164,45 @@ class LinkPredictor(object):
                 torch.as_tensor(x, device=device) for x in csr)
         return self._csr[key]
 
+    def _candidate_pools(self, candidates, rels, direction, n_ent, n_rel):
+        """(off, ent, query_pool) of ``candidates`` (tails()): the pools' CSR
+        (pool_csr: ids checked, Python lists sorted) and each query's pool."""
+        n = len(rels)
+        if isinstance(candidates, str):
+            if candidates != "typed":
+                raise ValueError("candidates must be None, 'typed' or id arrays, not %r"
+                                 % (candidates,))
+            if self._known is None:
+                raise ValueError("candidates='typed' needs known_triples")
+            check_triple_ids(self._known, n_ent, n_rel, "known triples")
+            if self._types is None:
+                self._types = pool_csr(type_pools(self._known, n_rel), n_ent, "candidates")
+            off, ent = self._types
+            return off, ent, check_pool_ids(2 * rels + (1 - direction), 2 * n_rel, "candidates")
+        if isinstance(candidates, tuple) and len(candidates) == 2:     # shared pools
+            off, ent = pool_csr(candidates[0], n_ent, "candidates")
+            ids = check_pool_ids(candidates[1], len(off) - 1, "candidates")
+            if len(ids) != n:
+                raise ValueError("candidates: %d pool ids for %d queries" % (len(ids), n))
+            return off, ent, ids
+        if torch.is_tensor(candidates):
+            candidates = candidates.cpu().numpy()
+        if isinstance(candidates, np.ndarray):
+            one = candidates.ndim == 1
+        else:
+            candidates = list(candidates)
+            one = len(candidates) > 0 and all(np.ndim(c) == 0 for c in candidates)
+        if one:     # one pool for every query
+            off, ent = pool_csr([candidates], n_ent, "candidates")
+            return off, ent, np.zeros(n, dtype=np.int32)
+        if len(candidates) != n:
+            raise ValueError("candidates: %d pools for %d queries" % (len(candidates), n))
+        off, ent = pool_csr(list(candidates), n_ent, "candidates")
+        return off, ent, np.arange(n, dtype=np.int32)
+
     # ---- the call ----
 
-    def _topk(self, anchor, p, k, filtered, exclude, direction):
+    def _topk(self, anchor, p, k, filtered, exclude, direction, candidates=None):
         model = self.model
         code, rel = _model_code(model)
         if self.scoring == "model":
@@ -181,6 +226,8 @@ class LinkPredictor(object):
         if filtered:
             check_triple_ids(self._known, n_ent, n_rel, "known triples")
         n = len(a)
+        pools = None if candidates is None else self._candidate_pools(candidates, r, direction,
+                                                                      n_ent, n_rel)
         if n == 0:
             return np.zeros((0, k), dtype=np.int64), np.zeros((0, k), dtype=np.float32)
         dev = model.device
@@ -194,6 +241,22 @@ class LinkPredictor(object):
         lib = L.lib()
         ents = torch.empty((n, k), dtype=torch.int32, device=dev)
         scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+        if pools is not None:
+            off, ent, qpool = pools
+            n_pools = len(off) - 1
+            d_off = torch.as_tensor(off, device=dev)
+            d_ent = torch.as_tensor(ent if len(ent) else np.zeros(1, dtype=np.int32), device=dev)
+            d_qpool = torch.as_tensor(qpool, device=dev)
+            nbytes = lib.skge_topk_pools_workspace_bytes(n, model.d, k, n_ent, n_pools)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            L.check(lib.skge_topk_pools(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), n_ent,
+                                        model.d, L.ptr(queries), n, direction, k, L.ptr(d_off),
+                                        L.ptr(d_ent), n_pools, L.ptr(d_qpool),
+                                        L.ptr(csr[0]) if csr else None,
+                                        L.ptr(csr[1]) if csr else None,
+                                        L.ptr(ws), nbytes, L.ptr(ents), L.ptr(scores)),
+                    "topk (pools)")
+            return ents.cpu().numpy().astype(np.int64), scores.cpu().numpy()
         nbytes = lib.skge_topk_workspace_bytes(n, model.d, k, n_ent)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         L.check(lib.skge_topk(L.stream_ptr(), code, L.ptr(E.data), L.ptr(rel.data), n_ent, model.d,
