@@ -939,6 +939,65 @@ int skge_topk_pools(void *stream, int model, const float *E, const float *R, int
                     const int *excl_off, const int *excl_ent,
                     void *workspace, size_t ws_bytes, int *ent_out, float *score_out);
 
+/* ---------------- link-prediction AUC and triple classification ---------------- */
+
+/*
+ * skge_score: the raw score of every explicit triple trip[i] = (s, o, p), the
+ * model's own training score before any activation:
+ *   SKGE_TRANSE_L1  -sum |E_s + R_p - E_o|      SKGE_TRANSE_L2  -sum (E_s + R_p - E_o)^2
+ *   SKGE_HOLE       R_p . ccorr(E_s, E_o)       SKGE_RESCAL     E_s W_p E_o   (R = W [M][d][d])
+ * Plain pointers: no table structs, no accumulators, nothing is updated.
+ * TransE and HolE take one wave per triple; RESCAL groups the triples by
+ * relation on the device and computes E_S W_p per group on the fp32 MFMA.
+ * Every sum has a fixed order and there are no float atomics: the same input
+ * gives the same bytes on every run.
+ *
+ * Refused before any launch, with an error text: a model outside 0 .. 3,
+ * n < 0 (or above INT_MAX / 4), N < 1, M < 1, d outside 1 .. 1024 (the step
+ * kernels' range), NULL pointers, a workspace below the workspace function's
+ * size.  n == 0 launches nothing.  The ids inside trip are NOT range-checked
+ * here (skge_amd checks them on the host).  Caller-owned buffers,
+ * stream-ordered.  The workspace function returns 0 for sizes it refuses.
+ */
+size_t skge_score_workspace_bytes(int model, int n, int M, int d);
+int skge_score(void *stream, int model, const float *E, const float *R, int N, int M, int d,
+               const int *trip, int64_t n, void *workspace, size_t ws_bytes, float *score_out);
+
+/*
+ * skge_curve_stats: ranking-curve statistics of n labelled scores (label > 0 =
+ * true), per segment seg[i] in 0 .. nseg - 1 (seg NULL: one segment).  Each
+ * segment is sorted descending by score and cut into groups of exactly equal
+ * score (-0.0 and +0.0 are one group, +-inf are legal).  With TP_k / FP_k the
+ * cumulative counts through group k (TP_0 = FP_0 = 0), P and Nneg the totals:
+ *   counts_out[4 s + 0 .. 3] = P, Nneg,
+ *                              2U = sum_k (FP_k - FP_k-1)(TP_k + TP_k-1)
+ *                                   (ROC-AUC = 2U / (2 P Nneg)),
+ *                              best_correct = max over cuts k >= 0 of
+ *                                             TP_k + (Nneg - FP_k);
+ *   areas_out[2 s + 0]       = sum_k (TP_k - TP_k-1) / P . (prec_k + prec_k-1) / 2,
+ *                              prec_k = TP_k / (TP_k + FP_k), prec_0 = 1: the
+ *                              trapezoid under the precision-recall points;
+ *   areas_out[2 s + 1]       = sum_k (TP_k - TP_k-1) / P . prec_k (average precision);
+ *   thresh_out[s]            = the score of the best cut's last group (the
+ *                              smallest k among equal maxima), +inf for cut 0
+ *                              ("predict none"); the rule is score >= thresh.
+ * The integers are exact.  The doubles use IEEE division and a summation tree
+ * fixed by (n, nseg): two runs give equal bytes.  An empty segment gives
+ * zeros, NaN areas and +inf; P == 0 or Nneg == 0 gives NaN areas.
+ *
+ * *status_out is cleared first, then: bit 1 = a NaN score, bit 2 = a segment
+ * id outside 0 .. nseg - 1.  With a bit set NO result is written.
+ *
+ * Refused before any launch: n < 0 (or above INT_MAX - 2048), nseg < 1, NULL
+ * pointers (score / label may be NULL when n == 0), a workspace below the
+ * workspace function's size (0 = sizes refused, or no device to size the sort
+ * for).  n == 0 is legal.  Caller-owned buffers, stream-ordered.
+ */
+size_t skge_curve_stats_workspace_bytes(int64_t n, int nseg);
+int skge_curve_stats(void *stream, const float *score, const signed char *label, const int *seg,
+                     int64_t n, int nseg, void *workspace, size_t ws_bytes,
+                     long long *counts_out, double *areas_out, float *thresh_out, int *status_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
+#include "skge_elem.h"
 #include "skge_host.h"
 #include "skge_stage.h"
 #include "skge_topk_list.h"
@@ -64,14 +65,8 @@ __global__ __launch_bounds__(128) void k_rel_query(RelQueryArgs a) {
       float v;
       if (dist) {
         v = eo[k] - es[k];
-      } else {   // ccorr(E_s, E_o)_k = sum_j E_s[j] E_o[(j+k) mod d] (k_rank_query's chain)
-        float c = 0.0f;
-        for (int j = 0; j < d; ++j) {
-          int ip = j + k;
-          ip -= ip >= d ? d : 0;
-          c = fmaf(es[j], eo[ip], c);
-        }
-        v = c;
+      } else {   // ccorr(E_s, E_o)_k (k_rank_query's chain)
+        v = ccorr_direct_k(es, eo, d, k);
       }
       q[k] = v;
       lq[k] = v;

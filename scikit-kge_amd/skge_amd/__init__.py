@@ -15,4 +15,6 @@ from .eval import (FilteredRankingEval, TransEEval, HolEEval, compute_scores, ra
 from .predict import LinkPredictor
 from .subgraphs import SUBTYPE, Subgraphs, SubgraphRankingEval, subgraph_ranking_scores
 from .neighbours import Neighbours, shared_role
+from .linkpred import (LinkPredictionEval, TripleClassifier, link_prediction_callback,
+                       score_triples, curve_stats)
 from .checkpoint import save_reference, load_reference, read_reference_state

@@ -99,6 +99,10 @@ SIGNATURES = {
     "skge_topk_pools_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     "skge_topk_pools": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p,
                               c_p, c_p, c_p, c_sz, c_p, c_p]),
+    "skge_score_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "skge_score": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_sz, c_p]),
+    "skge_curve_stats_workspace_bytes": (c_sz, [c_i64, c_i]),
+    "skge_curve_stats": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_sz, c_p, c_p, c_p, c_p]),
     "skge_pair_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "skge_triple_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, c_p, c_sz, c_p]),

@@ -204,6 +204,12 @@ class Model(object):
                                        L.ptr(out), None, None, None), "scores")
         return out
 
+    def score(self, triples):
+        """Raw training scores of explicit triples (s, o, p), array or list,
+        as a device fp32 tensor (skge_score; see linkpred.py)."""
+        from .linkpred import score_triples
+        return score_triples(self, triples)
+
     def _kernel_model(self):
         return self.model_code
 
