@@ -55,10 +55,12 @@ namespace skge {
 #endif
 
 // k_pipe_batch: the runners k_pipe_fused (below) does not take.  pipe_create's
-// r->fused is the rule: the fused kernel by default for one-GPU TransE with
-// batches of up to 16k slot records and rows of up to 64 floats
-// (SKGE_PIPE_FUSED=0 / 1 forces either, up to 256 floats); this kernel for
-// wider rows, larger batches and the data-parallel form.  nA apply workgroups
+// r->fused is the rule: the fused kernel for one-GPU TransE (not HolE, not the
+// data-parallel form) with batches of up to 16k slot records, fewer than 2^30
+// entity rows and, by default, rows of up to 64 floats; SKGE_PIPE_FUSED=1
+// extends it to rows of up to 256 floats, SKGE_PIPE_FUSED=0 turns it off.
+// This kernel takes everything else: wider rows (the flagship's d = 200),
+// larger batches, the data-parallel form.  nA apply workgroups
 // (dispatched first: they start the hand-offs the scoring waves may wait on),
 // then the scoring ones.
 // GRP: owner marks, GRP_ROWS owner rows per apply round trip.
@@ -66,8 +68,28 @@ namespace skge {
 // written); its own instance, so the one-GPU kernel keeps round 5's code (the
 // slice bounds and the record branch in the shared instance cost 10.45 ->
 // 11.15 us per launch, same box: VERDICT r05 item 4's A/B)
+//
+// Waves per SIMD of the WN18 one-GPU instances (KQ = 1, no owner marks, no hot
+// rows, not data-parallel), pinned so that an edit which adds or frees a
+// register cannot silently move them; 0 leaves it to the register count.
+// Measured at 5 / 6 / 7, same box, interleaved (profiles/pipe_regression/README.md):
+// int8 sums 1.069 / 1.008 / 0.992 ms per epoch (unpinned, 7 waves: 0.998-1.011),
+// int16 sums 1.091 / 1.045 / 0.995.  With int32x2 relation sums (W32) 7 waves
+// needs scratch, so those instances stay unpinned.
+#ifndef SKGE_PIPE_WAVES_I8
+#define SKGE_PIPE_WAVES_I8 7
+#endif
+#ifndef SKGE_PIPE_WAVES_I16
+#define SKGE_PIPE_WAVES_I16 7
+#endif
+constexpr int pipe_batch_waves(int kq, bool w32, bool e8, bool grp, bool hot, bool dp) {
+  return (kq != 1 || w32 || grp || hot || dp) ? 0 : (e8 ? SKGE_PIPE_WAVES_I8 : SKGE_PIPE_WAVES_I16);
+}
 template <int KQ, bool W32, bool E8, bool GRP = false, bool HOT = false, bool DP = false>
-__global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG) void k_pipe_batch(PipeArgs a) {
+__global__ __launch_bounds__(GRP ? PIPE_WG_GRP : SKGE_PIPE_WG)
+__attribute__((amdgpu_waves_per_eu(pipe_batch_waves(KQ, W32, E8, GRP, HOT, DP),
+                                   pipe_batch_waves(KQ, W32, E8, GRP, HOT, DP))))
+void k_pipe_batch(PipeArgs a) {
   const int wpb = blockDim.x >> 6;
   const int l = lane_id();
   const int d = a.d, nq = d >> 2;

@@ -5,6 +5,11 @@
 set -e
 name=$1; rev=$2; shift 2
 root="$(cd "$(dirname "$0")/.." && pwd)"
+if ! git -C "$root" rev-parse --git-dir > /dev/null 2>&1; then
+  echo "build_rev.sh: $root has no .git (a copied tree): build revisions on the build machine," >&2
+  echo "from a checkout with history, and carry the libraries over" >&2
+  exit 2
+fi
 tmp=$(mktemp -d)
 git -C "$root" archive "$rev" scikit-kge_amd/csrc include | tar -x -C "$tmp"
 out="$root/scikit-kge_amd/build_abl/$name"
