@@ -291,8 +291,6 @@ __global__ __launch_bounds__(256) void k_cs_final(const int* __restrict__ gTP,
   }
 }
 
-static size_t cs_align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // parts per segment: about 2048 workgroups, a function of nseg alone
 static int cs_parts(int nseg) { return std::max(1, std::min(256, (2048 + nseg - 1) / nseg)); }
 
@@ -321,7 +319,7 @@ static bool cs_layout(long long n, int nseg, CsLayout* L) {
   size_t o = 0;
   auto take = [&](size_t b) {
     const size_t at = o;
-    o += cs_align256(b);
+    o += align256(b);
     return at;
   };
   L->keys_a = take((size_t)n * 8);

@@ -38,6 +38,9 @@ void set_error(const char* fmt, ...);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// workspace parts start on 256-byte boundaries
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
 // registers per lane needed to hold a row of width d in the lane-strided
 // layout (see skge_device.h); 0 = unsupported
 inline int km_for(int d) {

@@ -31,8 +31,6 @@ constexpr int NB_TB = 128;            // table rows per LDS tile
 constexpr int NB_KC = 32;             // dims per LDS chunk
 constexpr int NB_PADT = NB_TB + 1;    // k-major images: a lane reads one dword, lanes along the rows
 
-typedef float nb_f32x16 __attribute__((ext_vector_type(16)));
-
 struct NbArgs {
   const float* T;
   const float* Q;        // [nq][d] or nullptr
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void k_nb_select(NbArgs a) {
   const int qi0 = wq * 32 * MI + (l & 31);     // + 32 mi: this lane's A rows
   const int tj0 = wt * 32 * NJ + (l & 31);     // + 32 nj: this lane's B columns
   for (int t0 = tbeg; t0 < tend; t0 += NB_TB) {
-    nb_f32x16 acc[MI][NJ];
+    f32x16 acc[MI][NJ];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll

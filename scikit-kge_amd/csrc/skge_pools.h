@@ -14,7 +14,7 @@
 
 namespace skge {
 
-constexpr int POOL_TILE = 128;   // candidate rows per LDS tile (EB2, TK_EB)
+constexpr int POOL_TILE = 128;   // candidate rows per LDS tile (RT_EB, TK_EB)
 
 struct PoolWork {
   const int4* items;         // (pool or -1, first slot of `order`, vectors, 0)

@@ -12,7 +12,7 @@
 //                      knows only the counts -- into a work list of items,
 //                      one block of up to 64 (or 32) vectors of one pool
 //                      (skge_pools.h)
-//   k_rank_count_pool  k_rank_count2's tile and micro-tile over one item x one
+//   k_rank_count_pool  the counting tile (skge_rank_tile.h) over one item x one
 //                      slice of its pool: Q rows through the order array,
 //                      candidate rows through pool_ent
 //   k_rank_known_pool  k_rank_known with a membership search: a known answer
@@ -23,6 +23,7 @@
 
 #include "skge_host.h"
 #include "skge_pools.h"
+#include "skge_rank_tile.h"
 #include "skge_topk_list.h"
 
 namespace skge {
@@ -81,8 +82,6 @@ __global__ __launch_bounds__(256) void k_pool_scatter(const int* __restrict__ ve
     order[atomicAdd(&bins[vec_pool[v] + 1], 1)] = v;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // every bin with a vector holds at most one partial block
 int pool_items_max(int nv, int n_pools, int bsz) {
   return (nv + bsz - 1) / bsz + (int)std::min<long long>(nv, (long long)n_pools + 1);
@@ -112,10 +111,7 @@ int launch_pool_group(hipStream_t st, const int* vec_pool, int nv, int n_pools, 
 }
 
 // ---- counting: one item (<= 64 vectors of one pool) x one slice of the pool ----
-constexpr int PQB = 64;            // query vectors per item
-constexpr int PEB = POOL_TILE;     // candidates per LDS tile
-constexpr int PKC = 32;            // dims per LDS chunk
-constexpr int PPADQ = PQB + 4, PPADE = PEB + 4;   // rows stay 16-B aligned
+static_assert(RT_EB == POOL_TILE, "a pool's slices are whole tiles of the counting pass");
 
 struct PoolRankArgs {
   const float* E;
@@ -126,16 +122,21 @@ struct PoolRankArgs {
   PoolWork pw;
 };
 
-// k_rank_count2's scheme (skge_eval.hip): thread = 8 candidates x 4 vectors,
-// every accumulator a sequential-k chain (the true score's arithmetic).  The
-// 64 Q rows come through the order array, candidate e of the pool is row
-// pool_ent[base + e] (pool -1: row e), loaded 16 B at a time along k.
+// the item's vectors through the order array (s_vec: their ids in LDS for the
+// tile's end); candidate e of the pool is row ent[e] (pool -1: row e)
+struct RankPoolRows {
+  const int* order;   // the item's first slot
+  int vcnt;
+  const int* ent;     // the pool's first entry, or nullptr
+  const int* s_vec;
+  __device__ __forceinline__ int vec(int i) const { return i < vcnt ? order[i] : -1; }
+  __device__ __forceinline__ int row(int e) const { return ent ? ent[e] : e; }
+  __device__ __forceinline__ int kept(int i) const { return s_vec[i]; }
+};
+
 template <bool L1>
 __global__ __launch_bounds__(256) void k_rank_count_pool(PoolRankArgs a) {
-  __shared__ __attribute__((aligned(16))) float sQ[PKC][PPADQ];
-  __shared__ __attribute__((aligned(16))) float sE[PKC][PPADE];
-  __shared__ int s_raw[PQB], s_vec[PQB];
-  __shared__ float s_tgt[PQB];
+  __shared__ int s_vec[RT_QB];
   if ((int)blockIdx.x >= *a.pw.n_items) return;
   const int4 item = a.pw.items[blockIdx.x];
   const int pool = item.x, vbeg = item.y, vcnt = item.z;
@@ -143,109 +144,10 @@ __global__ __launch_bounds__(256) void k_rank_count_pool(PoolRankArgs a) {
   int ebeg, eend;
   pool_slice(pool_size(a.pw, pool, a.N, base), a.pw.ns, blockIdx.y, ebeg, eend);
   if (ebeg >= eend) return;
-  const int tid = threadIdx.x, d = a.d;
-  if (tid < PQB) {
-    const int v = tid < vcnt ? a.pw.order[vbeg + tid] : -1;
-    s_vec[tid] = v;
-    s_tgt[tid] = v >= 0 ? a.tgt[v] : INFINITY;
-    s_raw[tid] = 0;
-  }
-  const int te = (tid & 15) * 8, tq = (tid >> 4) * 4;
-  int raw[4] = {0, 0, 0, 0};
-  // staging maps: Q chunk = 64 vectors x 8 float4 (2 per thread), candidate
-  // chunk = 128 rows x 8 float4 (4 per thread); k fastest in global memory
-  const int sq_v = tid >> 2, sq_k = (tid & 3) * 4;          // + 16 for the second float4
-  const int se_e = tid >> 1, se_k = (tid & 1) * 4;          // + 8, 16, 24
-  const int qv_id = sq_v < vcnt ? a.pw.order[vbeg + sq_v] : -1;
-  const float* qrow = a.Q + (size_t)(qv_id >= 0 ? qv_id : 0) * d;
-  for (int e0 = ebeg; e0 < eend; e0 += PEB) {
-    float acc[8][4];
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-#pragma unroll
-      for (int y = 0; y < 4; ++y) acc[x][y] = 0.0f;
-    const int e = e0 + se_e;
-    const int row = e < eend ? (pool >= 0 ? a.pw.pool_ent[base + e] : e) : 0;
-    const float* erow = a.E + (size_t)row * d;
-    for (int k0 = 0; k0 < d; k0 += PKC) {
-      float4 qa[2], ea[4];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int k = k0 + sq_k + 16 * u;
-        float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (qv_id >= 0) {
-          if ((d & 3) == 0 && k + 3 < d) {
-            x = *reinterpret_cast<const float4*>(qrow + k);
-          } else {
-            x.x = k < d ? qrow[k] : 0.0f;
-            x.y = k + 1 < d ? qrow[k + 1] : 0.0f;
-            x.z = k + 2 < d ? qrow[k + 2] : 0.0f;
-            x.w = k + 3 < d ? qrow[k + 3] : 0.0f;
-          }
-        }
-        qa[u] = x;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = k0 + se_k + 8 * u;
-        float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (e < eend) {
-          if ((d & 3) == 0 && k + 3 < d) {
-            x = *reinterpret_cast<const float4*>(erow + k);
-          } else {
-            x.x = k < d ? erow[k] : 0.0f;
-            x.y = k + 1 < d ? erow[k + 1] : 0.0f;
-            x.z = k + 2 < d ? erow[k + 2] : 0.0f;
-            x.w = k + 3 < d ? erow[k + 3] : 0.0f;
-          }
-        }
-        ea[u] = x;
-      }
-      __syncthreads();   // the previous chunk's reads are done
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int k = sq_k + 16 * u;
-        sQ[k][sq_v] = qa[u].x;
-        sQ[k + 1][sq_v] = qa[u].y;
-        sQ[k + 2][sq_v] = qa[u].z;
-        sQ[k + 3][sq_v] = qa[u].w;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = se_k + 8 * u;
-        sE[k][se_e] = ea[u].x;
-        sE[k + 1][se_e] = ea[u].y;
-        sE[k + 2][se_e] = ea[u].z;
-        sE[k + 3][se_e] = ea[u].w;
-      }
-      __syncthreads();
-      const int kn = min(PKC, d - k0);
-      for (int k = 0; k < kn; ++k) {
-        const float4 e4a = *reinterpret_cast<const float4*>(&sE[k][te]);
-        const float4 e4b = *reinterpret_cast<const float4*>(&sE[k][te + 4]);
-        const float4 q4 = *reinterpret_cast<const float4*>(&sQ[k][tq]);
-        const float ev[8] = {e4a.x, e4a.y, e4a.z, e4a.w, e4b.x, e4b.y, e4b.z, e4b.w};
-        const float qv[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-#pragma unroll
-          for (int y = 0; y < 4; ++y)
-            acc[x][y] = L1 ? acc[x][y] - fabsf(qv[y] - ev[x]) : fmaf(ev[x], qv[y], acc[x][y]);
-      }
-    }
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      const float t = s_tgt[tq + y];
-#pragma unroll
-      for (int x = 0; x < 8; ++x)
-        if (e0 + te + x < eend && acc[x][y] > t) ++raw[y];
-    }
-  }
-#pragma unroll
-  for (int y = 0; y < 4; ++y)
-    if (raw[y]) atomicAdd(&s_raw[tq + y], raw[y]);
-  __syncthreads();
-  if (tid < PQB && s_vec[tid] >= 0 && s_raw[tid]) atomicAdd(a.raw + s_vec[tid], s_raw[tid]);
+  const RankPoolRows m = {a.pw.order + vbeg, vcnt, pool >= 0 ? a.pw.pool_ent + base : nullptr,
+                          s_vec};
+  if (threadIdx.x < RT_QB) s_vec[threadIdx.x] = m.vec(threadIdx.x);
+  rank_count_tile<L1>(a.E, a.d, a.Q, a.tgt, a.raw, ebeg, eend, m);
 }
 
 // e is an entry of the ascending list p[0 .. n)
@@ -313,7 +215,7 @@ static bool pool_sizes_ok(int nq, int d, int n_pools) {
 extern "C" size_t skge_rank_pools_workspace_bytes(int nq, int d, int n_pools) {
   if (!pool_sizes_ok(nq, d, n_pools)) return 0;
   return align256((size_t)2 * nq * d * sizeof(float)) + 2 * align256((size_t)2 * nq * sizeof(float)) +
-         pool_group_bytes(2 * nq, n_pools, PQB) + 256;
+         pool_group_bytes(2 * nq, n_pools, RT_QB) + 256;
 }
 
 extern "C" int skge_rank_pools(void* stream, int model, const float* E, const float* R, int N,
@@ -348,11 +250,11 @@ extern "C" int skge_rank_pools(void* stream, int model, const float* E, const fl
   a.Q = Q;
   a.tgt = tgt;
   a.raw = raw;
-  const int rc = launch_pool_group(st, vec_pool, nv, n_pools, PQB, pool_off, pool_ent, gws, &a.pw);
+  const int rc = launch_pool_group(st, vec_pool, nv, n_pools, RT_QB, pool_off, pool_ent, gws, &a.pw);
   if (rc != SKGE_OK) return rc;
   launch_rank_query(st, model, E, R, N, d, queries, nq, Q, tgt);
   const bool l1 = model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2;
-  const int max_items = pool_items_max(nv, n_pools, PQB);
+  const int max_items = pool_items_max(nv, n_pools, RT_QB);
   a.pw.ns = pool_slices(max_items, N);
   const dim3 grid(max_items, a.pw.ns);
   const int kb = (nv + 255) / 256;

@@ -11,9 +11,8 @@
 //                    score by rank_score (the counting pass's chain)
 //   then launch_rank_count + k_rel_known, or launch_topk_select, over R.
 // RESCAL's E_s W_j E_o has no such vector:
-//   k_rel_rescal     workgroup = QB pairs x a few relations: T = E_S W_j on
-//                    v_mfma_f32_32x32x2_f32 in column tiles of 32, then
-//                    sum_b T[q][b] E_o[q][b] in a fixed order; one fp32 per
+//   k_rel_rescal     workgroup = QB pairs x a few relations: the MFMA score
+//                    tile (skge_rescal_tile.h) once per relation; one fp32 per
 //                    (pair, relation) into a score matrix [nq][M]
 //   k_rel_rank_rows  one wave per pair: relations strictly above sc[q][p], less
 //                    the known ones above it
@@ -22,11 +21,10 @@
 // exact tie is an exact tie.  No float atomics: the same bits on every run.
 #include <algorithm>
 #include <stdlib.h>
-#include <type_traits>
 
 #include "skge_elem.h"
 #include "skge_host.h"
-#include "skge_stage.h"
+#include "skge_rescal_tile.h"
 #include "skge_topk_list.h"
 
 namespace skge {
@@ -101,12 +99,6 @@ __global__ __launch_bounds__(256) void k_rel_known(const float* __restrict__ R, 
 }
 
 // ---- RESCAL: the score matrix ----
-constexpr int RR_CB = 128;            // columns of W_j per pass: 4 waves x one 32-column MFMA tile
-constexpr int RR_KC = 32;             // rows of W_j (dims of E_s) per LDS chunk
-constexpr int RR_PADW = RR_CB + 1;    // k-major images with odd strides (k_nb_select's)
-
-typedef float rr_f32x16 __attribute__((ext_vector_type(16)));
-
 struct RelRescalArgs {
   const float* E;
   const float* W;       // [M][d][d]
@@ -117,25 +109,14 @@ struct RelRescalArgs {
   float* S;             // [nq][M]
 };
 
-// A = the block's E_s rows, B = W_j: lane l feeds A[q = l & 31][a = l >> 5] and
-// B[a = l >> 5][b = l & 31] and holds T[q = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)]
-// [b = l & 31] (k_nb_select's layout).  Wave w owns columns b0 + 32 w .. + 31 of
-// every 128-column pass and all QB / 32 row tiles.  Per element the chain over
-// a = 0 .. d - 1 from 0.0f is the MFMA's; the chunk's zero padding adds +0.
-// The reduction over b, fixed: a lane folds its column of every pass into one
-// partial (fma, passes ascending), the 32 lanes of a half-wave add by the xor
-// butterfly 16, 8, 4, 2, 1, and the four waves' sums are added in wave order.
-// LDS 16.5 (QB 128) + 16.5 KB staging + 2.5 KB.
+// workgroup = QB pairs x relations j0 .. j1 - 1, the score tile
+// (skge_rescal_tile.h) once per relation.  LDS: the tile's + 2.5 KB.
 template <int QB>
 __global__ __launch_bounds__(256, 2) void k_rel_rescal(RelRescalArgs a) {
   constexpr int MI = QB / 32;
-  constexpr int PADQ = QB + 1;
-  __shared__ float sA[RR_KC * PADQ];
-  __shared__ float sW[RR_KC * RR_PADW];
   __shared__ int s_s[QB], s_o[QB];
   __shared__ float s_red[4][QB];
   const int tid = threadIdx.x, d = a.d;
-  const int l = tid & 63, w = tid >> 6, h = l >> 5;
   const int v0 = blockIdx.x * QB;
   for (int i = tid; i < QB; i += 256) {
     const int v = v0 + i;
@@ -144,125 +125,15 @@ __global__ __launch_bounds__(256, 2) void k_rel_rescal(RelRescalArgs a) {
     s_o[i] = ok ? a.queries[(size_t)a.stride * v + 1] : 0;
   }
   __syncthreads();
-  // staging.  E_s: row (tid >> 3) + 32 u of the block, dims 4 (tid & 7) .. + 3
-  // of the chunk.  W_j: row (tid >> 5) + 8 u of the chunk, columns
-  // 4 (tid & 31) .. + 3 of the pass (b is the fastest index in memory).
-  const int st_r = tid >> 3, st_k = (tid & 7) * 4;
-  const int sw_r = tid >> 5, sw_c = (tid & 31) * 4;
-  const float* erow[MI];
   bool eok[MI];
 #pragma unroll
-  for (int u = 0; u < MI; ++u) {
-    const int i = st_r + 32 * u;
-    eok[u] = v0 + i < a.nq;
-    erow[u] = a.E + (size_t)s_s[i] * d;
-  }
-  const bool vec = (d & 3) == 0;
-  const int qi0 = l & 31;              // + 32 mi: this lane's A rows
-  const int tj0 = 32 * w + (l & 31);   // this lane's B column of the pass
+  for (int u = 0; u < MI; ++u) eok[u] = v0 + (tid >> 3) + 32 * u < a.nq;
   const int j0 = blockIdx.y * a.rper;
   const int j1 = a.M - j0 < a.rper ? a.M : j0 + a.rper;
   for (int j = j0; j < j1; ++j) {
-    const float* Wj = a.W + (size_t)j * d * d;
-    float part[MI][16];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) part[mi][r] = 0.0f;
-    for (int b0 = 0; b0 < d; b0 += RR_CB) {
-      const bool active = b0 + 32 * w < d;   // wave-uniform: the tile has a column of W_j
-      rr_f32x16 acc[MI];
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mi][r] = 0.0f;
-      for (int k0 = 0; k0 < d; k0 += RR_KC) {
-        float4 ea[MI], wa[4];
-        auto load = [&](auto v4) {
-          constexpr bool VEC = decltype(v4)::value;
-#pragma unroll
-          for (int u = 0; u < MI; ++u) ea[u] = stage_load4<VEC>(erow[u], eok[u], k0 + st_k, d);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int ar = k0 + sw_r + 8 * u;
-            wa[u] = stage_load4<VEC>(Wj + (size_t)(ar < d ? ar : 0) * d, ar < d, b0 + sw_c, d);
-          }
-        };
-        if (vec)
-          load(std::true_type());
-        else
-          load(std::false_type());
-        __syncthreads();   // the previous chunk's reads are done
-#pragma unroll
-        for (int u = 0; u < MI; ++u) {
-          float* p = sA + st_k * PADQ + st_r + 32 * u;
-          p[0] = ea[u].x;
-          p[PADQ] = ea[u].y;
-          p[2 * PADQ] = ea[u].z;
-          p[3 * PADQ] = ea[u].w;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float* p = sW + (sw_r + 8 * u) * RR_PADW + sw_c;
-          p[0] = wa[u].x;
-          p[1] = wa[u].y;
-          p[2] = wa[u].z;
-          p[3] = wa[u].w;
-        }
-        __syncthreads();
-        if (active) {
-          // two dims per MFMA; an odd tail's second dim is the chunk's zero
-          // padding.  The next step's operands are read while this step's
-          // MFMAs run (the last step reads its own again).
-          const int steps = (min(RR_KC, d - k0) + 1) >> 1;
-          float av[MI], bv;
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) av[mi] = sA[h * PADQ + qi0 + 32 * mi];
-          bv = sW[h * RR_PADW + tj0];
-          for (int s = 0; s < steps; ++s) {
-            const int kn = 2 * min(s + 1, steps - 1) + h;
-            float an[MI], bn;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) an[mi] = sA[kn * PADQ + qi0 + 32 * mi];
-            bn = sW[kn * RR_PADW + tj0];
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi], bv, acc[mi], 0, 0, 0);
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) av[mi] = an[mi];
-            bv = bn;
-          }
-        }
-      }
-      if (active) {   // this pass's column of T times E_o[b]
-        const int b = b0 + tj0;
-        const bool bok = b < d;
-        const int bc = bok ? b : 0;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int qi = 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const float eo = a.E[(size_t)s_o[qi] * d + bc];
-            part[mi][r] = fmaf(acc[mi][r], bok ? eo : 0.0f, part[mi][r]);
-          }
-      }
-    }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float x = part[mi][r];
-#pragma unroll
-        for (int off = 16; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-        if ((l & 31) == 0) s_red[w][32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h] = x;
-      }
-    __syncthreads();
-    // (the next relation's staging barriers come between these reads and the
-    // next writes of s_red)
+    rescal_score_tile<QB>(a.E, a.W + (size_t)j * d * d, d, s_s, s_o, eok, s_red);
     if (tid < QB && v0 + tid < a.nq)
-      a.S[(size_t)(v0 + tid) * a.M + j] =
-          ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+      a.S[(size_t)(v0 + tid) * a.M + j] = rescal_row_sum<QB>(s_red, tid);
   }
 }
 
@@ -324,8 +195,6 @@ __global__ __launch_bounds__(256) void k_rel_topk_rows(const float* __restrict__
     so[64 + l] = hi ? key_score(hi) : -INFINITY;
   }
 }
-
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // RESCAL: pairs per pass of the entry points, so that the score matrix stays
 // within REL_SCORE_BYTES (SKGE_REL_SCORE_BYTES overrides it: the tests run a

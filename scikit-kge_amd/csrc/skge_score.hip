@@ -13,22 +13,19 @@
 //                     folded with R_p per lane, then the wave sum
 //   k_score_rescal    RESCAL: the triples are grouped by relation on the device
 //                     (launch_pool_group: histogram, scan, scatter); an item is
-//                     up to QB triples of ONE relation, T = E_S W_p on
-//                     v_mfma_f32_32x32x2_f32 in column tiles of 32 and
-//                     sum_b T[q][b] E_o[q][b] in k_rel_rescal's fixed order.
-//                     A triple's score does not depend on its place in the
-//                     item (row q of the MFMA reads only row q of A), so the
-//                     scatter's order does not reach the bits.
+//                     up to QB triples of ONE relation, scored by the MFMA
+//                     score tile (skge_rescal_tile.h, k_rel_rescal's too).  A
+//                     triple's score does not depend on its place in the item,
+//                     so the scatter's order does not reach the bits.
 // No float atomics anywhere: the same input gives the same bytes.
 #include <algorithm>
 #include <limits.h>
-#include <type_traits>
 
 #include "skge_elem.h"
 #include "skge_host.h"
 #include "skge_hole.h"
 #include "skge_pools.h"
-#include "skge_stage.h"
+#include "skge_rescal_tile.h"
 #include "skge_transe_l1.h"
 
 namespace skge {
@@ -140,12 +137,6 @@ __global__ __launch_bounds__(256) void k_score_hole(ScoreArgs a) {
 }
 
 // ---- RESCAL ----
-constexpr int SR_CB = 128;            // columns of W_p per pass: 4 waves x one 32-column MFMA tile
-constexpr int SR_KC = 32;             // rows of W_p (dims of E_s) per LDS chunk
-constexpr int SR_PADW = SR_CB + 1;
-
-typedef float sr_f32x16 __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(256) void k_score_rel(const int* __restrict__ trip, int n,
                                                    int* __restrict__ rel) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
@@ -161,20 +152,12 @@ struct ScoreRescalArgs {
   PoolWork pw;       // items: (relation, first slot of order, triples, 0)
 };
 
-// k_rel_rescal's tile (skge_relation.hip) over one item: A = the item's E_s
-// rows through the order array, B = W_p of the item's relation.  Lane l feeds
-// A[q = l & 31][a = l >> 5] and B[a = l >> 5][b = l & 31] and holds
-// T[q = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][b = l & 31]; wave w owns columns
-// b0 + 32 w .. + 31 of every pass.  The sum over b: a lane folds its column of
-// every pass into one partial (fma, passes ascending), the 32 lanes of a
-// half-wave add by the xor butterfly 16 .. 1, the four waves' sums in wave
-// order.  Rows past the item's count read entity 0 and are never written.
+// the score tile (skge_rescal_tile.h) over one item: the item's (s, o) rows
+// through the order array, W_p of the item's relation.  Rows past the item's
+// count read entity 0 and are never written.
 template <int QB>
 __global__ __launch_bounds__(256, 2) void k_score_rescal(ScoreRescalArgs a) {
   constexpr int MI = QB / 32;
-  constexpr int PADQ = QB + 1;
-  __shared__ float sA[SR_KC * PADQ];
-  __shared__ float sW[SR_KC * SR_PADW];
   __shared__ int s_s[QB], s_o[QB], s_v[QB];
   __shared__ float s_red[4][QB];
   if ((int)blockIdx.x >= *a.pw.n_items) return;
@@ -185,7 +168,6 @@ __global__ __launch_bounds__(256, 2) void k_score_rescal(ScoreRescalArgs a) {
   const int rel = item.x, vbeg = item.y, vcnt = item.z;
 #endif
   const int tid = threadIdx.x, d = a.d;
-  const int l = tid & 63, w = tid >> 6, h = l >> 5;
   for (int i = tid; i < QB; i += 256) {
     const int v = i < vcnt ? a.pw.order[vbeg + i] : -1;
     s_v[i] = v;
@@ -193,116 +175,12 @@ __global__ __launch_bounds__(256, 2) void k_score_rescal(ScoreRescalArgs a) {
     s_o[i] = v >= 0 ? a.trip[3 * (size_t)v + 1] : 0;
   }
   __syncthreads();
-  const int st_r = tid >> 3, st_k = (tid & 7) * 4;
-  const int sw_r = tid >> 5, sw_c = (tid & 31) * 4;
-  const float* erow[MI];
   bool eok[MI];
 #pragma unroll
-  for (int u = 0; u < MI; ++u) {
-    const int i = st_r + 32 * u;
-    eok[u] = i < vcnt;
-    erow[u] = a.E + (size_t)s_s[i] * d;
-  }
-  const bool vec = (d & 3) == 0;
-  const int qi0 = l & 31;
-  const int tj0 = 32 * w + (l & 31);
-  const float* Wj = a.W + (size_t)rel * d * d;
-  float part[MI][16];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) part[mi][r] = 0.0f;
-  for (int b0 = 0; b0 < d; b0 += SR_CB) {
-    const bool active = b0 + 32 * w < d;   // wave-uniform
-    sr_f32x16 acc[MI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][r] = 0.0f;
-    for (int k0 = 0; k0 < d; k0 += SR_KC) {
-      float4 ea[MI], wa[4];
-      auto load = [&](auto v4) {
-        constexpr bool VEC = decltype(v4)::value;
-#pragma unroll
-        for (int u = 0; u < MI; ++u) ea[u] = stage_load4<VEC>(erow[u], eok[u], k0 + st_k, d);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int ar = k0 + sw_r + 8 * u;
-          wa[u] = stage_load4<VEC>(Wj + (size_t)(ar < d ? ar : 0) * d, ar < d, b0 + sw_c, d);
-        }
-      };
-      if (vec)
-        load(std::true_type());
-      else
-        load(std::false_type());
-      __syncthreads();   // the previous chunk's reads are done
-#pragma unroll
-      for (int u = 0; u < MI; ++u) {
-        float* p = sA + st_k * PADQ + st_r + 32 * u;
-        p[0] = ea[u].x;
-        p[PADQ] = ea[u].y;
-        p[2 * PADQ] = ea[u].z;
-        p[3 * PADQ] = ea[u].w;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float* p = sW + (sw_r + 8 * u) * SR_PADW + sw_c;
-        p[0] = wa[u].x;
-        p[1] = wa[u].y;
-        p[2] = wa[u].z;
-        p[3] = wa[u].w;
-      }
-      __syncthreads();
-      if (active) {
-        const int steps = (min(SR_KC, d - k0) + 1) >> 1;
-        float av[MI], bv;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) av[mi] = sA[h * PADQ + qi0 + 32 * mi];
-        bv = sW[h * SR_PADW + tj0];
-        for (int s = 0; s < steps; ++s) {
-          const int kn = 2 * min(s + 1, steps - 1) + h;
-          float an[MI], bn;
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) an[mi] = sA[kn * PADQ + qi0 + 32 * mi];
-          bn = sW[kn * SR_PADW + tj0];
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi)
-            acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi], bv, acc[mi], 0, 0, 0);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) av[mi] = an[mi];
-          bv = bn;
-        }
-      }
-    }
-    if (active) {   // this pass's column of T times E_o[b]
-      const int b = b0 + tj0;
-      const bool bok = b < d;
-      const int bc = bok ? b : 0;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int qi = 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const float eo = a.E[(size_t)s_o[qi] * d + bc];
-          part[mi][r] = fmaf(acc[mi][r], bok ? eo : 0.0f, part[mi][r]);
-        }
-    }
-  }
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float x = part[mi][r];
-#pragma unroll
-      for (int off = 16; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-      if ((l & 31) == 0) s_red[w][32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h] = x;
-    }
-  __syncthreads();
-  if (tid < QB && s_v[tid] >= 0)
-    a.out[s_v[tid]] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+  for (int u = 0; u < MI; ++u) eok[u] = (tid >> 3) + 32 * u < vcnt;
+  rescal_score_tile<QB>(a.E, a.W + (size_t)rel * d * d, d, s_s, s_o, eok, s_red);
+  if (tid < QB && s_v[tid] >= 0) a.out[s_v[tid]] = rescal_row_sum<QB>(s_red, tid);
 }
-
-static size_t sc_align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // triples per item: wide items when the average relation fills them
 static int score_rescal_qb(int n, int M) { return (long long)n >= 64ll * M ? 128 : 32; }
@@ -318,7 +196,7 @@ using namespace skge;
 extern "C" size_t skge_score_workspace_bytes(int model, int n, int M, int d) {
   if (!score_sizes_ok(model, n, M, d)) return 0;
   if (model != SKGE_RESCAL || n == 0) return 256;   // unused; never 0 for good sizes
-  return sc_align256((size_t)n * sizeof(int)) + pool_group_bytes(n, M, score_rescal_qb(n, M)) + 512;
+  return align256((size_t)n * sizeof(int)) + pool_group_bytes(n, M, score_rescal_qb(n, M)) + 512;
 }
 
 extern "C" int skge_score(void* stream, int model, const float* E, const float* R, int N, int M,
@@ -380,7 +258,7 @@ extern "C" int skge_score(void* stream, int model, const float* E, const float* 
   }
   char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   int* rel = (int*)ws;
-  void* gws = ws + sc_align256((size_t)n * sizeof(int));
+  void* gws = ws + align256((size_t)n * sizeof(int));
   const int qb = score_rescal_qb((int)n, M);
   const int eb = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048));
   hipLaunchKernelGGL(k_score_rel, dim3(eb), dim3(256), 0, st, trip, (int)n, rel);

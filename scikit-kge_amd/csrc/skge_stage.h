@@ -1,8 +1,12 @@
-// Staging loads of the MFMA kernels (skge_neighbours.hip, skge_relation.hip).
+// Staging loads and the accumulator type of the fp32 MFMA kernels
+// (skge_neighbours.hip, skge_rescal_tile.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace skge {
+
+// the 16 accumulators a lane holds of a v_mfma_f32_32x32x2_f32 tile
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // four dims kk .. kk + 3 of a row, zeros past d and for a row past the end
 // (ok false; row is then any readable row).  Every load is issued, from a

@@ -107,6 +107,54 @@ def test_scores_float_tables_within_oracle_bar(model, d):
     assert got.tobytes() == again.tobytes()          # two runs, equal bytes
 
 
+def _reltopk_all(E, R, pairs):
+    """skge_reltopk (RESCAL) with k = M and no exclusions: the score of every
+    relation for every (s, o) pair, [nq][M] by relation id."""
+    from skge_amd import _lib as L
+    lib = L.load()
+    Et = torch.as_tensor(E, dtype=torch.float32, device=DEV).contiguous()
+    Rt = torch.as_tensor(R, dtype=torch.float32, device=DEV).contiguous()
+    q = torch.as_tensor(np.ascontiguousarray(pairs, dtype=np.int32), device=DEV)
+    nq, d, M = len(pairs), E.shape[1], R.shape[0]
+    code = LR.MODEL_CODE["rescal"]
+    nb = int(lib.skge_reltopk_workspace_bytes(nq, d, M, M, code))
+    assert nb > 0
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    ids = torch.full((nq, M), -7, dtype=torch.int32, device=DEV)
+    val = torch.full((nq, M), float("nan"), dtype=torch.float32, device=DEV)
+    L.check(lib.skge_reltopk(L.stream_ptr(), code, L.ptr(Et), L.ptr(Rt), E.shape[0], M, d, L.ptr(q),
+                             nq, M, None, None, L.ptr(ws), nb, L.ptr(ids), L.ptr(val)), "reltopk")
+    ids, val = ids.cpu().numpy(), val.cpu().numpy()
+    assert (np.sort(ids, axis=1) == np.arange(M)).all()      # every relation once
+    out = np.empty((nq, M), dtype=np.float32)
+    np.put_along_axis(out, ids, val, axis=1)
+    return out
+
+
+# (d, M, nq): scalar-tail staging, one partial column tile, a partial last row
+# block / the vector path, exactly two 32-column tiles / two 128-column passes
+# with a 2-column second pass, one live row
+@pytest.mark.parametrize("d,M,nq", [(33, 5, 70), (64, 3, 33), (130, 4, 1)])
+def test_rescal_score_and_reltopk_share_their_bits(d, M, nq):
+    """k_score_rescal and k_rel_rescal run one score tile (skge_rescal_tile.h):
+    the score of (s, o, p_j) is bit-equal from skge_score and from skge_reltopk,
+    whatever block width, row place and relation grouping either picks."""
+    rs = np.random.RandomState(1000 * d + nq)
+    N = 40
+    b = np.sqrt(6.0) / np.sqrt(2 * d)
+    E = rs.uniform(-b, b, size=(N, d)).astype(np.float32)
+    R = rs.uniform(-b, b, size=(M, d, d)).astype(np.float32)
+    pairs = rs.randint(0, N, size=(nq, 2)).astype(np.int32)
+    mat = _reltopk_all(E, R, pairs)
+    trip = np.concatenate([np.repeat(pairs, M, axis=0),
+                           np.tile(np.arange(M, dtype=np.int32), nq)[:, None]], axis=1)
+    got = _score("rescal", E, R, trip).reshape(nq, M)
+    assert (got != 0).all()           # the top-k key holds -0 as +0: no score is a zero
+    bad = int((got.view(np.int32) != mat.view(np.int32)).sum())
+    print("d=%d M=%d nq=%d mismatches=%d of %d" % (d, M, nq, bad, nq * M))
+    assert bad == 0, (got[:2], mat[:2])
+
+
 def _curve(scores, labels, seg, nseg):
     """skge_curve_stats through the C ABI; (status, counts, areas, thresh)."""
     from skge_amd import _lib as L

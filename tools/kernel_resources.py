@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
-"""Register and occupancy report of the pipelined runners' kernels (CPU only).
+"""Register, LDS and occupancy report of kernels (CPU only).
 
-Compiles skge_pipeline.hip and skge_hole_pipe.hip device-only with the
-Makefile's flags plus -Rpass-analysis=kernel-resource-usage and prints, as
-JSON, the VGPRs, SGPRs, spilled SGPRs / VGPRs, scratch bytes and waves per SIMD
-of every k_pipe_batch, k_pipe_fused and k_hole_pipe instance, followed by a
-diff against profiles/pipe_regression/resources.json ("head" entry).  It reads
-the compiler's remarks only; nothing runs on a GPU.
+Compiles the sources device-only with the Makefile's flags plus
+-Rpass-analysis=kernel-resource-usage and prints, as JSON, the VGPRs, SGPRs,
+spilled SGPRs / VGPRs, scratch bytes, LDS bytes and waves per SIMD of every
+instance of the kernels, followed by a diff against the "head" entry of a
+record file (the fields that the record holds).  By default: skge_pipeline.hip
+and skge_hole_pipe.hip, every k_pipe_batch, k_pipe_fused and k_hole_pipe
+instance, against profiles/pipe_regression/resources.json.  It reads the
+compiler's remarks only; nothing runs on a GPU.
 
-Usage: tools/kernel_resources.py [--csrc DIR] [--write FILE] [-- extra hipcc flags]
-  --csrc DIR    another tree's csrc/ (e.g. an exported revision)
-  --write FILE  also write the report to FILE
+Usage: tools/kernel_resources.py [--csrc DIR] [--sources A.hip,B.hip] [--kernels K1,K2]
+                                 [--record FILE] [--write FILE] [-- extra hipcc flags]
+  --csrc DIR     another tree's csrc/ (e.g. an exported revision)
+  --sources ...  the files of csrc/ to compile
+  --kernels ...  the kernel names (without template arguments) to report
+  --record FILE  the record to diff against
+  --write FILE   also write the report to FILE
 """
 import argparse
 import json
@@ -26,7 +32,7 @@ SOURCES = ("skge_pipeline.hip", "skge_hole_pipe.hip")
 KERNELS = ("k_pipe_batch", "k_pipe_fused", "k_hole_pipe")
 FIELDS = {"SGPRs": "sgprs", "TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch_bytes",
           "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spills",
-          "VGPRs Spill": "vgpr_spills"}
+          "VGPRs Spill": "vgpr_spills", "LDS Size [bytes/block]": "lds_bytes"}
 
 
 def makefile_flags():
@@ -68,10 +74,10 @@ def remarks(src, hipcc, flags, extra):
     return out
 
 
-def report(csrc, extra=()):
+def report(csrc, extra=(), sources=SOURCES, kernels=KERNELS):
     hipcc, flags = makefile_flags()
     res = {}
-    for s in SOURCES:
+    for s in sources:
         path = os.path.join(csrc, s)
         if not os.path.exists(path):
             continue
@@ -80,7 +86,7 @@ def report(csrc, extra=()):
         for mangled, r in rm.items():
             name = names[mangled]
             m = re.match(r"^(?:void )?skge::(\w+)(<.*>)?\(", name)
-            if m and m.group(1) in KERNELS:
+            if m and m.group(1) in kernels:
                 res[m.group(1) + (m.group(2) or "")] = r
     return dict(sorted(res.items()))
 
@@ -93,8 +99,8 @@ def diff(new, old):
         elif k not in new:
             out[k] = "gone"
         else:
-            ch = {f: [old[k].get(f), new[k].get(f)] for f in FIELDS.values()
-                  if old[k].get(f) != new[k].get(f)}
+            ch = {f: [old[k][f], new[k].get(f)] for f in FIELDS.values()
+                  if f in old[k] and old[k][f] != new[k].get(f)}
             if ch:
                 out[k] = ch
     return out
@@ -108,12 +114,15 @@ def main():
         argv = argv[:argv.index("--")]
     ap = argparse.ArgumentParser()
     ap.add_argument("--csrc", default=os.path.join(PKG, "csrc"))
+    ap.add_argument("--sources", default=",".join(SOURCES))
+    ap.add_argument("--kernels", default=",".join(KERNELS))
+    ap.add_argument("--record", default=RECORD)
     ap.add_argument("--write", default=None)
     args = ap.parse_args(argv)
-    res = report(args.csrc, extra)
+    res = report(args.csrc, extra, args.sources.split(","), args.kernels.split(","))
     out = {"resources": res}
-    if os.path.exists(RECORD):
-        rec = json.load(open(RECORD))
+    if os.path.exists(args.record):
+        rec = json.load(open(args.record))
         out["diff_against_record"] = diff(res, rec.get("head", {}))   # [recorded, now]
     txt = json.dumps(out, indent=1)
     print(txt)
