@@ -1,9 +1,12 @@
 // Small per-element pieces of the scores, stated once for the kernels that
 // score without a gradient: skge_score.hip (every TransE form but the L1 quad
 // layout, which goes through skge_transe_l1.h; HolE outside the quad kernels)
-// and k_rel_query (skge_relation.hip).
+// and the query-vector kernels of the evaluation entry points (k_rank_query,
+// skge_eval.hip; k_topk_query, skge_topk.hip; k_rel_query, skge_relation.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "../../include/skge_hip.h"
 
 namespace skge {
 
@@ -24,6 +27,35 @@ __device__ __forceinline__ float ccorr_direct_k(const float* a, const float* b, 
     ip -= ip >= d ? d : 0;
     c = fmaf(a[j], b[ip], c);
   }
+  return c;
+}
+
+// cconv(a, b)_k = sum_j a[j] b[(k - j) mod d], the same chain
+__device__ __forceinline__ float cconv_direct_k(const float* a, const float* b, int d, int k) {
+  float c = 0.0f;
+  for (int j = 0; j < d; ++j) {
+    int im = k - j;
+    im += im < 0 ? d : 0;
+    c = fmaf(a[j], b[im], c);
+  }
+  return c;
+}
+
+// Dimension k of the vector q that turns a model's score over every candidate
+// row x into one distance or dot product (skge_eval.hip header), for anchor row
+// ea and relation row rp (d floats each, in LDS) or RESCAL's W [d][d]:
+//            tail = true: x is the object      tail = false: x is the subject
+//   TransE   ea + rp                           ea - rp
+//   HolE     cconv(rp, ea)                     ccorr(rp, ea)
+//   RESCAL   (ea W)_k = sum_j ea[j] W[j][k]    (W ea)_k = sum_j W[k][j] ea[j]
+// every sum one fma chain in ascending j.
+__device__ __forceinline__ float query_elem(int model, bool tail, const float* ea, const float* rp,
+                                            const float* W, int d, int k) {
+  if (model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2) return tail ? ea[k] + rp[k] : ea[k] - rp[k];
+  if (model == SKGE_HOLE) return tail ? cconv_direct_k(rp, ea, d, k) : ccorr_direct_k(rp, ea, d, k);
+  float c = 0.0f;
+  for (int j = 0; j < d; ++j)
+    c = tail ? fmaf(ea[j], W[(size_t)j * d + k], c) : fmaf(W[(size_t)k * d + j], ea[j], c);
   return c;
 }
 

@@ -23,6 +23,7 @@
 // argsort, reversed).
 #include <algorithm>
 
+#include "skge_elem.h"
 #include "skge_host.h"
 #include "skge_rank_tile.h"
 
@@ -45,9 +46,9 @@ struct RankArgs {
 };
 
 // ---- query vectors and true scores: one wave per test triple ----
-// The true entity's score is recomputed by lane 0 with exactly the counting
-// kernel's arithmetic (sequential k, the same fma / abs expression on the
-// same stored query vector), so the true entity never outranks itself.
+// The vectors are query_elem's (skge_elem.h).  The true entity's score is
+// recomputed by lane 0 with rank_score, the counting kernel's arithmetic, on
+// the same stored query vector, so the true entity never outranks itself.
 __global__ __launch_bounds__(128) void k_rank_query(RankArgs a) {
   const int wpb = blockDim.x >> 6, l = lane_id(), d = a.d;
   extern __shared__ float sm[];
@@ -72,32 +73,8 @@ __global__ __launch_bounds__(128) void k_rank_query(RankArgs a) {
     const float* W = a.R + (size_t)p * d * d;
     const bool l1 = a.model == SKGE_TRANSE_L1 || a.model == SKGE_TRANSE_L2;
     for (int k = l; k < d; k += 64) {
-      float vt, vh;
-      if (l1) {
-        vt = es[k] + rp[k];
-        vh = eo[k] - rp[k];
-      } else if (a.model == SKGE_HOLE) {
-        // cconv(R, E_s)_k = sum_j R_j E_s[(k-j) mod d]; ccorr(R, E_o)_k = sum_j R_j E_o[(j+k) mod d]
-        float ct = 0.0f, ch = 0.0f;
-        for (int j = 0; j < d; ++j) {
-          int im = k - j;
-          im += im < 0 ? d : 0;
-          int ip = j + k;
-          ip -= ip >= d ? d : 0;
-          ct = fmaf(rp[j], es[im], ct);
-          ch = fmaf(rp[j], eo[ip], ch);
-        }
-        vt = ct;
-        vh = ch;
-      } else {   // RESCAL: (E_s W)_k = sum_j E_s[j] W[j][k]; (W E_o)_k = sum_j W[k][j] E_o[j]
-        float ct = 0.0f, ch = 0.0f;
-        for (int j = 0; j < d; ++j) {
-          ct = fmaf(es[j], W[(size_t)j * d + k], ct);
-          ch = fmaf(W[(size_t)k * d + j], eo[j], ch);
-        }
-        vt = ct;
-        vh = ch;
-      }
+      const float vt = query_elem(a.model, true, es, rp, W, d, k);
+      const float vh = query_elem(a.model, false, eo, rp, W, d, k);
       qt[k] = vt;
       qh[k] = vh;
       lqt[k] = vt;
@@ -105,18 +82,8 @@ __global__ __launch_bounds__(128) void k_rank_query(RankArgs a) {
     }
     __builtin_amdgcn_wave_barrier();
     if (l == 0) {   // tail: entity o under q_tail; head: entity s under q_head
-      float st = 0.0f, sh = 0.0f;
-      for (int k = 0; k < d; ++k) {
-        if (l1) {
-          st = st - fabsf(lqt[k] - eo[k]);
-          sh = sh - fabsf(lqh[k] - es[k]);
-        } else {
-          st = fmaf(eo[k], lqt[k], st);
-          sh = fmaf(es[k], lqh[k], sh);
-        }
-      }
-      a.tgt[2 * i] = st;
-      a.tgt[2 * i + 1] = sh;
+      a.tgt[2 * i] = l1 ? rank_score<true>(lqt, eo, d) : rank_score<false>(lqt, eo, d);
+      a.tgt[2 * i + 1] = l1 ? rank_score<true>(lqh, es, d) : rank_score<false>(lqh, es, d);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -301,17 +268,13 @@ void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d,
   b.Q = Q;
   b.tgt = tgt;
   b.raw = raw;
-  // enough workgroups to fill the chip: query blocks x entity slices
-  const int qb = (nv + RT_QB - 1) / RT_QB;
-  const int tiles = (rows + RT_EB - 1) / RT_EB;
-  const int want = std::max(1, std::min(tiles, (2048 + qb - 1) / qb));
-  const int per = (tiles + want - 1) / want;
-  b.eslice = per * RT_EB;
-  const int ns = (tiles + per - 1) / per;
+  const int qb = (nv + RT_QB - 1) / RT_QB;   // query blocks x entity slices
+  const SlicePlan p = slice_plan(qb, (rows + RT_EB - 1) / RT_EB);
+  b.eslice = p.per * RT_EB;
   if (l1)
-    hipLaunchKernelGGL((k_rank_count2<true>), dim3(qb, ns), dim3(256), 0, st, b);
+    hipLaunchKernelGGL((k_rank_count2<true>), dim3(qb, p.ns), dim3(256), 0, st, b);
   else
-    hipLaunchKernelGGL((k_rank_count2<false>), dim3(qb, ns), dim3(256), 0, st, b);
+    hipLaunchKernelGGL((k_rank_count2<false>), dim3(qb, p.ns), dim3(256), 0, st, b);
 }
 
 }  // namespace skge

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "../../include/skge_hip.h"
 #include "skge_device.h"
 
@@ -40,6 +42,18 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 // workspace parts start on 256-byte boundaries
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// The grid of a pass that crosses `blocks` query blocks with `tiles` units of
+// the other operand (128-row tiles of a table; relations): about 2048
+// workgroups, enough to fill the chip.  ns slices of `per` units each.
+struct SlicePlan {
+  int per, ns;
+};
+inline SlicePlan slice_plan(int blocks, int tiles) {
+  const int want = std::max(1, std::min(tiles, (2048 + blocks - 1) / std::max(1, blocks)));
+  const int per = (tiles + want - 1) / want;
+  return {per, (tiles + per - 1) / per};
+}
 
 // registers per lane needed to hold a row of width d in the lane-strided
 // layout (see skge_device.h); 0 = unsupported
@@ -155,7 +169,12 @@ void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d,
 // the plan's slices (pools->ns is set here).
 // launch_topk_query: skge_topk's query vectors (anchor, p) of one direction
 // into Q [nq][d].
+// launch_list_merge: the merge alone (k_list_merge), for a selection of
+// another kind (skge_neighbours.hip): each query's ns sorted lists [nq][ns][k]
+// of keys (skge_topk_list.h) into its k best, decoded.
 struct PoolWork;
+void launch_list_merge(hipStream_t st, const void* lists, int nq, int ns, int k, int* ids_out,
+                       float* score_out);
 void launch_topk_query(hipStream_t st, int model, const float* E, const float* R, int d,
                        const int* queries, int nq, int direction, float* Q);
 int topk_block_size(int k);

@@ -15,7 +15,7 @@
 //                 LDS query-major over the dead staging buffers, and each wave
 //                 offers them to its queries' sorted key lists
 //                 (skge_topk_list.h, as k_topk_select does)
-//   k_nb_merge    one wave per query: the slices' lists into the final k
+// and k_list_merge (skge_topk.hip) takes the slices' lists into the final k.
 // cos(q, j) = (dot * r_q) * r_j; the dot metric multiplies by 1.0f twice,
 // which changes no bit.  The self entry becomes key 0, "no candidate".
 #include <algorithm>
@@ -40,8 +40,6 @@ struct NbArgs {
   const float* rQ;       // workspace [nq]: 1 / |Q_i| (cosine, external queries)
   tkey_t* lists;         // workspace [nq][ns][k]
   int tslice, ns;        // table rows per slice (multiple of NB_TB), slices
-  int* ids_out;          // [nq][k]
-  float* sim_out;        // [nq][k]
 };
 
 // ---- reciprocal norms: one lane per row, the contract's chain ----
@@ -224,14 +222,7 @@ __global__ __launch_bounds__(256, 2) void k_nb_select(NbArgs a) {
         const int ja = t0 + l, jb = t0 + 64 + l;
         const tkey_t c0 = ja < tend && ja != self ? make_key(sS[qq * NB_TB + l], ja) : 0;
         const tkey_t c1 = jb < tend && jb != self ? make_key(sS[qq * NB_TB + 64 + l], jb) : 0;
-        tkey_t thr = s_list[qi][k - 1];
-        if (__ballot(c0 > thr || c1 > thr) == 0) continue;
-        tkey_t lo = l < k ? s_list[qi][l] : 0;
-        tkey_t hi = 64 + l < k ? s_list[qi][64 + l] : 0;
-        list_offer<false>(lo, hi, thr, c0, k, l, nullptr, nullptr);
-        list_offer<false>(lo, hi, thr, c1, k, l, nullptr, nullptr);
-        if (l < k) s_list[qi][l] = lo;
-        if (64 + l < k) s_list[qi][64 + l] = hi;
+        list_offer2(s_list[qi], c0, c1, k, l, nullptr, nullptr, 0);
       }
     }
   }
@@ -240,39 +231,12 @@ __global__ __launch_bounds__(256, 2) void k_nb_select(NbArgs a) {
   for (int qi = w; qi < QB; qi += 4) {
     const int v = v0 + qi;
     if (v >= a.nq) break;
-    tkey_t* out = a.lists + ((size_t)v * a.ns + blockIdx.y) * k;
-    if (l < k) out[l] = s_list[qi][l];
-    if (64 + l < k) out[64 + l] = s_list[qi][64 + l];
-  }
-}
-
-// ---- merge: one wave per query, the slices' lists into the final k ----
-__global__ __launch_bounds__(256) void k_nb_merge(NbArgs a) {
-  const int l = lane_id(), k = a.k;
-  const int v = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (v >= a.nq) return;
-  tkey_t lo = 0, hi = 0, thr = 0;
-  for (int s = 0; s < a.ns; ++s) {
-    const tkey_t* in = a.lists + ((size_t)v * a.ns + s) * k;
-    const tkey_t c0 = l < k ? in[l] : 0;
-    const tkey_t c1 = 64 + l < k ? in[64 + l] : 0;
-    list_offer<false>(lo, hi, thr, c0, k, l, nullptr, nullptr);
-    list_offer<false>(lo, hi, thr, c1, k, l, nullptr, nullptr);
-  }
-  int* io = a.ids_out + (size_t)v * k;
-  float* so = a.sim_out + (size_t)v * k;
-  if (l < k) {
-    io[l] = lo ? key_entity(lo) : -1;
-    so[l] = lo ? key_score(lo) : -INFINITY;
-  }
-  if (64 + l < k) {
-    io[64 + l] = hi ? key_entity(hi) : -1;
-    so[64 + l] = hi ? key_score(hi) : -INFINITY;
+    list_store(a.lists + ((size_t)v * a.ns + blockIdx.y) * k, s_list[qi], k, l);
   }
 }
 
 // query block (shrinks as k grows: the lists' LDS), table slices: enough
-// workgroups to fill the chip (as skge_topk sizes its selection)
+// workgroups to fill the chip (slice_plan)
 struct NbPlan {
   int qb_size, qb, tslice, ns;
 };
@@ -280,14 +244,12 @@ static NbPlan nb_plan(int nq, int k, int N) {
   NbPlan p;
   p.qb_size = k <= 16 ? 128 : k <= 32 ? 64 : 32;
   p.qb = (nq + p.qb_size - 1) / p.qb_size;
-  const int tiles = (N + NB_TB - 1) / NB_TB;
-  const int want = std::max(1, std::min(tiles, (2048 + p.qb - 1) / std::max(1, p.qb)));
-  const int per = (tiles + want - 1) / want;
-  p.tslice = per * NB_TB;
-  p.ns = (tiles + per - 1) / per;
+  const SlicePlan sp = slice_plan(p.qb, (N + NB_TB - 1) / NB_TB);
+  p.tslice = sp.per * NB_TB;
+  p.ns = sp.ns;
   return p;
 }
-static size_t nb_r_bytes(int n) { return (((size_t)n * sizeof(float)) + 255) & ~(size_t)255; }
+static size_t nb_r_bytes(int n) { return align256((size_t)n * sizeof(float)); }
 
 }  // namespace skge
 
@@ -330,8 +292,6 @@ extern "C" int skge_neighbours(void* stream, const float* T, int N, int d, const
   a.lists = (tkey_t*)((char*)workspace + nb_r_bytes(N) + nb_r_bytes(nq));
   a.tslice = p.tslice;
   a.ns = p.ns;
-  a.ids_out = ids_out;
-  a.sim_out = sim_out;
   hipStream_t st = as_stream(stream);
   if (a.cosine) {
     hipLaunchKernelGGL(k_nb_norms, dim3((N + 255) / 256), dim3(256), 0, st, T, N, d, rT);
@@ -343,7 +303,7 @@ extern "C" int skge_neighbours(void* stream, const float* T, int N, int d, const
     hipLaunchKernelGGL((k_nb_select<64, 32>), dim3(p.qb, p.ns), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((k_nb_select<32, TK_KMAX>), dim3(p.qb, p.ns), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k_nb_merge, dim3((nq + 3) / 4), dim3(256), 0, st, a);
+  launch_list_merge(st, a.lists, nq, p.ns, k, ids_out, sim_out);
   SKGE_CHECK_LAUNCH("neighbours");
   return SKGE_OK;
 }

@@ -12,9 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace skge {
+#include "skge_rank_tile.h"
 
-constexpr int POOL_TILE = 128;   // candidate rows per LDS tile (RT_EB, TK_EB)
+namespace skge {
 
 struct PoolWork {
   const int4* items;         // (pool or -1, first slot of `order`, vectors, 0)
@@ -25,14 +25,15 @@ struct PoolWork {
   int ns;                    // candidate slices per item (grid.y)
 };
 
-// slice y of ns of a pool of `size` candidates, in whole tiles: [ebeg, eend)
+// slice y of ns of a pool of `size` candidates, in whole tiles of the score
+// tile (skge_rank_tile.h): [ebeg, eend)
 // (empty when the pool has fewer tiles than slices)
 __device__ __forceinline__ void pool_slice(int size, int ns, int y, int& ebeg, int& eend) {
-  const int tiles = (size + POOL_TILE - 1) / POOL_TILE;
+  const int tiles = (size + RT_EB - 1) / RT_EB;
   const int per = (tiles + ns - 1) / ns;
-  const long long b = (long long)y * per * POOL_TILE;
+  const long long b = (long long)y * per * RT_EB;
   ebeg = b < size ? (int)b : size;
-  eend = size - ebeg < per * POOL_TILE ? size : ebeg + per * POOL_TILE;
+  eend = size - ebeg < per * RT_EB ? size : ebeg + per * RT_EB;
 }
 
 // the candidates of item `it` under w: the pool's size, and base so that
@@ -45,5 +46,18 @@ __device__ __forceinline__ int pool_size(const PoolWork& w, int pool, int N, int
   base = w.pool_off[pool];
   return (int)(w.pool_off[pool + 1] - base);
 }
+
+// The score tile's mapping (skge_rank_tile.h) of one item: its vectors through
+// the order array (s_vec: their ids in LDS for the counting's end, unused by
+// the selection); candidate e of the pool is row ent[e] (pool -1: row e)
+struct RankPoolRows {
+  const int* order;   // the item's first slot
+  int vcnt;
+  const int* ent;     // the pool's first entry, or nullptr
+  const int* s_vec;
+  __device__ __forceinline__ int vec(int i) const { return i < vcnt ? order[i] : -1; }
+  __device__ __forceinline__ int row(int e) const { return ent ? ent[e] : e; }
+  __device__ __forceinline__ int kept(int i) const { return s_vec[i]; }
+};
 
 }  // namespace skge

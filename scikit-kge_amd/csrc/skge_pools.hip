@@ -23,7 +23,6 @@
 
 #include "skge_host.h"
 #include "skge_pools.h"
-#include "skge_rank_tile.h"
 #include "skge_topk_list.h"
 
 namespace skge {
@@ -111,8 +110,6 @@ int launch_pool_group(hipStream_t st, const int* vec_pool, int nv, int n_pools, 
 }
 
 // ---- counting: one item (<= 64 vectors of one pool) x one slice of the pool ----
-static_assert(RT_EB == POOL_TILE, "a pool's slices are whole tiles of the counting pass");
-
 struct PoolRankArgs {
   const float* E;
   int N, d;
@@ -120,18 +117,6 @@ struct PoolRankArgs {
   const float* tgt;    // [nv]
   int* raw;            // [nv] candidates scoring strictly higher (atomics over the slices)
   PoolWork pw;
-};
-
-// the item's vectors through the order array (s_vec: their ids in LDS for the
-// tile's end); candidate e of the pool is row ent[e] (pool -1: row e)
-struct RankPoolRows {
-  const int* order;   // the item's first slot
-  int vcnt;
-  const int* ent;     // the pool's first entry, or nullptr
-  const int* s_vec;
-  __device__ __forceinline__ int vec(int i) const { return i < vcnt ? order[i] : -1; }
-  __device__ __forceinline__ int row(int e) const { return ent ? ent[e] : e; }
-  __device__ __forceinline__ int kept(int i) const { return s_vec[i]; }
 };
 
 template <bool L1>
@@ -194,16 +179,6 @@ __global__ __launch_bounds__(256) void k_rank_known_pool(
   ranks[4 * qi + 2 * dir + 1] = 1 + raw[v] - dec;
 }
 
-// candidate slices per item: launch_rank_count's rule (enough workgroups to
-// fill the chip) with the item bound for the query blocks and N for a pool's
-// size; a pool with fewer tiles than slices leaves the others empty
-static int pool_slices(int max_items, int N) {
-  const int tiles = (N + POOL_TILE - 1) / POOL_TILE;
-  const int want = std::max(1, std::min(tiles, (2048 + max_items - 1) / max_items));
-  const int per = (tiles + want - 1) / want;
-  return (tiles + per - 1) / per;
-}
-
 }  // namespace skge
 
 using namespace skge;
@@ -255,7 +230,9 @@ extern "C" int skge_rank_pools(void* stream, int model, const float* E, const fl
   launch_rank_query(st, model, E, R, N, d, queries, nq, Q, tgt);
   const bool l1 = model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2;
   const int max_items = pool_items_max(nv, n_pools, RT_QB);
-  a.pw.ns = pool_slices(max_items, N);
+  // a pool has at most N candidates; one with fewer tiles than slices leaves
+  // the others empty
+  a.pw.ns = slice_plan(max_items, (N + RT_EB - 1) / RT_EB).ns;
   const dim3 grid(max_items, a.pw.ns);
   const int kb = (nv + 255) / 256;
   if (l1) {

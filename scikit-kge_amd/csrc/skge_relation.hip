@@ -60,12 +60,9 @@ __global__ __launch_bounds__(128) void k_rel_query(RelQueryArgs a) {
     __builtin_amdgcn_wave_barrier();
     float* q = a.Q + (size_t)i * d;
     for (int k = l; k < d; k += 64) {
-      float v;
-      if (dist) {
-        v = eo[k] - es[k];
-      } else {   // ccorr(E_s, E_o)_k (k_rank_query's chain)
-        v = ccorr_direct_k(es, eo, d, k);
-      }
+      // E_o - E_s or ccorr(E_s, E_o): query_elem's subject-side forms with E_o
+      // for the anchor and E_s for the relation row
+      const float v = query_elem(a.model, false, eo, es, nullptr, d, k);
       q[k] = v;
       lq[k] = v;
     }
@@ -184,16 +181,7 @@ __global__ __launch_bounds__(256) void k_rel_topk_rows(const float* __restrict__
     else
       list_offer<false>(lo, hi, thr, c, k, l, nullptr, nullptr);
   }
-  int* ro = rel_out + (size_t)v * k;
-  float* so = score_out + (size_t)v * k;
-  if (l < k) {
-    ro[l] = lo ? key_entity(lo) : -1;
-    so[l] = lo ? key_score(lo) : -INFINITY;
-  }
-  if (64 + l < k) {
-    ro[64 + l] = hi ? key_entity(hi) : -1;
-    so[64 + l] = hi ? key_score(hi) : -INFINITY;
-  }
+  list_decode_store(lo, hi, k, l, rel_out + (size_t)v * k, score_out + (size_t)v * k);
 }
 
 // RESCAL: pairs per pass of the entry points, so that the score matrix stays
@@ -222,12 +210,12 @@ static void launch_rel_rescal(hipStream_t st, const float* E, const float* W, in
   a.queries = queries;
   a.stride = stride;
   a.S = S;
-  // query blocks x relation groups: about 2048 workgroups (skge_topk's rule)
+  // query blocks x relation groups (slice_plan over the M relations)
   const int qb_size = nq <= 32 ? 32 : nq <= 64 ? 64 : 128;
   const int qb = (nq + qb_size - 1) / qb_size;
-  const int want = std::max(1, std::min(M, (2048 + qb - 1) / qb));
-  a.rper = (M + want - 1) / want;
-  const int groups = (M + a.rper - 1) / a.rper;
+  const SlicePlan sp = slice_plan(qb, M);
+  a.rper = sp.per;
+  const int groups = sp.ns;
   if (qb_size == 32)
     hipLaunchKernelGGL((k_rel_rescal<32>), dim3(qb, groups), dim3(256), 0, st, a);
   else if (qb_size == 64)

@@ -286,7 +286,7 @@ static void launch_embed(hipStream_t st, const EmbedArgs& a) {
 }
 
 // workspace: [grp_base S ints | parts cap x d floats | piece_grp cap ints]
-static size_t sg_head_bytes(int S) { return (((size_t)S * sizeof(int)) + 255) & ~(size_t)255; }
+static size_t sg_head_bytes(int S) { return align256((size_t)S * sizeof(int)); }
 static size_t sg_piece_bytes(int d) { return (size_t)d * sizeof(float) + sizeof(int); }
 
 // ---- ranking: the best eligible subgraph that contains the answer ----

@@ -1,5 +1,8 @@
 // The sorted key lists of the top-k selections (skge_topk.hip,
-// skge_neighbours.hip).
+// skge_neighbours.hip, k_rel_topk_rows of skge_relation.hip) and what every
+// selection does with one: offer a tile's candidates to a list kept in LDS
+// (list_offer2), write a list out (list_store), decode a finished one
+// (list_decode_store).
 //
 // A list entry is one 64-bit key, (order-preserving bits of the fp32 score)
 // << 32 | (0xffffffff - entity id): the larger key is the better entry under
@@ -70,6 +73,47 @@ __device__ __forceinline__ void list_offer(tkey_t& lo, tkey_t& hi, tkey_t& thr, 
     list_insert(lo, hi, K, k, l);
     thr = list_kth(lo, hi, k);
     m &= __ballot(cand > thr);
+  }
+}
+
+// One wave offers two candidates per lane (0 = none) to a list kept in memory
+// (LDS), slot l in list[l]: nothing is loaded unless one of them beats the
+// k-th entry.  excl_off: the exclusion CSR, row v this list's, or nullptr.
+__device__ __forceinline__ void list_offer2(tkey_t* list, tkey_t c0, tkey_t c1, int k, int l,
+                                            const int* excl_off, const int* excl_ent, int v) {
+  tkey_t thr = list[k - 1];
+  if (__ballot(c0 > thr || c1 > thr) == 0) return;
+  tkey_t lo = l < k ? list[l] : 0;
+  tkey_t hi = 64 + l < k ? list[64 + l] : 0;
+  if (excl_off) {
+    const int* xb = excl_ent + excl_off[v];
+    const int* xe = excl_ent + excl_off[v + 1];
+    list_offer<true>(lo, hi, thr, c0, k, l, xb, xe);
+    list_offer<true>(lo, hi, thr, c1, k, l, xb, xe);
+  } else {
+    list_offer<false>(lo, hi, thr, c0, k, l, nullptr, nullptr);
+    list_offer<false>(lo, hi, thr, c1, k, l, nullptr, nullptr);
+  }
+  if (l < k) list[l] = lo;
+  if (64 + l < k) list[64 + l] = hi;
+}
+
+// one wave copies a list of k keys
+__device__ __forceinline__ void list_store(tkey_t* out, const tkey_t* list, int k, int l) {
+  if (l < k) out[l] = list[l];
+  if (64 + l < k) out[64 + l] = list[64 + l];
+}
+
+// a finished list to k (id, score) pairs, the empty slots as (-1, -inf)
+__device__ __forceinline__ void list_decode_store(tkey_t lo, tkey_t hi, int k, int l, int* ids,
+                                                  float* scores) {
+  if (l < k) {
+    ids[l] = lo ? key_entity(lo) : -1;
+    scores[l] = lo ? key_score(lo) : -INFINITY;
+  }
+  if (64 + l < k) {
+    ids[64 + l] = hi ? key_entity(hi) : -1;
+    scores[64 + l] = hi ? key_score(hi) : -INFINITY;
   }
 }
 
