@@ -391,6 +391,17 @@ skge_pair_runner_t *skge_pair_runner_create_ex(void *stream, int model, int af,
                                                int64_t set_capacity, int nbatches, uint64_t seed,
                                                uint64_t *epoch_key, float margin, int ntries,
                                                int *nviol_total, const skge_sampler_t *smp);
+/* skge_runner_create drawing its negatives with smp: the typed / LCWA
+ * instances of its sample_grad kernels draw, one positive per wave, by the
+ * rule of skge_epoch_sample_ex -- the same pairs, bit for bit (NULL or RANDOM:
+ * skge_runner_create itself).  The runner keeps smp's pointers only; the
+ * caller owns the pools for the runner's lifetime. */
+skge_runner_t *skge_runner_create_smp(void *stream, int l1, const skge_table_t *ent,
+                                      const skge_table_t *rel, int d, const int *trip, int64_t T,
+                                      const void *set, int64_t set_capacity, int nbatches,
+                                      uint64_t seed, uint64_t *epoch_key, float margin,
+                                      int ntries, int *nviol, int *nviol_total,
+                                      const skge_sampler_t *smp);
 int skge_pair_runner_run(skge_pair_runner_t *r, void *stream, int nepochs);
 int skge_pair_runner_nlaunches(const skge_pair_runner_t *r);
 void skge_pair_runner_destroy(skge_pair_runner_t *r);
@@ -557,6 +568,41 @@ skge_pipe_runner_t *skge_hole_pipe_runner_create(void *stream, int af, const skg
                                                  int64_t T, const void *set, int64_t set_capacity,
                                                  int nbatches, uint64_t seed, uint64_t *epoch_key,
                                                  float margin, int ntries, int *nviol_total);
+/*
+ * The pipelined runners drawing their negatives with smp (skge_sampler_t; NULL
+ * or RANDOM: the constructors above, kernel for kernel).  Only the epoch's
+ * draw launch differs: the kind's instance writes the records of
+ * skge_epoch_sample_ex and, as the RANDOM launch, the runner's copy of the
+ * epoch key, and draws no negative once the error word is set.  The hot rows
+ * are chosen by occurrences, as ever; SKGE_PIPE_HOT_NEG=1 adds a pool kind's
+ * expected corruptions per epoch (a pool of length L gets its relation's
+ * positives / L per member) -- the same bits either way, and measured slower.
+ * SKGE_PIPE_DP with a pool kind is refused.  The runner keeps smp's pointers
+ * only; the caller owns the pools for the runner's lifetime.
+ */
+skge_pipe_runner_t *skge_pipe_runner_create_smp(void *stream, const skge_table_t *ent,
+                                                const skge_table_t *rel, int d, const int *trip,
+                                                int64_t T, const void *set, int64_t set_capacity,
+                                                int nbatches, uint64_t seed, uint64_t *epoch_key,
+                                                float margin, int ntries, int *nviol_total,
+                                                int flags, const skge_sampler_t *smp);
+skge_pipe_runner_t *skge_hole_pipe_runner_create_smp(void *stream, int af,
+                                                     const skge_table_t *ent,
+                                                     const skge_table_t *rel, int d,
+                                                     const int *trip, int64_t T, const void *set,
+                                                     int64_t set_capacity, int nbatches,
+                                                     uint64_t seed, uint64_t *epoch_key,
+                                                     float margin, int ntries, int *nviol_total,
+                                                     const skge_sampler_t *smp);
+/* The pipelined runners' draw launch on its own (tests / host-side replay):
+ * skge_epoch_sample_ex's records through the launch the runners capture, with
+ * its two extra duties -- *key_copy = *epoch_key (optional), and no negative
+ * drawn (every s' and o' is -1) when *err (optional, device) is non-zero.
+ * ntries >= 0. */
+int skge_pipe_epoch_sample(void *stream, const int *trip, int64_t T, const void *set,
+                           int64_t set_capacity, int n_ent, uint64_t seed,
+                           const uint64_t *epoch_key, int ntries, int *rec, int *rec_n1,
+                           const skge_sampler_t *smp, const int *err, uint64_t *key_copy);
 int skge_pipe_runner_run(skge_pipe_runner_t *r, void *stream, int nepochs);
 /* synchronizes the stream; returns 0, or a bit set (results then invalid):
  * 1 = a bounded cross-workgroup wait gave up, 2 = a row's per-batch count

@@ -54,6 +54,7 @@ struct SampleArgs {
   int* nviol_total;
   int* vshards;   // runner: violations go to these shards (folded at the epoch end), not nviol_total
   int* neg_out;
+  Pools pl;       // the typed / LCWA instances' type index (skge_runner_create_smp)
 };
 
 // a wave's violation count: sharded (runner) or one atomic per workgroup
@@ -93,7 +94,20 @@ __device__ __forceinline__ void sample_rest(const SampleArgs& a, uint64_t skey, 
   }
 }
 
-template <int KM, bool L1>
+// The typed / LCWA negatives of a wave's positive (the KIND != SAMPLER_RANDOM
+// instances below): every lane runs draw_pools' sequential rule on the same
+// wave-uniform arguments, so the pair is the one k_epoch_sample_pools records,
+// bit for bit.  No first-try shortcut: a typed try indexes a pool whose length
+// depends on the positive's relation.
+template <int KIND>
+__device__ __forceinline__ void wave_draw_pools(const SampleArgs& a, uint64_t skey, long long j,
+                                                int s, int o, int p, int& neg0, int& neg1) {
+  draw_pools<KIND>(skey, a.set, a.pl, a.n_ent, a.ntries, j, s, o, p, neg0, neg1);
+  neg0 = __builtin_amdgcn_readfirstlane(neg0);
+  neg1 = __builtin_amdgcn_readfirstlane(neg1);
+}
+
+template <int KM, bool L1, int KIND = SAMPLER_RANDOM>
 __global__ __launch_bounds__(256) void k_transe_sample_grad(SampleArgs a) {
   const int wpb = blockDim.x >> 6;
   const int l = lane_id();
@@ -109,8 +123,10 @@ __global__ __launch_bounds__(256) void k_transe_sample_grad(SampleArgs a) {
     // speculatively, in the same memory round trip as the triple itself
     const int cand0 = draw(skey, j, 0, 0, a.n_ent), cand1 = draw(skey, j, 1, 0, a.n_ent);
     float fs[KM], fo[KM];
-    load_row<KM>(a.E, cand0, d, fs);
-    load_row<KM>(a.E, cand1, d, fo);
+    if (KIND == SAMPLER_RANDOM) {
+      load_row<KM>(a.E, cand0, d, fs);
+      load_row<KM>(a.E, cand1, d, fo);
+    }
     const int s = __builtin_amdgcn_readfirstlane(a.trip[3 * t]);
     const int o = __builtin_amdgcn_readfirstlane(a.trip[3 * t + 1]);
     const int p = __builtin_amdgcn_readfirstlane(a.trip[3 * t + 2]);
@@ -118,18 +134,26 @@ __global__ __launch_bounds__(256) void k_transe_sample_grad(SampleArgs a) {
     load_row<KM>(a.E, s, d, es);
     load_row<KM>(a.E, o, d, eo);
     load_row<KM>(a.R, p, d, rp);
-    // rejection test of the first tries (lane 0: (cand0, o, p), lane 1: (s, cand1, p))
-    bool ok = true;
-    if (l < 2) ok = l == 0 ? !set_contains(a.set, cand0, o, p) : !set_contains(a.set, s, cand1, p);
-    const uint64_t okm = __ballot(ok);
-    int neg0 = (okm & 1ull) ? cand0 : -1;
-    int neg1 = (okm & 2ull) ? cand1 : -1;
-    if (neg0 < 0 || neg1 < 0) {   // rare: a first draw hit a training triple
-      sample_rest(a, skey, j, s, o, p, 1, neg0, neg1);
-      neg0 = __builtin_amdgcn_readfirstlane(neg0);
-      neg1 = __builtin_amdgcn_readfirstlane(neg1);
-      if (neg0 >= 0 && neg0 != cand0) load_row<KM>(a.E, neg0, d, fs);
-      if (neg1 >= 0 && neg1 != cand1) load_row<KM>(a.E, neg1, d, fo);
+    int neg0, neg1;
+    if (KIND == SAMPLER_RANDOM) {
+      // rejection test of the first tries (lane 0: (cand0, o, p), lane 1: (s, cand1, p))
+      bool ok = true;
+      if (l < 2) ok = l == 0 ? !set_contains(a.set, cand0, o, p) : !set_contains(a.set, s, cand1, p);
+      const uint64_t okm = __ballot(ok);
+      neg0 = (okm & 1ull) ? cand0 : -1;
+      neg1 = (okm & 2ull) ? cand1 : -1;
+      if (neg0 < 0 || neg1 < 0) {   // rare: a first draw hit a training triple
+        sample_rest(a, skey, j, s, o, p, 1, neg0, neg1);
+        neg0 = __builtin_amdgcn_readfirstlane(neg0);
+        neg1 = __builtin_amdgcn_readfirstlane(neg1);
+        if (neg0 >= 0 && neg0 != cand0) load_row<KM>(a.E, neg0, d, fs);
+        if (neg1 >= 0 && neg1 != cand1) load_row<KM>(a.E, neg1, d, fo);
+      }
+    } else {
+      // (a missing negative scores the positive's own row: its pair is dropped)
+      wave_draw_pools<KIND>(a, skey, j, s, o, p, neg0, neg1);
+      load_row<KM>(a.E, neg0 >= 0 ? neg0 : s, d, fs);
+      load_row<KM>(a.E, neg1 >= 0 ? neg1 : o, d, fo);
     }
     float ps = 0.0f, n0 = 0.0f, n1 = 0.0f, gp[KM], g0[KM], g1[KM];
 #pragma unroll
@@ -199,7 +223,7 @@ __global__ __launch_bounds__(256) void k_transe_sample_grad(SampleArgs a) {
 struct PosL1 {
   int s, o, p, neg0, neg1, v0, v1;
 };
-template <int KQ>
+template <int KQ, int KIND = SAMPLER_RANDOM>
 __device__ __forceinline__ PosL1 transe_l1_front(const SampleArgs& a, const Perm& pm,
                                                  uint64_t skey, long long j, float4 (&gp)[KQ],
                                                  float4 (&g0)[KQ], float4 (&g1)[KQ]) {
@@ -210,8 +234,10 @@ __device__ __forceinline__ PosL1 transe_l1_front(const SampleArgs& a, const Perm
   // in the same memory round trip as the triple
   const int cand0 = draw(skey, j, 0, 0, a.n_ent), cand1 = draw(skey, j, 1, 0, a.n_ent);
   float4 fs[KQ], fo[KQ];
-  load_row4<KQ>(a.E, cand0, d, fs);
-  load_row4<KQ>(a.E, cand1, d, fo);
+  if (KIND == SAMPLER_RANDOM) {
+    load_row4<KQ>(a.E, cand0, d, fs);
+    load_row4<KQ>(a.E, cand1, d, fo);
+  }
   PosL1 r;
   r.s = __builtin_amdgcn_readfirstlane(a.trip[3 * t]);
   r.o = __builtin_amdgcn_readfirstlane(a.trip[3 * t + 1]);
@@ -221,17 +247,25 @@ __device__ __forceinline__ PosL1 transe_l1_front(const SampleArgs& a, const Perm
   load_row4<KQ>(a.E, s, d, es);
   load_row4<KQ>(a.E, o, d, eo);
   load_row4<KQ>(a.R, p, d, rp);
-  bool ok = true;
-  if (l < 2) ok = l == 0 ? !set_contains(a.set, cand0, o, p) : !set_contains(a.set, s, cand1, p);
-  const uint64_t okm = __ballot(ok);
-  int neg0 = (okm & 1ull) ? cand0 : -1;
-  int neg1 = (okm & 2ull) ? cand1 : -1;
-  if (neg0 < 0 || neg1 < 0) {   // rare: a first draw hit a training triple
-    sample_rest(a, skey, j, s, o, p, 1, neg0, neg1);
-    neg0 = __builtin_amdgcn_readfirstlane(neg0);
-    neg1 = __builtin_amdgcn_readfirstlane(neg1);
-    if (neg0 >= 0 && neg0 != cand0) load_row4<KQ>(a.E, neg0, d, fs);
-    if (neg1 >= 0 && neg1 != cand1) load_row4<KQ>(a.E, neg1, d, fo);
+  int neg0, neg1;
+  if (KIND == SAMPLER_RANDOM) {
+    bool ok = true;
+    if (l < 2) ok = l == 0 ? !set_contains(a.set, cand0, o, p) : !set_contains(a.set, s, cand1, p);
+    const uint64_t okm = __ballot(ok);
+    neg0 = (okm & 1ull) ? cand0 : -1;
+    neg1 = (okm & 2ull) ? cand1 : -1;
+    if (neg0 < 0 || neg1 < 0) {   // rare: a first draw hit a training triple
+      sample_rest(a, skey, j, s, o, p, 1, neg0, neg1);
+      neg0 = __builtin_amdgcn_readfirstlane(neg0);
+      neg1 = __builtin_amdgcn_readfirstlane(neg1);
+      if (neg0 >= 0 && neg0 != cand0) load_row4<KQ>(a.E, neg0, d, fs);
+      if (neg1 >= 0 && neg1 != cand1) load_row4<KQ>(a.E, neg1, d, fo);
+    }
+  } else {
+    // (a missing negative scores the positive's own row: its pair is dropped)
+    wave_draw_pools<KIND>(a, skey, j, s, o, p, neg0, neg1);
+    load_row4<KQ>(a.E, neg0 >= 0 ? neg0 : s, d, fs);
+    load_row4<KQ>(a.E, neg1 >= 0 ? neg1 : o, d, fo);
   }
   float ps, n0, n1;
   l1_scores_signs<KQ>(es, eo, fs, fo, rp, ps, n0, n1, gp, g0, g1);
@@ -279,7 +313,7 @@ __device__ __forceinline__ void transe_l1_commit(const SampleArgs& a, long long 
 // quad row layout: the sign contributions are small integers, so four
 // elements share one 64-bit integer atomic, and every row gather / row atomic
 // is a single 16-byte-per-lane wave-instruction (d <= 256).
-template <int KQ>
+template <int KQ, int KIND = SAMPLER_RANDOM>
 __global__ __launch_bounds__(256) void k_transe_l1_sample_grad_i16(SampleArgs a) {
   const int wpb = blockDim.x >> 6;
   const int l = lane_id();
@@ -290,7 +324,7 @@ __global__ __launch_bounds__(256) void k_transe_l1_sample_grad_i16(SampleArgs a)
   for (int w = blockIdx.x * wpb + (threadIdx.x >> 6); w < a.count; w += gridDim.x * wpb) {
     const long long j = a.start + w;
     float4 gp[KQ], g0[KQ], g1[KQ];
-    const PosL1 r = transe_l1_front<KQ>(a, pm, skey, j, gp, g0, g1);
+    const PosL1 r = transe_l1_front<KQ, KIND>(a, pm, skey, j, gp, g0, g1);
     if (a.neg_out && l == 0) {
       a.neg_out[2 * (long long)w] = r.neg0;
       a.neg_out[2 * (long long)w + 1] = r.neg1;
@@ -317,7 +351,7 @@ __global__ void k_epoch_end(uint64_t* ek, int* shards, int* nviol_total) {
   if (threadIdx.x == 0) *ek += 1;
 }
 
-static int launch_sample(const SampleArgs& a, bool l1, hipStream_t st) {
+static int launch_sample(const SampleArgs& a, bool l1, hipStream_t st, int kind = SAMPLER_RANDOM) {
   const int km = km_for(a.d);
   int blocks = (a.count + 3) / 4;
   if (blocks < 1) blocks = 1;
@@ -329,8 +363,17 @@ static int launch_sample(const SampleArgs& a, bool l1, hipStream_t st) {
       return SKGE_EINVAL;
     }
     const int kq = (a.d / 4 + 63) / 64;
-#define SKGE_SP(K) \
-  hipLaunchKernelGGL((k_transe_l1_sample_grad_i16<K>), dim3(blocks), dim3(256), 0, st, a)
+#define SKGE_SP(K)                                                                               \
+  do {                                                                                           \
+    if (kind == SAMPLER_TYPED)                                                                   \
+      hipLaunchKernelGGL((k_transe_l1_sample_grad_i16<K, SAMPLER_TYPED>), dim3(blocks),          \
+                         dim3(256), 0, st, a);                                                   \
+    else if (kind == SAMPLER_LCWA)                                                               \
+      hipLaunchKernelGGL((k_transe_l1_sample_grad_i16<K, SAMPLER_LCWA>), dim3(blocks),           \
+                         dim3(256), 0, st, a);                                                   \
+    else                                                                                         \
+      hipLaunchKernelGGL((k_transe_l1_sample_grad_i16<K>), dim3(blocks), dim3(256), 0, st, a);   \
+  } while (0)
     if (kq <= 1) SKGE_SP(1);
     else if (kq <= 2) SKGE_SP(2);
     else SKGE_SP(4);
@@ -342,12 +385,21 @@ static int launch_sample(const SampleArgs& a, bool l1, hipStream_t st) {
     set_error("mixed accumulator modes");
     return SKGE_EINVAL;
   }
+#define SKGE_SGK(K, L1, KIND) \
+  hipLaunchKernelGGL((k_transe_sample_grad<K, L1, KIND>), dim3(blocks), dim3(256), 0, st, a)
 #define SKGE_SG(K)                                                                               \
   case K:                                                                                        \
-    if (l1)                                                                                      \
+    if (kind == SAMPLER_TYPED) {                                                                 \
+      if (l1) SKGE_SGK(K, true, SAMPLER_TYPED);                                                  \
+      else SKGE_SGK(K, false, SAMPLER_TYPED);                                                    \
+    } else if (kind == SAMPLER_LCWA) {                                                           \
+      if (l1) SKGE_SGK(K, true, SAMPLER_LCWA);                                                   \
+      else SKGE_SGK(K, false, SAMPLER_LCWA);                                                     \
+    } else if (l1) {                                                                             \
       hipLaunchKernelGGL((k_transe_sample_grad<K, true>), dim3(blocks), dim3(256), 0, st, a);   \
-    else                                                                                         \
+    } else {                                                                                     \
       hipLaunchKernelGGL((k_transe_sample_grad<K, false>), dim3(blocks), dim3(256), 0, st, a);  \
+    }                                                                                            \
     break;
   switch (km) {
     SKGE_SG(1)
@@ -361,6 +413,7 @@ static int launch_sample(const SampleArgs& a, bool l1, hipStream_t st) {
       return SKGE_ENOTSUP;
   }
 #undef SKGE_SG
+#undef SKGE_SGK
   SKGE_CHECK_LAUNCH("transe sample grad");
   return SKGE_OK;
 }
@@ -474,12 +527,15 @@ struct skge_runner : GraphRunnerCore {
   int* shards = nullptr;
 };
 
-extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_table_t* ent,
-                                             const skge_table_t* rel, int d, const int* trip,
-                                             int64_t T, const void* set_slots,
-                                             int64_t set_capacity, int nbatches, uint64_t seed,
-                                             uint64_t* epoch_key, float margin, int ntries,
-                                             int* nviol, int* nviol_total) {
+extern "C" skge_runner_t* skge_runner_create_smp(void* stream, int l1, const skge_table_t* ent,
+                                                 const skge_table_t* rel, int d, const int* trip,
+                                                 int64_t T, const void* set_slots,
+                                                 int64_t set_capacity, int nbatches, uint64_t seed,
+                                                 uint64_t* epoch_key, float margin, int ntries,
+                                                 int* nviol, int* nviol_total,
+                                                 const skge_sampler_t* smp) {
+  if (check_sampler(smp, "runner")) return nullptr;
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
   SampleArgs a;
   // (this runner takes any T and any power-of-two set, as skge_transe_sample_grad does)
   if (fill_sample_args(a, l1, ent, rel, d, trip, T, set_slots, set_capacity, seed, epoch_key,
@@ -494,6 +550,9 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
   r->shards = (int*)r->alloc(NSHARD * SHARD_STRIDE * 4, true);
   if (!r->alloc_ok) return fail("runner: device allocation failed");
   a.vshards = r->shards;
+  // (the runner keeps the pointers only: the caller owns the pools)
+  if (kind != SKGE_SAMPLER_RANDOM)
+    a.pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
   if (!r->begin_capture(st)) return nullptr;
   int rc = SKGE_OK;
   // large batches: when a batch's entity slot records outnumber the table's
@@ -511,7 +570,7 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
     a.neg_out = nullptr;
     int ns[2] = {(int)(4 * b.second), (int)b.second};
     if ((rc = check_slots(ent, ns[0], "ent")) || (rc = check_slots(rel, ns[1], "rel"))) break;
-    if ((rc = launch_sample(a, l1 != 0, st))) break;
+    if ((rc = launch_sample(a, l1 != 0, st, kind))) break;
     skge_table_t at[2] = {tabs[0], tabs[1]};
     if (dense_mode > 0 && ns[0] >= ent->rows) {
       at[0].acc_touched = nullptr;
@@ -525,6 +584,17 @@ extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_ta
     r->nlaunch += 1;
   }
   return r->end_capture(st, rc) ? r.release() : nullptr;
+}
+
+extern "C" skge_runner_t* skge_runner_create(void* stream, int l1, const skge_table_t* ent,
+                                             const skge_table_t* rel, int d, const int* trip,
+                                             int64_t T, const void* set_slots,
+                                             int64_t set_capacity, int nbatches, uint64_t seed,
+                                             uint64_t* epoch_key, float margin, int ntries,
+                                             int* nviol, int* nviol_total) {
+  return skge_runner_create_smp(stream, l1, ent, rel, d, trip, T, set_slots, set_capacity,
+                                nbatches, seed, epoch_key, margin, ntries, nviol, nviol_total,
+                                nullptr);
 }
 
 extern "C" int skge_runner_run(skge_runner_t* r, void* stream, int nepochs) {

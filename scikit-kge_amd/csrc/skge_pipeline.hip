@@ -808,13 +808,32 @@ __global__ void k_epoch_sample(const int* __restrict__ trip, long long T, int ha
 }
 
 // the typed / LCWA samplers' epoch (the pair and logistic loops): an instance
-// of its own per kind, so k_epoch_sample -- RANDOM, the only kind the
-// pipelined runners draw -- stays the kernel it was
+// of its own per kind, so k_epoch_sample -- RANDOM, the pipelined runners'
+// headline draw -- stays the kernel it was (their typed / LCWA draw is
+// k_pipe_sample_pools below)
 template <int KIND>
 __global__ void k_epoch_sample_pools(const int* __restrict__ trip, long long T, int half,
                                      uint64_t seed, const uint64_t* ekp, TripleSet set, Pools pl,
                                      int n_ent, int ntries, int4* rec, int* rec_n1) {
   const uint64_t ek = *ekp;
+  const Perm pm = {(uint64_t)T, half, epoch_perm_key(seed, ek)};
+  const uint64_t skey = epoch_sample_key(seed, ek);
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
+       j += (long long)gridDim.x * blockDim.x)
+    sample_record_pools<KIND>(trip, pm, skey, set, pl, n_ent, ntries, j, rec, rec_n1);
+}
+
+// the pipelined runners' draw launch for the typed / LCWA kinds:
+// k_epoch_sample_pools with k_epoch_sample's two runner duties (block 0
+// writes key_copy; no negative is drawn once *err is set)
+template <int KIND>
+__global__ void k_pipe_sample_pools(const int* __restrict__ trip, long long T, int half,
+                                    uint64_t seed, const uint64_t* ekp, TripleSet set, Pools pl,
+                                    int n_ent, int ntries, int4* rec, int* rec_n1, const int* err,
+                                    uint64_t* key_copy) {
+  const uint64_t ek = *ekp;
+  if (key_copy && blockIdx.x == 0 && threadIdx.x == 0) *key_copy = ek;
+  if (err && *err) ntries = 0;
   const Perm pm = {(uint64_t)T, half, epoch_perm_key(seed, ek)};
   const uint64_t skey = epoch_sample_key(seed, ek);
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
@@ -861,6 +880,26 @@ int launch_epoch_sample(hipStream_t st, const int* trip, long long T, uint64_t s
   }
   SKGE_CHECK_LAUNCH("epoch sample");
   return SKGE_OK;
+}
+
+// The pipelined runners' draw launch: RANDOM is k_epoch_sample as it always
+// was launched; a pool kind its k_pipe_sample_pools instance, same grid.
+void launch_pipe_sample(hipStream_t st, const int* trip, long long T, int half, uint64_t seed,
+                        const uint64_t* epoch_key, TripleSet set, int kind, Pools pl, int n_ent,
+                        int ntries, int4* rec, int* rec_n1, const int* err, uint64_t* key_copy) {
+  long long blocks = (T + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (kind == SAMPLER_TYPED)
+    hipLaunchKernelGGL(k_pipe_sample_pools<SAMPLER_TYPED>, dim3((unsigned)blocks), dim3(256), 0,
+                       st, trip, T, half, seed, epoch_key, set, pl, n_ent, ntries, rec, rec_n1,
+                       err, key_copy);
+  else if (kind == SAMPLER_LCWA)
+    hipLaunchKernelGGL(k_pipe_sample_pools<SAMPLER_LCWA>, dim3((unsigned)blocks), dim3(256), 0, st,
+                       trip, T, half, seed, epoch_key, set, pl, n_ent, ntries, rec, rec_n1, err,
+                       key_copy);
+  else
+    hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, trip, T, half,
+                       seed, epoch_key, set, n_ent, ntries, rec, rec_n1, err, key_copy);
 }
 
 // n negatives per positive over any modes (skge_sampler.h sample_slot): one
@@ -959,6 +998,8 @@ struct skge_pipe_runner : GraphRunnerCore {
   uint64_t* epoch_key = nullptr;   // the caller's word
   uint64_t* key_copy = nullptr;    // graph runners: the word the epoch's launches read
   TripleSet set;
+  int kind = SAMPLER_RANDOM;       // the draw launch's sampler (launch_pipe_sample)
+  Pools pl = {nullptr, nullptr, 0};   // the caller's type index (pool kinds; not owned)
   int4* rec = nullptr;
   int* rec_n1 = nullptr;
   std::vector<PipeArgs> batch;     // nb1 batches + the flush
@@ -1065,13 +1106,9 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
                           int trace_launch = -1, unsigned long long* trace = nullptr) {
   int i = 0;
   if (ev) (void)hipEventRecord(ev[i], st);
-  {
-    long long blocks = (r->T + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_epoch_sample, dim3((unsigned)blocks), dim3(256), 0, st, r->trip, r->T,
-                       r->half, r->seed, (const uint64_t*)r->epoch_key, r->set, r->n_ent,
-                       r->ntries, r->rec, r->rec_n1, (const int*)r->err, r->key_copy);
-  }
+  launch_pipe_sample(st, r->trip, r->T, r->half, r->seed, (const uint64_t*)r->epoch_key, r->set,
+                     r->kind, r->pl, r->n_ent, r->ntries, r->rec, r->rec_n1, (const int*)r->err,
+                     r->key_copy);
   ++i;
   if (ev) (void)hipEventRecord(ev[i], st);
   for (size_t k = 0; k < r->batch.size(); ++k, ++i) {
@@ -1170,8 +1207,74 @@ __global__ void k_ent_occ(const int* __restrict__ trip, long long T, int* occ) {
   }
 }
 
+__global__ void k_rel_occ(const int* __restrict__ trip, long long T, int n_rel, int* occ) {
+  for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
+       j += (long long)gridDim.x * blockDim.x) {
+    const int p = trip[3 * j + 2];
+    if (p >= 0 && p < n_rel) atomicAdd(occ + p, 1);
+  }
+}
+
+// Typed / LCWA draws make hubs through negatives too: a pool of length L
+// receives the corruptions of its relation's cnt_p positives, cnt_p / L per
+// member and epoch (TYPED: pools 2p and 2p + 1; LCWA: pool 2p, and T / N per
+// row from its uniform o-corruptions) -- device.py corruption_load's formula
+// per epoch.  w[row] gets that expected count; false (w untouched, the
+// occurrence-only choice) if a copy fails or the pools are not a CSR of
+// entity ids.
+static bool corruption_weight(hipStream_t st, const skge_sampler_t* smp, const int* trip,
+                              long long T, int N, std::vector<double>& w) {
+  const int nr = smp->n_rel;
+  std::vector<long long> off((size_t)2 * nr + 1);
+  if (hipMemcpy(off.data(), smp->pool_off, off.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return false;
+  if (off[0] < 0) return false;
+  for (size_t q = 0; q + 1 < off.size(); ++q)
+    if (off[q + 1] < off[q]) return false;
+  const long long n0 = off[0], n1 = off.back();
+  if (n1 - n0 > 4ll * T + 4) return false;   // (a pool lists entities of its relation's triples)
+  std::vector<int> ent((size_t)(n1 - n0)), cnt(nr);
+  int* dc = nullptr;
+  if (hipMalloc(&dc, (size_t)nr * 4) != hipSuccess) return false;
+  const unsigned blocks = (unsigned)std::max(1ll, std::min((T + 255) / 256, 4096ll));
+  bool ok = hipMemsetAsync(dc, 0, (size_t)nr * 4, st) == hipSuccess;
+  hipLaunchKernelGGL(k_rel_occ, dim3(blocks), dim3(256), 0, st, trip, T, nr, dc);
+  ok = ok && hipMemcpyAsync(cnt.data(), dc, (size_t)nr * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  (void)hipFree(dc);
+  if (ok && !ent.empty())
+    ok = hipMemcpy(ent.data(), smp->pool_ent + n0, ent.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
+  if (!ok) return false;
+  for (int e : ent)
+    if (e < 0 || e >= N) return false;
+  const int sides = smp->kind == SKGE_SAMPLER_TYPED ? 2 : 1;
+  for (int p = 0; p < nr; ++p)
+    for (int m = 0; m < sides; ++m) {
+      const long long b = off[2 * p + m], e = off[2 * p + m + 1];
+      if (e <= b || cnt[p] == 0) continue;
+      const double share = (double)cnt[p] / (double)(e - b);
+      for (long long i = b; i < e; ++i) w[(size_t)ent[(size_t)(i - n0)]] += share;
+    }
+  if (sides == 1)
+    for (auto& x : w) x += (double)T / N;
+  return true;
+}
+
+// SKGE_PIPE_HOT_NEG=1 counts a pool sampler's expected corruptions into the
+// hot-row choice; the default chooses by occurrences only.  The result never
+// depends on it (hub sums are exact integers), only the launch time -- and
+// measured it costs time: 64 two-entity object pools of 350 occurrences each
+// (below the bar; 700 with their corruptions), WN18 size, d = 200, nb = 100,
+// TYPED, same box, interleaved: 0.848 ms per epoch with no hot row against
+// 1.057 ms with those 128 (profiles/samplers_pipe/), so it stays off
+static bool hot_negatives() {
+  const char* e = getenv("SKGE_PIPE_HOT_NEG");
+  return e ? atoi(e) != 0 : false;
+}
+
 static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const int* trip,
-                          long long T, int nb1, int N, int d, int row_words) {
+                          long long T, int nb1, int N, int d, int row_words,
+                          const skge_sampler_t* smp = nullptr) {
   t.hot = t.hot_rows = nullptr;
   t.nhot = 0;
   int* occ = nullptr;
@@ -1186,11 +1289,17 @@ static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const
   if (!ok) return false;
   // expected slots per batch = occurrences / nb1; the average row's: 2T / N / nb1
   const double bar = std::max((double)HOT_MIN * nb1, (double)HOT_REL * 2.0 * (double)T / N);
-  std::vector<std::pair<int, int>> cand;   // (occurrences, row)
+  // (smp: a pool sampler whose expected corruptions per epoch count as well)
+  std::vector<double> wt(N, 0.0);
+  if (smp && smp->kind != SKGE_SAMPLER_RANDOM) {
+    std::vector<double> w(N, 0.0);
+    if (corruption_weight(st, smp, trip, T, N, w)) wt.swap(w);
+  }
+  std::vector<std::pair<double, int>> cand;   // (occurrences [+ corruptions], row)
   for (int i = 0; i < N; ++i)
-    if ((double)h[i] >= bar) cand.push_back({h[i], i});
+    if ((double)h[i] + wt[i] >= bar) cand.push_back({(double)h[i] + wt[i], i});
   if (cand.empty()) return true;
-  std::sort(cand.begin(), cand.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) {
+  std::sort(cand.begin(), cand.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) {
     return x.first != y.first ? x.first > y.first : x.second < y.second;
   });
   if ((int)cand.size() > HOT_MAX) cand.resize(HOT_MAX);
@@ -1226,7 +1335,10 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
                                        const skge_table_t* rel, int d, const int* trip, int64_t T,
                                        const void* set, int64_t set_capacity, int nbatches,
                                        uint64_t seed, uint64_t* epoch_key, float margin,
-                                       int ntries, int* nviol_total, int flags, bool hole, int af) {
+                                       int ntries, int* nviol_total, int flags, bool hole, int af,
+                                       const skge_sampler_t* smp = nullptr) {
+  if (check_sampler(smp, "pipelined runner")) return nullptr;
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
   if (flags & ~SKGE_PIPE_DP) {
     set_error("pipelined runner: unknown flags %d", flags);
     return nullptr;
@@ -1234,6 +1346,11 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   const bool dp = (flags & SKGE_PIPE_DP) != 0;
   if (dp && hole) {
     set_error("pipelined runner: the data-parallel form is TransE-L1 only");
+    return nullptr;
+  }
+  if (dp && kind != SKGE_SAMPLER_RANDOM) {
+    set_error("pipelined runner: the data-parallel form (SKGE_PIPE_DP) draws RANDOM negatives "
+              "only, not sampler kind %d", kind);
     return nullptr;
   }
   if (!ent || !rel) {
@@ -1278,6 +1395,9 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
   std::unique_ptr<skge_pipe_runner> r(new skge_pipe_runner());
   r->hole = hole;
   r->dp = dp;
+  r->kind = kind;
+  if (kind != SKGE_SAMPLER_RANDOM)
+    r->pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
   // HolE at d = 200 in the FFT form: two waves per positive (the pair form)
   // while the batch's 2 x B scoring waves fit the chip's 4-wave-per-SIMD
   // residency.  WN18 d = 200, same box: nb = 100 93.7 -> 106.7 M triples/s
@@ -1357,7 +1477,8 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
       // (the data-parallel form keeps every row in the tables: no hot rows;
       // HolE: the pair form only, fp32 sums of d floats per replica row)
       if (r->alloc_ok && !r->e8 && !dp && (!hole || (hole_pair && SKGE_HPIPE_HOT)))
-        ok = find_hot_rows(r.get(), as_stream(stream), t, trip, T, nb1, N, d, hole ? d / 2 : nq);
+        ok = find_hot_rows(r.get(), as_stream(stream), t, trip, T, nb1, N, d, hole ? d / 2 : nq,
+                           hot_negatives() ? smp : nullptr);
     }
     RelTab& q = a.R;
     const int M = rel->rows;
@@ -1512,6 +1633,45 @@ extern "C" skge_pipe_runner_t* skge_hole_pipe_runner_create(
     uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total) {
   return pipe_create(stream, ent, rel, d, trip, T, set, set_capacity, nbatches, seed, epoch_key,
                      margin, ntries, nviol_total, 0, true, af);
+}
+
+extern "C" skge_pipe_runner_t* skge_pipe_runner_create_smp(
+    void* stream, const skge_table_t* ent, const skge_table_t* rel, int d, const int* trip,
+    int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
+    uint64_t* epoch_key, float margin, int ntries, int* nviol_total, int flags,
+    const skge_sampler_t* smp) {
+  return pipe_create(stream, ent, rel, d, trip, T, set, set_capacity, nbatches, seed, epoch_key,
+                     margin, ntries, nviol_total, flags, false, 0, smp);
+}
+
+extern "C" skge_pipe_runner_t* skge_hole_pipe_runner_create_smp(
+    void* stream, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
+    uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total,
+    const skge_sampler_t* smp) {
+  return pipe_create(stream, ent, rel, d, trip, T, set, set_capacity, nbatches, seed, epoch_key,
+                     margin, ntries, nviol_total, 0, true, af, smp);
+}
+
+extern "C" int skge_pipe_epoch_sample(void* stream, const int* trip, int64_t T, const void* set,
+                                      int64_t set_capacity, int n_ent, uint64_t seed,
+                                      const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1,
+                                      const skge_sampler_t* smp, const int* err,
+                                      uint64_t* key_copy) {
+  SKGE_CHECK_ARG(trip && set && epoch_key && rec && rec_n1, "NULL argument");
+  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
+  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
+                 "set capacity must be a power of 2 >= 2T");
+  SKGE_CHECK_ARG(n_ent > 0 && ntries >= 0, "bad n_ent / ntries");
+  if (int rc = check_sampler(smp, "pipelined epoch sample")) return rc;
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
+  Pools pl = {nullptr, nullptr, 0};
+  if (kind != SKGE_SAMPLER_RANDOM) pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
+  launch_pipe_sample(as_stream(stream), trip, T, perm_half(T), seed, epoch_key,
+                     triple_set_view(set, set_capacity), kind, pl, n_ent, ntries, (int4*)rec,
+                     rec_n1, err, key_copy);
+  SKGE_CHECK_LAUNCH("pipelined epoch sample");
+  return SKGE_OK;
 }
 
 extern "C" skge_pipe_runner_t* skge_pipe_runner_create(void* stream, const skge_table_t* ent,

@@ -116,9 +116,9 @@ __device__ __forceinline__ bool pool_contains(const int* __restrict__ ent, long 
   return lo < end && ent[lo] == c;
 }
 
-// sample_record for the typed (KIND == SAMPLER_TYPED) and LCWA samplers: the
-// same record, counter use and first-accepted-try rule; only what a try draws
-// and what accepts it differ.
+// The typed (KIND == SAMPLER_TYPED) and LCWA samplers' negatives of positive
+// (s, o, p) at position j: sample_record's counter use and first-accepted-try
+// rule; only what a try draws and what accepts it differ.
 //   TYPED, mode m: c = pool[2p + m][draw(skey, j, m, tr, L)], L the pool's
 //     length (L == 0 draws nothing), accepted if the corrupted triple is not
 //     a training triple (skge/sample.py:82-85).
@@ -134,12 +134,9 @@ __device__ __forceinline__ bool pool_contains(const int* __restrict__ ent, long 
 // the slow one of the three kinds.
 // A relation id outside [0, n_rel) has no pools: no pool negative is drawn.
 template <int KIND>
-__device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip, const Perm& pm,
-                                                    uint64_t skey, const TripleSet& set,
-                                                    const Pools& pl, int n_ent, int ntries,
-                                                    long long j, int4* rec, int* rec_n1) {
-  const long long t = (long long)perm_index((uint64_t)j, pm);
-  const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
+__device__ __forceinline__ void draw_pools(uint64_t skey, const TripleSet& set, const Pools& pl,
+                                           int n_ent, int ntries, long long j, int s, int o, int p,
+                                           int& neg0, int& neg1) {
   const bool has = p >= 0 && p < pl.n_rel;
   long long b0 = 0, e0 = 0, b1 = 0, e1 = 0;
   if (has) {
@@ -147,7 +144,7 @@ __device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip
     e0 = b1 = pl.off[2 * p + 1];
     if (KIND == SAMPLER_TYPED) e1 = pl.off[2 * p + 2];
   }
-  int neg0 = -1, neg1 = -1;
+  neg0 = neg1 = -1;
   if (e0 > b0) {
     const int L = (int)(e0 - b0);
     for (int tr = 0; tr < ntries; ++tr) {
@@ -184,6 +181,20 @@ __device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip
       }
     }
   }
+}
+
+// the record of the epoch's positive j drawn with draw_pools (sample_record's
+// layout); the two-launch TransE kernels call draw_pools themselves, one
+// positive per wave, so every runner draws the same bits
+template <int KIND>
+__device__ __forceinline__ void sample_record_pools(const int* __restrict__ trip, const Perm& pm,
+                                                    uint64_t skey, const TripleSet& set,
+                                                    const Pools& pl, int n_ent, int ntries,
+                                                    long long j, int4* rec, int* rec_n1) {
+  const long long t = (long long)perm_index((uint64_t)j, pm);
+  const int s = trip[3 * t], o = trip[3 * t + 1], p = trip[3 * t + 2];
+  int neg0, neg1;
+  draw_pools<KIND>(skey, set, pl, n_ent, ntries, j, s, o, p, neg0, neg1);
   rec[j] = make_int4(s, o, p, neg0);
   rec_n1[j] = neg1;
 }

@@ -115,6 +115,8 @@ SIGNATURES = {
     "skge_epoch_advance": (c_i, [c_p, c_p]),
     "skge_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p,
                                  c_f, c_i, c_p, c_p]),
+    "skge_runner_create_smp": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
+                                     c_p, c_f, c_i, c_p, c_p, S_P]),
     "skge_runner_run": (c_i, [c_p, c_p, c_i]),
     "skge_runner_nlaunches": (c_i, [c_p]),
     "skge_runner_destroy": (None, [c_p]),
@@ -147,6 +149,12 @@ SIGNATURES = {
                                          c_p, c_f, c_i, c_p, c_i]),
     "skge_hole_pipe_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i,
                                            c_u64, c_p, c_f, c_i, c_p]),
+    "skge_pipe_runner_create_smp": (c_p, [c_p, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
+                                          c_p, c_f, c_i, c_p, c_i, S_P]),
+    "skge_hole_pipe_runner_create_smp": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,
+                                               c_i, c_u64, c_p, c_f, c_i, c_p, S_P]),
+    "skge_pipe_epoch_sample": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i, c_u64, c_p, c_i, c_p, c_p,
+                                     S_P, c_p, c_p]),
     "skge_pipe_runner_run": (c_i, [c_p, c_p, c_i]),
     "skge_pipe_runner_error": (c_i, [c_p, c_p]),
     "skge_pipe_runner_profile": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_i64]),

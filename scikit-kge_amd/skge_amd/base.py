@@ -431,7 +431,8 @@ class PairwiseStochasticTrainer(StochasticTrainer):
     (with device_loop: n negatives per positive over any modes from {0, 1, 2}
     drawn on the device; off, only (1, [0, 1]) is), ``device_runner``
     ('auto', 'epoch': TransE's fused runners, 'pairs': the any-model pair
-    loop), ``seed`` (device sampler / permutation key), ``ntries``."""
+    loop, 'pipe': TransE's / HolE's pipelined runner drawing the sampler's own
+    kind, typed and LCWA included), ``seed`` (device sampler / permutation key), ``ntries``."""
 
     def __init__(self, *args, **kwargs):
         self.device_loop = kwargs.pop("device_loop", False)

@@ -82,7 +82,44 @@ def _row_counts(col, n):
     return torch.bincount(col.long(), minlength=n)
 
 
-def packed_count_bound(kg, n_ent, batch, tail=None):
+def corruption_load(kind, pool_off, pool_ent, rel_counts, n_ent, batch, T):
+    """Expected corruptions per batch of every entity row, float64 [n_ent] on
+    the pools' device (pure tensor arithmetic: CPU tensors stay on the CPU).
+    kind: SKGE_SAMPLER_*; pool_off [2 * n_rel + 1] / pool_ent: the type index
+    (DeviceKG.pools); rel_counts [n_rel]: triples per relation; batch
+    positives of the T triples per batch.
+      RANDOM  both modes draw an entity uniformly: 2 batch / n_ent per row.
+      TYPED   mode m of a positive of relation p draws uniformly from pool
+              2p + m: a batch holds cnt_p batch / T positives of p, so a row
+              gets cnt_p batch / (T L) from every pool of length L it is in.
+      LCWA    mode 0 accepts candidates of pool 2p only, uniform over it (the
+              TYPED share of pool 2p); mode 1 is RANDOM's: batch / n_ent.
+    An empty pool draws nothing.  Rejected tries are not discounted (an upper
+    estimate: a try that hits a training triple is redrawn from the same
+    pool)."""
+    n_ent, batch, T = int(n_ent), float(batch), float(max(int(T), 1))
+    if kind == L.SKGE_SAMPLER_RANDOM:
+        dev = pool_off.device if torch.is_tensor(pool_off) else None
+        return torch.full((n_ent,), 2.0 * batch / max(n_ent, 1), dtype=torch.float64, device=dev)
+    if kind not in (L.SKGE_SAMPLER_TYPED, L.SKGE_SAMPLER_LCWA):
+        raise ValueError("unknown sampler kind %r" % (kind,))
+    off = torch.as_tensor(pool_off).long()
+    ent = torch.as_tensor(pool_ent, device=off.device).long()
+    cnt = torch.as_tensor(rel_counts, device=off.device).double()
+    lens = off[1:] - off[:-1]
+    if lens.numel() != 2 * cnt.numel():
+        raise ValueError("pool_off needs 2 * n_rel + 1 entries for %d relations" % cnt.numel())
+    share = cnt.repeat_interleave(2) * (batch / T) / lens.clamp(min=1).double()
+    if kind == L.SKGE_SAMPLER_LCWA:
+        share[1::2] = 0.0
+    load = torch.zeros(n_ent, dtype=torch.float64, device=off.device)
+    load.index_add_(0, ent[int(off[0]):int(off[-1])], share.repeat_interleave(lens))
+    if kind == L.SKGE_SAMPLER_LCWA:
+        load += batch / max(n_ent, 1)
+    return load
+
+
+def packed_count_bound(kg, n_ent, batch, tail=None, sampler=L.SKGE_SAMPLER_RANDOM, n_rel=None):
     """Upper bound on an ENTITY row's per-batch occurrence count in the
     TransE-L1 device loops (the count bounds every 16-bit field of its packed
     sums, csrc/skge_pipeline.hip).  A positive adds at most 3 to each of its s
@@ -96,9 +133,14 @@ def packed_count_bound(kg, n_ent, batch, tail=None):
     count alone sent skewed KGs to fp32 sums at every batch past ~3k);
     likewise as object.  The corruptions are uniform draws over the entities
     (skge/sample.py:41-46), bounded by their Poisson tail (lambda + 12
-    sqrt(lambda) + 40, lambda = 2 batch / n_ent).  The applies still check
-    every row's count at run time (ERR_PACKED), and device_optim reads that
-    flag after every epoch."""
+    sqrt(lambda) + 40, lambda = 2 batch / n_ent).  The typed and LCWA samplers
+    (sampler=, with n_rel= the model's relation count) draw from pools instead:
+    a row's corruptions have the mean corruption_load() gives it -- a
+    two-entity pool takes every corruption of its relation -- so the bound is
+    per row, max over rows of (3 x its occurrences + the tail of its load):
+    the row with the most occurrences need not be the one with the largest
+    load.  The applies still check every row's count at run time (ERR_PACKED),
+    and device_optim reads that flag after every epoch."""
     T = float(max(int(kg.trip.shape[0]), 1))
     B = float(min(int(batch), int(kg.trip.shape[0])))
 
@@ -107,6 +149,16 @@ def packed_count_bound(kg, n_ent, batch, tail=None):
         mu = c * (B / T)
         return torch.minimum(torch.minimum(c, torch.full_like(c, B)), (tail or _tail)(mu))
     occ = per_batch(kg.trip[:, 0]) + per_batch(kg.trip[:, 1])
+    if sampler != L.SKGE_SAMPLER_RANDOM:
+        if n_rel is None:
+            raise ValueError("the typed and LCWA samplers need the model's relation count")
+        off, ent = kg.pools(n_rel)
+        load = corruption_load(sampler, off, ent, _row_counts(kg.trip[:, 2], int(n_rel)), n_ent,
+                               batch, kg.trip.shape[0])
+        cap = float(2 * int(batch))
+        rows = 3.0 * torch.clamp(torch.ceil(occ), max=cap) + \
+            torch.clamp(torch.ceil((tail or _tail)(load)), max=cap)
+        return int(rows.max().item())
     det = 3 * min(int(math.ceil(float(occ.max().item()))), 2 * int(batch))
     lam = 2.0 * batch / max(n_ent, 1)
     corr = min(2 * int(batch), int(math.ceil((tail or _tail)(lam))))
@@ -426,15 +478,19 @@ class EpochRunner(_PaddedTables, _PipeRunner):
     _packed_hint = "; use force_f32=True"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 nviol_total=None, force_f32=False, replicas=1, pipelined=None, packed=None):
+                 nviol_total=None, force_f32=False, replicas=1, pipelined=None, packed=None,
+                 sampler=L.SKGE_SAMPLER_RANDOM):
         from .transe import TransE
         if not isinstance(model, TransE):
             raise NotImplementedError("device_loop supports TransE (the north-star path) only")
         dev = model.device
-        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
         self.nviol_total = self._total(nviol_total, torch.int32)
         self._hold_state(updaters)
         bs = kg.T // nbatches
+        # the per-batch count bound of this runner's sampler kind
+        bound = lambda tail=None: packed_count_bound(kg, model.E.rows, bs, tail,
+                                                     sampler=self.sampler, n_rel=model.sz[2])
         self.hot_rows = 0   # pipelined TransE: entity rows with replicated sums (skewed KGs)
         # d % 4 != 0 (e.g. the reference's d = 50): the packed / pipelined
         # runners work on quads, so they run on zero-padded copies of the
@@ -450,7 +506,7 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         # sums while every row's per-batch count stays <= 32767 (the applies
         # flag a larger count, checked by synchronize())
         can_pack = bool(model.l1) and (model.d % 4 == 0 or self._pad) and not force_f32
-        self.count_bound = packed_count_bound(kg, model.E.rows, bs) if can_pack else 0
+        self.count_bound = bound() if can_pack else 0
         auto_packed = packed is None
         if packed is None:
             packed = can_pack and self.count_bound <= PACKED_MAX
@@ -480,7 +536,7 @@ class EpochRunner(_PaddedTables, _PipeRunner):
                 acc = E.rows * (E.width * 2 + 4) + 4 * 4 * bs
                 extra = 3 * acc + kg.T * 20 + (64 << 20) + E.rows * (16 + 8 * E.width)
             else:
-                e8_est = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
+                e8_est = (bound(_tail8) <= 127 and
                           _os.environ.get("SKGE_PIPE_E8", "1") != "0")
                 acc = E.rows * ((wd // 4) * (4 if e8_est else 8) + 4) + 2 * 4 * 4 * bs
                 extra = 2 * acc + E.rows * 5 * 4 + kg.T * 20 + (256 << 20)
@@ -491,15 +547,19 @@ class EpochRunner(_PaddedTables, _PipeRunner):
             # fits them (faster: half the atomics), else int32x2; entity sums in
             # 8-bit fields while every entity's per-batch count is <= 127 (half
             # the atomic bytes again; the apply checks every count)
-            e8 = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
+            e8 = (bound(_tail8) <= 127 and
                   _os.environ.get("SKGE_PIPE_E8", "1") != "0")
             self._tables(model, updaters, packed, 1, rel_w32=rel_reps != 1, ent_i8=e8,
                          pad=self._pad)
             self.ent_i8 = e8
             try:
-                self._create("skge_pipe_runner", self.te, self.tr,
-                             self.d_pad if self._pad else model.d, *self._epoch_args(),
-                             float(model.margin), self.ntries, L.ptr(self.nviol_total))
+                args = (self.te, self.tr, self.d_pad if self._pad else model.d) + \
+                    self._epoch_args() + (float(model.margin), self.ntries, L.ptr(self.nviol_total))
+                if self._smp is None:
+                    self._create("skge_pipe_runner", *args)
+                else:   # the typed / LCWA draw launch (flags 0)
+                    self._create("skge_pipe_runner", *(args + (0, self._smp)),
+                                 create="skge_pipe_runner_create_smp")
                 self.hot_rows = lib.skge_pipe_runner_hot_rows(self.handle)
                 self.kernel = ("k_pipe_batch",
                                "k_pipe_fused")[lib.skge_pipe_runner_kernel(self.handle)]
@@ -522,9 +582,12 @@ class EpochRunner(_PaddedTables, _PipeRunner):
                                  "accumulator copies hold; use packed=None or force_f32=True")
             packed = False
         self._tables(model, updaters, packed, max(int(replicas), rel_reps) if packed else replicas)
-        self._create("skge_runner", int(bool(model.l1)), self.te, self.tr, model.d,
-                     *self._epoch_args(), float(model.margin), self.ntries, None,
-                     L.ptr(self.nviol_total))
+        args = (int(bool(model.l1)), self.te, self.tr, model.d) + self._epoch_args() + \
+            (float(model.margin), self.ntries, None, L.ptr(self.nviol_total))
+        if self._smp is None:
+            self._create("skge_runner", *args)
+        else:
+            self._create("skge_runner", *(args + (self._smp,)), create="skge_runner_create_smp")
 
     def synchronize(self):
         if self.pipelined:
@@ -546,13 +609,13 @@ class HolePipeRunner(_PipeRunner):
     _who = "pipelined HolE runner"
 
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
-                 nviol_total=None):
+                 nviol_total=None, sampler=L.SKGE_SAMPLER_RANDOM):
         from .hole import HolE
         from .param import Accumulator
         if not isinstance(model, HolE):
             raise TypeError("HolePipeRunner trains HolE")
         dev = model.device
-        self._setup(model, kg, nbatches, seed, ntries, stream)
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
         self.nviol_total = self._total(nviol_total, torch.int32)
         self._hold_state(updaters)
         E, R = model.params["E"], model.params["R"]
@@ -564,9 +627,13 @@ class HolePipeRunner(_PipeRunner):
                                       rout=reg["E"][1], fixed_div=reg["E"][2])
         self.tr = updaters["R"].table(self.accR, counters=False, rin=reg["R"][0],
                                       rout=reg["R"][1], fixed_div=reg["R"][2])
-        self._create("skge_pipe_runner", model._af_code(), self.te, self.tr, model.d,
-                     *self._epoch_args(), float(model.margin), self.ntries,
-                     L.ptr(self.nviol_total), create="skge_hole_pipe_runner_create")
+        args = (model._af_code(), self.te, self.tr, model.d) + self._epoch_args() + \
+            (float(model.margin), self.ntries, L.ptr(self.nviol_total))
+        if self._smp is None:
+            self._create("skge_pipe_runner", *args, create="skge_hole_pipe_runner_create")
+        else:
+            self._create("skge_pipe_runner", *(args + (self._smp,)),
+                         create="skge_hole_pipe_runner_create_smp")
         # hub rows (pair form, skewed KGs)
         self.hot_rows = L.lib().skge_pipe_runner_hot_rows(self.handle)
 
@@ -742,13 +809,32 @@ def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=N
                 runner="auto", sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
     """runner: 'auto' (TransE -> EpochRunner, the fused sampler/score runners;
     HolE -> HolePipeRunner where it applies, RESCAL -> PairLoopRunner),
-    'epoch', 'hole_pipe' or 'pairs'.  sampler: the kind of negatives
-    (SKGE_SAMPLER_*); the fused and pipelined runners draw RANDOM only, so the
-    typed and LCWA kinds run the pair loop for every model.  negatives: the
+    'epoch', 'hole_pipe', 'pairs' or 'pipe'.  sampler: the kind of negatives
+    (SKGE_SAMPLER_*); under 'auto' (and by the names 'epoch' / 'hole_pipe')
+    the fused and pipelined runners draw RANDOM only, so the typed and LCWA
+    kinds run the pair loop for every model.  'pipe' is the model's throughput
+    runner with whatever kind the sampler is: TransE -> EpochRunner(sampler=),
+    an eligible HolE -> HolePipeRunner(sampler=); anything else (RESCAL, a
+    HolE outside the runner's widths, n or modes other than (1, [0, 1])) is
+    refused and needs 'pairs'.  negatives: the
     sampler's (n, modes, rel_range) (None: (1, [0, 1])); the fused and
     pipelined runners draw (1, [0, 1]) only, so any other runs the pair loop."""
     from .transe import TransE
     from .base import deterministic
+    if runner == "pipe":
+        if negatives is not None and (int(negatives[0]), list(negatives[1])) != (1, [0, 1]):
+            raise ValueError("device runner 'pipe' draws one negative per mode of [0, 1] only; "
+                             "n = %r, modes = %r need 'pairs' (or 'auto')"
+                             % (negatives[0], list(negatives[1])))
+        if isinstance(model, TransE):
+            return EpochRunner(model, updaters, kg, nbatches, seed=seed, ntries=ntries,
+                               nviol_total=nviol_total, sampler=sampler)
+        if HolePipeRunner.eligible(model) and not deterministic():
+            return HolePipeRunner(model, updaters, kg, nbatches, seed=seed, ntries=ntries,
+                                  nviol_total=nviol_total, sampler=sampler)
+        raise ValueError("device runner 'pipe' is TransE's or HolE's (d %% 4 == 0, 4 <= d <= 256, "
+                         "not deterministic) pipelined runner; %s needs 'pairs' (or 'auto')"
+                         % type(model).__name__)
     if sampler != L.SKGE_SAMPLER_RANDOM:
         if runner not in ("auto", "pairs"):
             raise ValueError("device runner %r draws RandomModeSampler negatives only; the typed "
