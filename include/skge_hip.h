@@ -42,8 +42,20 @@ enum {
   SKGE_ENOTSUP = -3   /* unsupported configuration (e.g. d > 1024) */
 };
 
-/* models (skge/transe.py, skge/hole.py, skge/rescal.py) */
-enum { SKGE_TRANSE_L1 = 0, SKGE_TRANSE_L2 = 1, SKGE_HOLE = 2, SKGE_RESCAL = 3 };
+/* models (skge/transe.py, skge/hole.py, skge/rescal.py; DistMult and ComplEx:
+ * HolE's tables and conventions with the trilinear score, csrc/skge_diag.h).
+ * Code 4 is unassigned: every entry point accepts 0..3, 5 and 6 -- not
+ * "<= 6" -- and answers 4 with SKGE_EINVAL like any unknown code.
+ * skge_subgraph_rank takes 0..3 only.  SKGE_COMPLEX needs an even d: a row
+ * holds d/2 complex components interleaved, (re, im) = (x[2j], x[2j+1]). */
+enum {
+  SKGE_TRANSE_L1 = 0,
+  SKGE_TRANSE_L2 = 1,
+  SKGE_HOLE = 2,
+  SKGE_RESCAL = 3,
+  SKGE_DISTMULT = 5,
+  SKGE_COMPLEX = 6
+};
 /* activation functions (skge/actfun.py:13-57) */
 enum { SKGE_AF_LINEAR = 0, SKGE_AF_SIGMOID = 1, SKGE_AF_TANH = 2, SKGE_AF_RELU = 3 };
 /* updaters (skge/param.py:124-155) */

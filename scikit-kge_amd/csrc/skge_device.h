@@ -14,7 +14,7 @@
 
 namespace skge {
 
-enum Model : int { TRANSE_L1 = 0, TRANSE_L2 = 1, HOLE = 2, RESCAL = 3 };
+enum Model : int { TRANSE_L1 = 0, TRANSE_L2 = 1, HOLE = 2, RESCAL = 3, DISTMULT = 5, COMPLEX = 6 };
 enum Act : int { AF_LINEAR = 0, AF_SIGMOID = 1, AF_TANH = 2, AF_RELU = 3 };
 enum Opt : int { OPT_SGD = 0, OPT_ADAGRAD = 1 };
 enum Post : int { POST_NONE = 0, POST_NORMALIZE = 1, POST_NORMLESS1 = 2 };

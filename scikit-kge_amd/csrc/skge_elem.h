@@ -48,11 +48,25 @@ __device__ __forceinline__ float cconv_direct_k(const float* a, const float* b, 
 //   TransE   ea + rp                           ea - rp
 //   HolE     cconv(rp, ea)                     ccorr(rp, ea)
 //   RESCAL   (ea W)_k = sum_j ea[j] W[j][k]    (W ea)_k = sum_j W[k][j] ea[j]
-// every sum one fma chain in ascending j.
+//   DistMult ea[k] rp[k]                       ea[k] rp[k]
+//   ComplEx  (ea * rp)_k                       (conj(rp) * ea)_k
+// every sum one fma chain in ascending j.  ComplEx (skge_diag.h): * is the
+// complex product over the interleaved components, (re, im) = (x[2j], x[2j+1]),
+// d even; the tail form is d phi / d o, the head form d phi / d s.  With E_o
+// for the anchor and E_s for the relation row the head form is d phi / d r,
+// the relation query (skge_relation.hip).
 __device__ __forceinline__ float query_elem(int model, bool tail, const float* ea, const float* rp,
                                             const float* W, int d, int k) {
   if (model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2) return tail ? ea[k] + rp[k] : ea[k] - rp[k];
   if (model == SKGE_HOLE) return tail ? cconv_direct_k(rp, ea, d, k) : ccorr_direct_k(rp, ea, d, k);
+  if (model == SKGE_DISTMULT) return ea[k] * rp[k];
+  if (model == SKGE_COMPLEX) {
+    const int kp = k ^ 1;   // the component's other half
+    if (k & 1)   // im: Re a Im r + Im a Re r   |   Re r Im a - Im r Re a
+      return tail ? fmaf(ea[kp], rp[k], ea[k] * rp[kp]) : fmaf(rp[kp], ea[k], -(rp[k] * ea[kp]));
+    // re: Re a Re r - Im a Im r   |   Re r Re a + Im r Im a
+    return tail ? fmaf(ea[k], rp[k], -(ea[kp] * rp[kp])) : fmaf(rp[k], ea[k], rp[kp] * ea[kp]);
+  }
   float c = 0.0f;
   for (int j = 0; j < d; ++j)
     c = tail ? fmaf(ea[j], W[(size_t)j * d + k], c) : fmaf(W[(size_t)k * d + j], ea[j], c);

@@ -290,7 +290,7 @@ extern "C" int skge_rank_known(void* stream, int model, const float* E, const fl
                                const int* tail_ent, const int* head_off, const int* head_ent,
                                void* workspace, size_t ws_bytes, int* ranks_out) {
   SKGE_CHECK_ARG(E && R && queries && ranks_out && tail_off && head_off, "NULL argument");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && nq >= 0, "bad sizes (d <= 1024)");
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_rank_known_workspace_bytes(nq, d),
@@ -322,7 +322,7 @@ extern "C" int skge_rank(void* stream, int model, const float* E, const float* R
                          const int* queries, int nq, const void* set, int64_t set_capacity,
                          void* workspace, size_t ws_bytes, int* ranks_out) {
   SKGE_CHECK_ARG(E && R && queries && ranks_out, "NULL argument");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && nq >= 0, "bad sizes (d <= 1024)");
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_rank_workspace_bytes(nq, d),

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <vector>
 
+#include "skge_diag.h"
 #include "skge_hole.h"
 #include "skge_hole_fft.h"
 #include "skge_host.h"
@@ -468,6 +469,47 @@ __device__ __forceinline__ bool rescal_pair(const PairArgs& a, int i, float* sw,
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// DistMult / ComplEx pair (skge_diag.h): HolE's conventions -- violation
+// f(n) + margin > f(p), gp = -g(f(p)), gn = g(f(n)), relation rows (pp, pn),
+// entity rows (sp, sn) and (op, on), rows on one id merged -- with
+//   score  E[s] . (conj(R[p]) * E[o])
+//   R[p] <- g conj(E[s]) * E[o]    E[s] <- g conj(R[p]) * E[o]    E[o] <- g E[s] * R[p]
+// Registers only: no LDS.
+// ---------------------------------------------------------------------------
+template <int MODEL, int KM>
+__device__ __forceinline__ bool diag_pair(const PairArgs& a, int i, const int (&ix)[6]) {
+  const int d = a.d;
+  const int sp = ix[0], op = ix[1], pp = ix[2], sn = ix[3], on = ix[4], pn = ix[5];
+  float es[KM], eo[KM], rp[KM], fs[KM], fo[KM], rn[KM];
+  load_row<KM>(a.E, sp, d, es);
+  load_row<KM>(a.E, op, d, eo);
+  load_row<KM>(a.R, pp, d, rp);
+  load_row<KM>(a.E, sn, d, fs);
+  load_row<KM>(a.E, on, d, fo);
+  load_row<KM>(a.R, pn, d, rn);
+  float u[KM], v[KM];
+  diag_cmul<MODEL, KM>(rp, eo, u);   // d phi / d s of the positive
+  diag_cmul<MODEL, KM>(rn, fo, v);   // ... of the negative
+  const float praw = diag_dot<KM>(es, u), nraw = diag_dot<KM>(fs, v);
+  if (lane_id() == 0) {
+    if (a.pscore) a.pscore[i] = praw;
+    if (a.nscore) a.nscore[i] = nraw;
+  }
+  const float pf = af_f(a.af, praw), nf = af_f(a.af, nraw);
+  if (!(nf + a.margin > pf)) return false;
+  const float gp = -af_g_given_f(a.af, pf);
+  const float gn = af_g_given_f(a.af, nf);
+  diag_acc_pair<KM>(a.accE, sp, gp, u, sn, gn, v, d);
+  diag_mul<MODEL, KM>(es, rp, u);    // d phi / d o
+  diag_mul<MODEL, KM>(fs, rn, v);
+  diag_acc_pair<KM>(a.accE, op, gp, u, on, gn, v, d);
+  diag_cmul<MODEL, KM>(es, eo, u);   // d phi / d r
+  diag_cmul<MODEL, KM>(fs, fo, v);
+  diag_acc_pair<KM>(replica(a.accR, i), pp, gp, u, pn, gn, v, d);
+  return true;
+}
+
 // E.violations[u] += 1 for each distinct u in {sn, on, sp, op} of a violating
 // pair (skge/transe.py:78-83): lane j < 4 takes one entity and counts it
 // unless an earlier lane holds the same id
@@ -503,6 +545,8 @@ __global__ __launch_bounds__(256) void k_pair_grad(PairArgs a) {
       v = transe_pair<KM, false>(a, i, ix);
     else if (MODEL == HOLE)
       v = hole_pair<KM>(a, i, sw, ix);
+    else if constexpr (is_diag(MODEL))
+      v = diag_pair<MODEL, KM>(a, i, ix);
     else
       v = rescal_pair<KM>(a, i, sw, ix);
     const Accum aR = replica(a.accR, i);   // dense relation tables may spread over copies
@@ -864,6 +908,167 @@ int launch_hole_pos(hipStream_t st, int af, const skge_table_t* ent, const skge_
 }
 
 // ---------------------------------------------------------------------------
+// DistMult / ComplEx pairwise, one positive and BOTH of its pairs per wave
+// (device pair loop; records as for k_hole_pos: pair 2j = ((s,o,p), (s',o,p)),
+// pair 2j+1 = ((s,o,p), (s,o',p))).  The wave reads E[s], E[o], R[p] once and
+// one entity row per corruption -- 5 row reads where the explicit pairs make
+// 12 -- forms A = conj(R[p]) * E[o] and C = E[s] * R[p] once, and scores
+//   f(s,o,p) = E[s] . A,   f(s',o,p) = E[s'] . A,   f(s,o',p) = E[s] . B,
+//   B = conj(R[p]) * E[o']
+// with diag_pair's arithmetic, so the margin decisions are the pair path's.
+// A violating pair's rows are diag_pair's, each with its own rounding
+// (diag_acc_pair: ids that coincide within a pair are merged there -- always
+// (o, o) and (p, p) of pair 2j, (s, s) and (p, p) of pair 2j+1):
+//   E[s] : [v0] gp A (+ g0 A if s' == s)   + [v1] (gp A + g1 B)
+//   E[o] : [v0] (gp C + g0 E[s'] * R[p])   + [v1] gp C (+ g1 C if o' == o)
+//   R[p] : [v0] (gp D + g0 conj(E[s']) * E[o]) + [v1] (gp D + g1 conj(E[s]) * E[o'])
+//   E[s']: g0 A     E[o']: g1 C            (D = conj(E[s]) * E[o])
+// and the two terms of a row go out as ONE add per element (diag_acc_row2):
+// the float sum, or in the deterministic mode the sum of the two fixed-point
+// roundings, which is bit for bit what the explicit pairs add.  Entity slots
+// 4j..4j+3 name (s, o, s', o'), relation slot j names p, with the counts
+// commit_pair gives the two pairs.
+// ---------------------------------------------------------------------------
+struct DiagPosArgs {
+  const float* E;
+  const float* R;
+  Accum accE, accR;
+  const int4* rec;   // the epoch's records (s, o, p, s' or -1)
+  const int* rec_n1; // o' or -1
+  long long start;   // this batch: positives [start, start + count)
+  int count, d, af;
+  float margin;
+  int* nviol;        // this batch's gate word: += violating pairs
+};
+
+template <int MODEL, int KM>
+__global__ __launch_bounds__(256) void k_diag_pos(DiagPosArgs a) {
+  const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6, l = lane_id();
+  const int d = a.d;
+  int nv = 0;
+  for (int j = blockIdx.x * wpb + wave; j < a.count; j += gridDim.x * wpb) {
+    const int4 r4 = a.rec[a.start + j];
+    const int s = uni(r4.x), o = uni(r4.y), p = uni(r4.z), neg0 = uni(r4.w);
+    const int neg1 = uni(a.rec_n1[a.start + j]);
+    // a corruption that was not drawn reads the row it would have replaced
+    const int n0r = neg0 >= 0 ? neg0 : s, n1r = neg1 >= 0 ? neg1 : o;
+    float es[KM], eo[KM], rp[KM], fs[KM], fo[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.E, o, d, eo);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, n0r, d, fs);
+    load_row<KM>(a.E, n1r, d, fo);
+    float A[KM], B[KM];
+    diag_cmul<MODEL, KM>(rp, eo, A);
+    diag_cmul<MODEL, KM>(rp, fo, B);
+    const float praw = diag_dot<KM>(es, A), raw0 = diag_dot<KM>(fs, A);
+    const float raw1 = diag_dot<KM>(es, B);
+    const float pf = af_f(a.af, praw), f0 = af_f(a.af, raw0), f1 = af_f(a.af, raw1);
+    const int v0 = uni((neg0 >= 0 && f0 + a.margin > pf) ? 1 : 0);
+    const int v1 = uni((neg1 >= 0 && f1 + a.margin > pf) ? 1 : 0);
+    const bool ms = neg0 == s, mo = neg1 == o;   // a corruption that drew the id it replaces
+    const Accum aR = replica(a.accR, j);
+    if (l < 4)
+      commit_slot(a.accE,
+                  sel4(l, s, o, neg0, neg1),
+                  sel4(l, v0 * (ms ? 2 : 1) + 2 * v1, 2 * v0 + v1 * (mo ? 2 : 1), ms ? 0 : v0,
+                       mo ? 0 : v1),
+                  4 * j + l);
+    else if (l == 4)
+      commit_slot(aR, p, 2 * (v0 + v1), j);
+    if (v0 + v1 == 0) continue;
+    nv += v0 + v1;
+    const float gp = -af_g_given_f(a.af, pf);
+    const float g0 = af_g_given_f(a.af, f0), g1 = af_g_given_f(a.af, f1);
+    float x[KM], y[KM], t[KM];
+    // E[s] and E[s']
+    if (ms) diag_axpby<KM>(x, gp, A, g0, A);
+    else diag_scale<KM>(x, gp, A);
+    diag_axpby<KM>(y, gp, A, g1, B);
+    diag_acc_row2<KM>(a.accE, s, x, v0 != 0, y, v1 != 0, d);
+    if (v0 && !ms) {
+      diag_scale<KM>(x, g0, A);
+      acc_row<KM>(a.accE, neg0, x, d);
+    }
+    // E[o] and E[o']
+    diag_mul<MODEL, KM>(es, rp, A);    // C
+    diag_mul<MODEL, KM>(fs, rp, t);
+    diag_axpby<KM>(x, gp, A, g0, t);
+    if (mo) diag_axpby<KM>(y, gp, A, g1, A);
+    else diag_scale<KM>(y, gp, A);
+    diag_acc_row2<KM>(a.accE, o, x, v0 != 0, y, v1 != 0, d);
+    if (v1 && !mo) {
+      diag_scale<KM>(x, g1, A);
+      acc_row<KM>(a.accE, neg1, x, d);
+    }
+    // R[p]
+    diag_cmul<MODEL, KM>(es, eo, A);   // D
+    diag_cmul<MODEL, KM>(fs, eo, t);
+    diag_axpby<KM>(x, gp, A, g0, t);
+    diag_cmul<MODEL, KM>(es, fo, t);
+    diag_axpby<KM>(y, gp, A, g1, t);
+    diag_acc_row2<KM>(aR, p, x, v0 != 0, y, v1 != 0, d);
+  }
+  __shared__ int lds_nv;
+  block_count_add(a.nviol, nv, &lds_nv);   // one atomic per workgroup
+}
+
+bool diag_pos_ok(int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d) {
+  return model_diag(model) && af >= 0 && af <= 3 && d >= 1 && d <= 256 &&
+         (model != SKGE_COMPLEX || d % 2 == 0) && ent && rel && ent->width == d &&
+         rel->width == d &&
+         (ent->acc_mode == SKGE_ACC_F32 || ent->acc_mode == SKGE_ACC_FX64) &&
+         (rel->acc_mode == SKGE_ACC_F32 || rel->acc_mode == SKGE_ACC_FX64) &&
+         ent->acc_replicas <= 1 && ent->acc_sum && ent->acc_cnt && rel->acc_sum && rel->acc_cnt;
+}
+
+// one batch of the DistMult / ComplEx device pair loop (slots: 4 * count
+// entity, count relation)
+int launch_diag_pos(hipStream_t st, int model, int af, const skge_table_t* ent,
+                    const skge_table_t* rel, int d, const int4* rec, const int* rec_n1,
+                    long long start, int count, float margin, int* nviol) {
+  int rc;
+  if ((rc = check_table(ent, "ent", true)) || (rc = check_table(rel, "rel", true)) ||
+      (rc = check_slots(ent, 4ll * count, "ent")) || (rc = check_slots(rel, count, "rel")))
+    return rc;
+  SKGE_CHECK_ARG(diag_pos_ok(model, af, ent, rel, d), "DistMult / ComplEx positive kernel: "
+                 "unsupported tables");
+  SKGE_CHECK_ARG(rec && rec_n1 && nviol && count >= 0, "bad argument");
+  if (count == 0) return SKGE_OK;
+  DiagPosArgs a = {};
+  a.E = ent->param;
+  a.R = rel->param;
+  a.accE = accum_of(ent);
+  a.accR = accum_of(rel);
+  a.rec = rec;
+  a.rec_n1 = rec_n1;
+  a.start = start;
+  a.count = count;
+  a.d = d;
+  a.af = af;
+  a.margin = margin;
+  a.nviol = nviol;
+  const int blocks = std::max(1, std::min((count + 3) / 4, 8192));
+#define SKGE_DPOS(K)                                                                         \
+  case K:                                                                                    \
+    if (model == SKGE_DISTMULT)                                                              \
+      hipLaunchKernelGGL((k_diag_pos<DISTMULT, K>), dim3(blocks), dim3(256), 0, st, a);      \
+    else                                                                                     \
+      hipLaunchKernelGGL((k_diag_pos<COMPLEX, K>), dim3(blocks), dim3(256), 0, st, a);       \
+    break;
+  switch (km_for(d)) {
+    SKGE_DPOS(1)
+    SKGE_DPOS(2)
+    SKGE_DPOS(3)
+    default:
+    SKGE_DPOS(4)
+  }
+#undef SKGE_DPOS
+  SKGE_CHECK_LAUNCH("distmult / complex positive kernel");
+  return SKGE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // logistic loss: HolE skge/hole.py:22-42, RESCAL skge/rescal.py:37-76
 // (logistic(): skge_device.h).  A triple with relation -1 is SKIPPED
 // (skge_triple_grad in skge_hip.h): its slots name no row, coef 0, nothing
@@ -874,7 +1079,7 @@ template <int MODEL>
 __device__ __forceinline__ void skip_triple(const PairArgs& a, int i) {
   const int l = lane_id();
   if (l < 2) commit_slot(a.accE, -1, 0, 2 * i + l);
-  if (MODEL == HOLE && l == 2) commit_slot(replica(a.accR, i), -1, 0, i);
+  if (MODEL != RESCAL && l == 2) commit_slot(replica(a.accR, i), -1, 0, i);
   if (l == 0 && a.coef) a.coef[i] = 0.0f;
 }
 
@@ -908,7 +1113,23 @@ __global__ __launch_bounds__(256) void k_triple_grad(PairArgs a) {
     load_row<KM>(a.E, s, d, es);
     load_row<KM>(a.E, o, d, eo);
     float score, li, fs;
-    if (MODEL == HOLE && KM <= 4 && fast) {
+    if constexpr (is_diag(MODEL)) {
+      // DistMult / ComplEx (skge_diag.h), HolE's logistic step (hole.py:22-42)
+      // with the trilinear form: score E[s] . (conj(R[p]) * E[o])
+      float rp[KM], yv[KM];
+      load_row<KM>(a.R, p, d, rp);
+      diag_cmul<MODEL, KM>(rp, eo, t);   // d phi / d s
+      score = diag_dot<KM>(es, t);
+      logistic(y, score, &li, &fs);
+      diag_cmul<MODEL, KM>(es, eo, x);   // R: fs conj(E[s]) * E[o]
+      scale<KM>(x, x, fs);
+      acc_row<KM>(replica(a.accR, i), p, x, d);
+      if (lane_id() == 2) commit_slot(replica(a.accR, i), p, 1, i);
+      scale<KM>(x, t, fs);               // E[s]: fs conj(R[p]) * E[o]
+      diag_mul<MODEL, KM>(es, rp, t);    // E[o]: fs E[s] * R[p]
+      scale<KM>(yv, t, fs);
+      acc_two<KM>(a.accE, s, x, o, yv, d);
+    } else if (MODEL == HOLE && KM <= 4 && fast) {
       float rp[KM], c[KM];
       load_row<KM>(a.R, p, d, rp);
       to_lds_a<KM>(fEs, es, d);
@@ -1364,7 +1585,9 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
   int blocks = (a.P + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   if (blocks < 1) blocks = 1;
-  size_t lds = (MODEL == TRANSE_L1 || MODEL == TRANSE_L2) ? 0 : (size_t)4 * 6 * 64 * km * 4;
+  // TransE, DistMult and ComplEx work in registers: no LDS to cap their occupancy
+  size_t lds = (MODEL == TRANSE_L1 || MODEL == TRANSE_L2 || is_diag(MODEL))
+                   ? 0 : (size_t)4 * 6 * 64 * km * 4;
   const int path = MODEL == HOLE ? hole_step_path(a.d, logistic_mode, a.record != 0)
                                  : SKGE_PATH_GENERIC;
   const bool hfast = path != SKGE_PATH_GENERIC;
@@ -1447,7 +1670,7 @@ static int check_model_tables(int model, const skge_table_t* ent, const skge_tab
   if ((rc = check_single(ent, "ent")) ||
       (model == SKGE_RESCAL && (rc = check_single(rel, "rel"))))
     return rc;
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(d > 0 && ent->width == d, "entity width %d != d %d", ent->width, d);
   if (model == SKGE_RESCAL)
     SKGE_CHECK_ARG(rel->width == d * d, "W width %d != d*d", rel->width);
@@ -1494,6 +1717,8 @@ extern "C" int skge_pair_grad(void* stream, int model, int af, const skge_table_
     case SKGE_TRANSE_L1: return launch_pair<TRANSE_L1>(a, km, st, false);
     case SKGE_TRANSE_L2: return launch_pair<TRANSE_L2>(a, km, st, false);
     case SKGE_HOLE: return launch_pair<HOLE>(a, km, st, false);
+    case SKGE_DISTMULT: return launch_pair<DISTMULT>(a, km, st, false);
+    case SKGE_COMPLEX: return launch_pair<COMPLEX>(a, km, st, false);
     default: return launch_pair<RESCAL>(a, km, st, false);
   }
 }
@@ -1503,8 +1728,8 @@ extern "C" int skge_triple_grad(void* stream, int model, const skge_table_t* ent
                                 int T, float* score, float* coef, float* loss) {
   int rc = check_model_tables(model, ent, rel, d);
   if (rc) return rc;
-  SKGE_CHECK_ARG(model == SKGE_HOLE || model == SKGE_RESCAL,
-                 "logistic loss is defined for HolE and RESCAL only");
+  SKGE_CHECK_ARG(model == SKGE_HOLE || model == SKGE_RESCAL || model_diag(model),
+                 "logistic loss is defined for HolE, RESCAL, DistMult and ComplEx only");
   SKGE_CHECK_ARG(T >= 0, "T < 0");
   if (T == 0) return SKGE_OK;
   SKGE_CHECK_ARG(trip && ys, "trip/ys NULL");
@@ -1522,10 +1747,12 @@ extern "C" int skge_triple_grad(void* stream, int model, const skge_table_t* ent
   a.loss = loss;
   a.record = 1;
   if ((rc = check_slots(ent, 2ll * T, "ent"))) return rc;
-  if (model == SKGE_HOLE && (rc = check_slots(rel, T, "rel"))) return rc;
+  if (model != SKGE_RESCAL && (rc = check_slots(rel, T, "rel"))) return rc;
   const int km = km_for(d);
   hipStream_t st = as_stream(stream);
   if (model == SKGE_HOLE) return launch_pair<HOLE>(a, km, st, true);
+  if (model == SKGE_DISTMULT) return launch_pair<DISTMULT>(a, km, st, true);
+  if (model == SKGE_COMPLEX) return launch_pair<COMPLEX>(a, km, st, true);
   return launch_pair<RESCAL>(a, km, st, true);
 }
 

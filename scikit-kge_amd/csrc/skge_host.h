@@ -67,6 +67,20 @@ inline int km_for(int d) {
   return 0;
 }
 
+// the model codes of include/skge_hip.h: 0..3, 5, 6 (4 is unassigned)
+inline bool model_known(int model) {
+  return (model >= SKGE_TRANSE_L1 && model <= SKGE_RESCAL) || model == SKGE_DISTMULT ||
+         model == SKGE_COMPLEX;
+}
+// DistMult / ComplEx: HolE's table shapes and slot maps, skge_diag.h's scores
+inline bool model_diag(int model) { return model == SKGE_DISTMULT || model == SKGE_COMPLEX; }
+// the model's code and width: ComplEx rows hold d/2 interleaved (re, im) pairs
+#define SKGE_CHECK_MODEL(model, d)                                                       \
+  do {                                                                                   \
+    SKGE_CHECK_ARG(::skge::model_known(model), "unknown model %d", model);               \
+    SKGE_CHECK_ARG((model) != SKGE_COMPLEX || (d) % 2 == 0, "ComplEx needs an even d (%d)", d); \
+  } while (0)
+
 int* dev_err_word();   // skge_update.hip: the device error word (Accum::err)
 inline Accum accum_of(const skge_table_t* t) {
   Accum a;
@@ -236,6 +250,13 @@ int hole_step_path(int d, bool logistic_mode, bool record);
 int launch_hole_pos(hipStream_t st, int af, const skge_table_t* ent, const skge_table_t* rel,
                     int d, const int4* rec, const int* rec_n1, long long start, int count,
                     float margin, int* nviol, int* fold, int* total);
+
+// skge_grad.hip: DistMult / ComplEx pairwise, one positive (both of its pairs)
+// per wave (k_diag_pos): d <= 256, fp32 or fixed-point sums, one entity copy
+bool diag_pos_ok(int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d);
+int launch_diag_pos(hipStream_t st, int model, int af, const skge_table_t* ent,
+                    const skge_table_t* rel, int d, const int4* rec, const int* rec_n1,
+                    long long start, int count, float margin, int* nviol);
 
 // The RESCAL W updater's step after the fused front (skge_rescal.hip
 // k_rescal_front_fused): W[p] from relation p's split-K dW partial tiles,

@@ -21,6 +21,8 @@
 // Exception: HolE (d % 4 == 0, d <= 256) scores both pairs of a positive in
 // one wave straight from the records (k_hole_pos, skge_grad.hip): the same
 // pairs, contributions and counts, 7 correlations per positive instead of 12.
+// DistMult and ComplEx (d <= 256) do the same with k_diag_pos: 5 row reads per
+// positive instead of 12, one accumulator add per distinct row.
 #include <cstdlib>
 #include <vector>
 
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(256) void k_pairs_of_epoch(const int4* __restrict__
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < T;
        j += (long long)gridDim.x * blockDim.x) {
     if (j < nb) gates[j] = 0;
-    if (pos == nullptr) continue;   // HolE positive path: the records are its input
+    if (pos == nullptr) continue;   // per-positive kernels: the records are their input
     const int4 r = rec[j];
     const int n1 = rec_n1[j];
     if (dedup) {   // RESCAL: each positive once ([T][3]), its two negatives ([T][2][3])
@@ -146,7 +148,8 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
     const skge_sampler_t* smp) {
   if (!ent || !rel) return fail("pair runner: NULL table");
   if (check_sampler(smp, "pair runner")) return nullptr;
-  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("pair runner: unknown model");
+  if (!model_known(model)) return fail("pair runner: unknown model");
+  if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
   if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity,
                          2 * T, ntries, stream))
     return nullptr;
@@ -167,6 +170,11 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
   const char* rp = getenv("SKGE_RESCAL_PAIRS");
   const bool rpos = model == SKGE_RESCAL && !(rp && atoi(rp)) &&
                     rescal_pair_mfma_selected(d, rel->rows);
+  // DistMult / ComplEx: both pairs of a positive in one wave straight from the
+  // records (k_diag_pos, skge_grad.hip; SKGE_DIAG_PAIRS=1 keeps the explicit
+  // pairs)
+  const char* dg = getenv("SKGE_DIAG_PAIRS");
+  const bool dpos = !(dg && atoi(dg)) && diag_pos_ok(model, af, ent, rel, d);
   const int nb = batches.size();
   // RESCAL: every batch's relation buckets built once per epoch, up front (the
   // items do not depend on the parameters); SKGE_RESCAL_EPOCH_BUCKETS=0 keeps
@@ -178,7 +186,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
                     : skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
   r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
   r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
-  if (!hpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
+  if (!hpos && !dpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
   if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
   if (!r->alloc_ok) return fail("pair runner: device allocation failed");
@@ -206,9 +214,11 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
     const long long start = batches[k].first;
     const int count = (int)batches[k].second;
     int* gate = r->nviol + k;
-    if (hpos) {
-      rc = launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin, gate,
-                           nullptr, nullptr);
+    if (hpos || dpos) {
+      rc = hpos ? launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin,
+                                  gate, nullptr, nullptr)
+                : launch_diag_pos(st, model, af, ent, rel, d, r->rec, r->rec_n1, start, count,
+                                  margin, gate);
       if (!rc) {
         skge_table_t t[2] = {*ent, *rel};
         t[0].gate = gate;
@@ -274,7 +284,8 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
     const skge_sampler_t* smp, const skge_negatives_t* negs) {
   if (!ent || !rel) return fail("pair runner: NULL table");
   if (check_sampler(smp, "pair runner")) return nullptr;
-  if (model < SKGE_TRANSE_L1 || model > SKGE_RESCAL) return fail("pair runner: unknown model");
+  if (!model_known(model)) return fail("pair runner: unknown model");
+  if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
   int K = 0;
   if (check_negatives(negs, smp, rel->rows, "pair runner", &K)) return nullptr;
   // pairs, their 3 ids and their 4 entity slots are indexed with ints

@@ -201,7 +201,7 @@ extern "C" int skge_rank_pools(void* stream, int model, const float* E, const fl
                                int* ranks_out) {
   SKGE_CHECK_ARG(E && R && queries && ranks_out && vec_pool && tail_off && head_off,
                  "NULL argument");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && nq >= 0, "bad sizes (d <= 1024)");
   SKGE_CHECK_ARG(n_pools >= 0, "n_pools = %d is negative", n_pools);
   SKGE_CHECK_ARG(n_pools == 0 || (pool_off && pool_ent), "NULL argument (%d pools, no pool arrays)",
@@ -263,7 +263,7 @@ extern "C" int skge_topk_pools(void* stream, int model, const float* E, const fl
                                void* workspace, size_t ws_bytes, int* ent_out, float* score_out) {
   SKGE_CHECK_ARG(E && R && queries && query_pool && ent_out && score_out, "NULL argument");
   SKGE_CHECK_ARG(!excl_off || excl_ent, "NULL argument (excl_ent with excl_off given)");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(direction == 0 || direction == 1, "direction must be 0 (tail) or 1 (head)");
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && nq >= 0, "bad sizes (d <= 1024)");
   SKGE_CHECK_ARG(k >= 1 && k <= TK_KMAX, "k = %d outside 1 .. %d", k, TK_KMAX);

@@ -258,7 +258,7 @@ extern "C" int skge_relrank(void* stream, int model, const float* E, const float
                             int* ranks_out) {
   SKGE_CHECK_ARG(E && R && queries && ranks_out, "NULL argument");
   SKGE_CHECK_ARG(!known_off || known_rel, "NULL argument (known_rel with known_off given)");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(N > 0 && M >= 1 && d > 0 && d <= 1024 && nq >= 0,
                  "bad sizes (N = %d, M = %d, d = %d <= 1024, nq = %d)", N, M, d, nq);
   if (nq == 0) return SKGE_OK;
@@ -308,7 +308,7 @@ extern "C" int skge_reltopk(void* stream, int model, const float* E, const float
                             float* score_out) {
   SKGE_CHECK_ARG(E && R && pairs && rel_out && score_out, "NULL argument");
   SKGE_CHECK_ARG(!excl_off || excl_rel, "NULL argument (excl_rel with excl_off given)");
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(N > 0 && M >= 1 && d > 0 && d <= 1024 && nq >= 0,
                  "bad sizes (N = %d, M = %d, d = %d <= 1024, nq = %d)", N, M, d, nq);
   SKGE_CHECK_ARG(k >= 1 && k <= TK_KMAX, "k = %d outside 1 .. %d", k, TK_KMAX);

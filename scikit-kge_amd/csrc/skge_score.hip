@@ -11,6 +11,8 @@
 //                     corr_quad, then hole_score_q(E_s, A) (skge_hole.h)
 //   k_score_hole      HolE, any d: ccorr_direct_k (skge_elem.h, k_rel_query's),
 //                     folded with R_p per lane, then the wave sum
+//   k_score_diag      DistMult / ComplEx: E_s . (conj(R_p) * E_o) on rows in
+//                     registers (skge_diag.h), the step kernels' expression
 //   k_score_rescal    RESCAL: the triples are grouped by relation on the device
 //                     (launch_pool_group: histogram, scan, scatter); an item is
 //                     up to QB triples of ONE relation, scored by the MFMA
@@ -21,6 +23,7 @@
 #include <algorithm>
 #include <limits.h>
 
+#include "skge_diag.h"
 #include "skge_elem.h"
 #include "skge_host.h"
 #include "skge_hole.h"
@@ -136,6 +139,40 @@ __global__ __launch_bounds__(256) void k_score_hole(ScoreArgs a) {
   }
 }
 
+// ---- DistMult / ComplEx: E_s . (conj(R_p) * E_o), the step kernels' score
+// (skge_diag.h), one wave per triple, rows in registers ----
+template <int MODEL, int KM>
+__global__ __launch_bounds__(256) void k_score_diag(ScoreArgs a) {
+  const int wpb = blockDim.x >> 6, d = a.d;
+  for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < a.n; i += gridDim.x * wpb) {
+    const int s = uni(a.trip[3 * (size_t)i]), o = uni(a.trip[3 * (size_t)i + 1]);
+    const int p = uni(a.trip[3 * (size_t)i + 2]);
+    float es[KM], eo[KM], rp[KM], q[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, o, d, eo);
+    diag_cmul<MODEL, KM>(rp, eo, q);
+    const float sc = diag_dot<KM>(es, q);
+    if (lane_id() == 0) a.out[i] = sc;
+  }
+}
+
+template <int MODEL>
+static void launch_score_diag(hipStream_t st, int blocks, const ScoreArgs& a) {
+#define SKGE_SC_D(K) \
+  case K: hipLaunchKernelGGL((k_score_diag<MODEL, K>), dim3(blocks), dim3(256), 0, st, a); break;
+  switch (km_for(a.d)) {
+    SKGE_SC_D(1)
+    SKGE_SC_D(2)
+    SKGE_SC_D(3)
+    SKGE_SC_D(4)
+    SKGE_SC_D(8)
+    default:
+    SKGE_SC_D(16)
+  }
+#undef SKGE_SC_D
+}
+
 // ---- RESCAL ----
 __global__ __launch_bounds__(256) void k_score_rel(const int* __restrict__ trip, int n,
                                                    int* __restrict__ rel) {
@@ -186,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void k_score_rescal(ScoreRescalArgs a) {
 static int score_rescal_qb(int n, int M) { return (long long)n >= 64ll * M ? 128 : 32; }
 
 static bool score_sizes_ok(int model, long long n, int M, int d) {
-  return model >= 0 && model <= 3 && n >= 0 && n <= INT_MAX / 4 && M >= 1 && d >= 1 && d <= 1024;
+  return model_known(model) && (model != SKGE_COMPLEX || d % 2 == 0) && n >= 0 && n <= INT_MAX / 4 && M >= 1 && d >= 1 && d <= 1024;
 }
 
 }  // namespace skge
@@ -202,7 +239,7 @@ extern "C" size_t skge_score_workspace_bytes(int model, int n, int M, int d) {
 extern "C" int skge_score(void* stream, int model, const float* E, const float* R, int N, int M,
                           int d, const int* trip, int64_t n, void* workspace, size_t ws_bytes,
                           float* score_out) {
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
+  SKGE_CHECK_MODEL(model, d);
   SKGE_CHECK_ARG(n >= 0 && n <= INT_MAX / 4, "n = %lld outside 0 .. %d", (long long)n, INT_MAX / 4);
   SKGE_CHECK_ARG(N > 0 && M >= 1 && d >= 1 && d <= 1024,
                  "bad sizes (N = %d, M = %d, d = %d, 1 <= d <= 1024)", N, M, d);
@@ -254,6 +291,14 @@ extern "C" int skge_score(void* stream, int model, const float* E, const float* 
       hipLaunchKernelGGL(k_score_hole, dim3(blocks), dim3(256), (size_t)4 * 2 * d * sizeof(float),
                          st, a);
     SKGE_CHECK_LAUNCH("score (HolE)");
+    return SKGE_OK;
+  }
+  if (model_diag(model)) {
+    if (model == SKGE_DISTMULT)
+      launch_score_diag<DISTMULT>(st, blocks, a);
+    else
+      launch_score_diag<COMPLEX>(st, blocks, a);
+    SKGE_CHECK_LAUNCH("score (DistMult / ComplEx)");
     return SKGE_OK;
   }
   char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);

@@ -242,8 +242,10 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_ex(
     uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp) {
   if (!ent || !rel) return fail("triple runner: NULL table");
   if (check_sampler(smp, "triple runner")) return nullptr;
-  if (model != SKGE_HOLE && model != SKGE_RESCAL)
-    return fail("triple runner: logistic loss is defined for HolE and RESCAL only");
+  if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
+    return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
+                "and ComplEx)");
+  if (model == SKGE_COMPLEX && d % 2) return fail("triple runner: ComplEx needs an even d");
   if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / 3, nbatches,
                          set_capacity, 2 * T, ntries, stream))
     return nullptr;
@@ -334,8 +336,10 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_multi(
     const skge_negatives_t* negs) {
   if (!ent || !rel) return fail("triple runner: NULL table");
   if (check_sampler(smp, "triple runner")) return nullptr;
-  if (model != SKGE_HOLE && model != SKGE_RESCAL)
-    return fail("triple runner: logistic loss is defined for HolE and RESCAL only");
+  if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
+    return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
+                "and ComplEx)");
+  if (model == SKGE_COMPLEX && d % 2) return fail("triple runner: ComplEx needs an even d");
   int K = 0;
   if (check_negatives(negs, smp, rel->rows, "triple runner", &K)) return nullptr;
   // triples, their 3 ids and their 2 entity slots are indexed with ints

@@ -1082,11 +1082,12 @@ static bool rescal_use_mfma(int d, int M) { return skge_rescal_mfma_ok(d, M); }
 bool rescal_pair_mfma_selected(int d, int M) { return rescal_use_mfma(d, M); }
 
 extern "C" int skge_step_path(int model, int logistic, int d, int n_rel, int n_items) {
-  SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
-  SKGE_CHECK_ARG(!logistic || model == SKGE_HOLE || model == SKGE_RESCAL,
-                 "logistic loss is defined for HolE and RESCAL only");
+  SKGE_CHECK_ARG(model_known(model), "unknown model %d", model);
+  SKGE_CHECK_ARG(!logistic || model == SKGE_HOLE || model == SKGE_RESCAL || model_diag(model),
+                 "logistic loss is defined for HolE, RESCAL, DistMult and ComplEx only");
   const int km = d > 0 ? km_for(d) : 0;
   SKGE_CHECK_ARG(km != 0, "d=%d unsupported (1..1024)", d);
+  SKGE_CHECK_ARG(model != SKGE_COMPLEX || d % 2 == 0, "ComplEx needs an even d (%d)", d);
   SKGE_CHECK_ARG(n_rel >= 1 && n_items >= 0, "n_rel %d / n_items %d", n_rel, n_items);
   int path = SKGE_PATH_GENERIC;
   if (model == SKGE_HOLE) {

@@ -1,13 +1,15 @@
 """skge_amd -- MI355X-native (HIP/gfx950) scikit-kge training hot path.
 
 Drop-in for skge's model / updater / trainer protocol: TransE, HolE, RESCAL,
-StochasticTrainer, PairwiseStochasticTrainer, SGD, AdaGrad,
+DistMult, ComplEx, StochasticTrainer, PairwiseStochasticTrainer, SGD, AdaGrad,
 RandomModeSampler, CorruptedSampler, LCWASampler.  Every numeric step runs in libskgehip.so."""
 from .version import __version__
 from .base import Model, StochasticTrainer, PairwiseStochasticTrainer, set_deterministic, deterministic
 from .transe import TransE
 from .hole import HolE
 from .rescal import RESCAL
+from .distmult import DistMult
+from .complex import ComplEx
 from .param import Parameter, SGD, AdaGrad, normalize, normless1
 from .sample import RandomModeSampler, CorruptedSampler, LCWASampler, type_index
 from .eval import (FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores,

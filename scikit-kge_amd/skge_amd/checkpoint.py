@@ -36,7 +36,10 @@ import numpy as np
 
 from . import actfun as AF
 
-MODEL_MODULES = {"TransE": "skge.transe", "HolE": "skge.hole", "RESCAL": "skge.rescal"}
+MODEL_MODULES = {"TransE": "skge.transe", "HolE": "skge.hole", "RESCAL": "skge.rescal",
+                 # not reference classes: the same layout under the names the
+                 # reference would use, so both round-trip through this module
+                 "DistMult": "skge.distmult", "ComplEx": "skge.complex"}
 _ACTFUNS = ("ActivationFunction", "Linear", "Sigmoid", "Tanh", "ReLU", "Softplus")
 _NUMPY_GLOBALS = {
     ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
@@ -170,9 +173,12 @@ def load_reference(fname):
     from .hole import HolE
     from .rescal import RESCAL
     from .transe import TransE
+    from .distmult import DistMult
+    from .complex import ComplEx
     with open(fname, "rb") as f:
         cname, hp, params, _ = read_reference_state(f)
-    cls = {"TransE": TransE, "HolE": HolE, "RESCAL": RESCAL}[cname]
+    cls = {"TransE": TransE, "HolE": HolE, "RESCAL": RESCAL, "DistMult": DistMult,
+           "ComplEx": ComplEx}[cname]
     m = cls.__new__(cls)
     m.__setstate__({"hyperparams": hp, "params": params})
     return m

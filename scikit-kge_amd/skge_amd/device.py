@@ -687,7 +687,8 @@ class PairLoopRunner(_Runner):
 
 
 def _require_logistic_model(model):
-    if model._kernel_model() not in (L.SKGE_HOLE, L.SKGE_RESCAL):
+    if model._kernel_model() not in (L.SKGE_HOLE, L.SKGE_RESCAL, L.SKGE_DISTMULT,
+                                     L.SKGE_COMPLEX):
         raise NotImplementedError("%s has no logistic loss in the reference"
                                   % type(model).__name__)
 
@@ -821,6 +822,11 @@ def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=N
     pipelined runners draw (1, [0, 1]) only, so any other runs the pair loop."""
     from .transe import TransE
     from .base import deterministic
+    from .distmult import DistMult
+    if isinstance(model, DistMult) and runner in ("pipe", "epoch", "hole_pipe"):
+        # DistMult / ComplEx train on the pair loop only (k_diag_pos)
+        raise ValueError("device runner %r is TransE's or HolE's; %s needs 'pairs' (or 'auto')"
+                         % (runner, type(model).__name__))
     if runner == "pipe":
         if negatives is not None and (int(negatives[0]), list(negatives[1])) != (1, [0, 1]):
             raise ValueError("device runner 'pipe' draws one negative per mode of [0, 1] only; "

@@ -181,6 +181,10 @@ class DataParallelRunner(_PaddedTables, _PipeRunner):
     def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, group=None, stream=None,
                  capture=None):
         from .transe import TransE
+        from .distmult import DistMult
+        if isinstance(model, DistMult):
+            raise ValueError("data-parallel runner: TransE-L1 only; %s trains on one device with "
+                             "device_runner='pairs'" % type(model).__name__)
         if not isinstance(model, TransE) or not model.l1 or model.d > 1024:
             raise ValueError("data-parallel runner: TransE-L1 with d <= 1024")
         T = kg.T

@@ -25,6 +25,9 @@ def _model_code(model):
     from .transe import TransE
     from .hole import HolE
     from .rescal import RESCAL
+    from .distmult import DistMult
+    if isinstance(model, DistMult):   # ComplEx too: its own code
+        return model.model_code, model.params["R"]
     if isinstance(model, TransE):
         return L.SKGE_TRANSE_L1, model.params["R"]
     if isinstance(model, HolE):
