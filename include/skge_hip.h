@@ -335,6 +335,33 @@ int skge_runner_nlaunches(const skge_runner_t *r);
 void skge_runner_destroy(skge_runner_t *r);
 
 /*
+ * Ordering of one run of ANY runner below (its _run / _profile calls on
+ * run_stream) against the stream the caller works on, paid for on the host:
+ * run_stream never receives a cross-stream event wait, and caller_stream
+ * only when asked.  (These two calls are the exception to "no call
+ * synchronises".)
+ *
+ * begin, before the run's first launch, returns a path code or SKGE_E*:
+ *   0  the streams are the same, or hipStreamQuery(caller_stream) found
+ *      nothing in flight: nothing is enqueued on either stream;
+ *   1  the caller's stream had work in flight: the HOST waited for it
+ *      (hipStreamSynchronize); still nothing is enqueued on run_stream.
+ * Any other status of the query (e.g. a capturing caller_stream) is SKGE_EHIP.
+ * end, after the last launch, returns a path code or SKGE_E*:
+ *   0  the streams are the same: nothing to do;
+ *   1  queued == 0: the HOST waited for run_stream (hipStreamSynchronize);
+ *      nothing is enqueued on caller_stream.  A wait queued on caller_stream
+ *      sits unsatisfied in its hardware queue while the replays run, and
+ *      that is what was measured to cost ~0.9 us on every replayed launch
+ *      (profiles/run_ordering);
+ *   2  queued != 0: an event recorded on run_stream (no timing) that
+ *      caller_stream waits for; the call returns at once.
+ * run_stream must not be NULL; caller_stream NULL = the legacy default stream.
+ */
+int skge_run_order_begin(void *run_stream, void *caller_stream);
+int skge_run_order_end(void *run_stream, void *caller_stream, int queued);
+
+/*
  * Device pair loop for any model (TransE L1/L2, HolE, RESCAL): one epoch of
  * PairwiseStochasticTrainer with RandomModeSampler(1, [0, 1])
  * (skge/base.py:1242-1291, 1394-1427; skge/sample.py:28-46) captured into a

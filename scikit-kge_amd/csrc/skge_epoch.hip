@@ -604,3 +604,12 @@ extern "C" int skge_runner_run(skge_runner_t* r, void* stream, int nepochs) {
 extern "C" int skge_runner_nlaunches(const skge_runner_t* r) { return r ? r->nlaunch : -1; }
 
 extern "C" void skge_runner_destroy(skge_runner_t* r) { delete r; }
+
+// every runner family's run() ordering (skge_graph_runner.h)
+extern "C" int skge_run_order_begin(void* run_stream, void* caller_stream) {
+  return run_order_begin(run_stream, caller_stream);
+}
+
+extern "C" int skge_run_order_end(void* run_stream, void* caller_stream, int queued) {
+  return run_order_end(run_stream, caller_stream, queued);
+}

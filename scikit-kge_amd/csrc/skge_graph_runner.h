@@ -149,4 +149,51 @@ inline int run_graph(GraphRunnerCore* r, void* stream, int nepochs) {
   return SKGE_OK;
 }
 
+// A run()'s ordering against the caller's stream (skge_run_order_begin / _end,
+// include/skge_hip.h; one implementation for every runner family), paid for
+// on the host: by default neither stream receives a cross-stream event wait.
+//
+// begin: the caller's earlier work done before the runner's first launch.
+// 0: nothing in flight on the caller's stream (or one stream), nothing
+// enqueued anywhere; 1: the host waited for the caller's stream.
+inline int run_order_begin(void* run_stream, void* caller_stream) {
+  SKGE_CHECK_ARG(run_stream, "run_order_begin: needs the runner's (non-default) stream");
+  if (run_stream == caller_stream) return 0;
+  const hipError_t e = hipStreamQuery(as_stream(caller_stream));
+  if (e == hipSuccess) return 0;
+  // (a not-ready answer must not stay behind as HIP's last error: the launch
+  // checks read that word)
+  (void)hipGetLastError();
+  if (e != hipErrorNotReady) {
+    set_error("run_order_begin: hipStreamQuery(caller_stream): %s", hipGetErrorString(e));
+    return SKGE_EHIP;
+  }
+  SKGE_CHECK_HIP(hipStreamSynchronize(as_stream(caller_stream)));
+  return 1;
+}
+
+// end: the caller's later work after the runner's launches.  0: one stream,
+// nothing to do.  1 (queued == 0): the host waited for the runner's stream --
+// the wait queued on the caller's stream is what slows the replays down (the
+// other hardware queue holds an unsatisfied barrier while they run; measured,
+// profiles/run_ordering), so by default none is queued.  2 (queued != 0): an
+// event recorded on the runner's stream (no timing), waited for by the
+// caller's, released at once (the runtime keeps it until it fires).
+inline int run_order_end(void* run_stream, void* caller_stream, int queued) {
+  SKGE_CHECK_ARG(run_stream, "run_order_end: needs the runner's (non-default) stream");
+  if (run_stream == caller_stream) return 0;
+  if (!queued) {
+    SKGE_CHECK_HIP(hipStreamSynchronize(as_stream(run_stream)));
+    return 1;
+  }
+  hipEvent_t ev = nullptr;
+  SKGE_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, as_stream(run_stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(as_stream(caller_stream), ev, 0);
+  const hipError_t d = hipEventDestroy(ev);
+  SKGE_CHECK_HIP(e);
+  SKGE_CHECK_HIP(d);
+  return 2;
+}
+
 }  // namespace skge

@@ -121,6 +121,8 @@ SIGNATURES = {
     "skge_runner_run": (c_i, [c_p, c_p, c_i]),
     "skge_runner_nlaunches": (c_i, [c_p]),
     "skge_runner_destroy": (None, [c_p]),
+    "skge_run_order_begin": (c_i, [c_p, c_p]),
+    "skge_run_order_end": (c_i, [c_p, c_p, c_i]),
     "skge_pair_runner_create": (c_p, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i,
                                       c_u64, c_p, c_f, c_i, c_p]),
     "skge_pair_runner_create_ex": (c_p, [c_p, c_i, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,

@@ -300,14 +300,53 @@ class _Runner(object):
         L.check(getattr(L.lib(), self._abi + "_run")(self.handle, L.stream_ptr(self.stream),
                                                      int(nepochs)), self._abi + "_run")
 
+    last_order = None   # the last run()'s / profile()'s path code (_order_begin)
+
+    def _order_begin(self):
+        """The caller's stream's earlier work (parameters it wrote) before the
+        runner's launches, without a wait queued on the runner's stream
+        (include/skge_hip.h, skge_run_order_begin).  Keeps the path code in
+        last_order: 0 = the caller's stream was idle, nothing enqueued (after
+        a synchronize: the fit loop); 1 = the host waited for it."""
+        rc = L.lib().skge_run_order_begin(L.stream_ptr(self.stream), L.stream_ptr())
+        if rc < 0:
+            L.check(rc, "skge_run_order_begin")
+        self.last_order = rc
+
+    # True: the ordering after a run is an event wait queued on the caller's
+    # stream (run() returns at once; the replays run ~10% slower while that
+    # wait is pending, profiles/run_ordering); False: the host waits
+    queued_after = _os.environ.get("SKGE_RUN_ORDER_AFTER", "host") == "event"
+    last_order_end = None   # skge_run_order_end's path code
+
+    def _order_end(self):
+        """The caller's stream's later work after the runner's launches."""
+        rc = L.lib().skge_run_order_end(L.stream_ptr(self.stream), L.stream_ptr(),
+                                        int(self.queued_after))
+        if rc < 0:
+            L.check(rc, "skge_run_order_end")
+        self.last_order_end = rc
+
     def run(self, nepochs=1):
         """nepochs epochs on the runner's stream, ordered after the caller's
-        stream (parameters it wrote) and before its later work."""
-        self.stream.wait_stream(torch.cuda.current_stream())
+        stream (parameters it wrote) and before its later work.
+
+        Called from another stream than the runner's, both orderings are paid
+        for on the host, so that no cross-stream wait is queued on either
+        stream.  Before: when the caller's stream still has work in flight,
+        run() BLOCKS until that work has drained (last_order == 1); a caller
+        that synchronised first pays nothing (last_order == 0).  After: run()
+        BLOCKS until its epochs are done (what the synchronize() that follows
+        would wait for); queued_after = True (SKGE_RUN_ORDER_AFTER=event)
+        queues an event wait on the caller's stream instead and returns at
+        once, at ~0.9 us more per replayed launch.  Called on the runner's
+        own stream (the fit loops) run() orders nothing and never blocks.
+        The caller's stream must not be capturing."""
+        self._order_begin()
         self._pad_in()
         self._launch(nepochs)
         self._pad_out()
-        torch.cuda.current_stream().wait_stream(self.stream)
+        self._order_end()
 
     def synchronize(self):
         self.stream.synchronize()
@@ -389,11 +428,10 @@ class _PaddedTables(object):
 
     def _pad_in(self):
         """Padded tables: the model's parameters / states into the copies
-        (ordered after the caller's stream)."""
+        (run()'s _order_begin has ordered them after the caller's stream)."""
         if not self._pad:
             return
         d = self.model.d
-        self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             for P, Pp, st, sp in self._padded:
                 Pp[:, :d].copy_(P.data)
@@ -401,6 +439,7 @@ class _PaddedTables(object):
                     sp[:, :d].copy_(st)
 
     def _pad_out(self):
+        """The copies back into the model (run()'s _order_end follows)."""
         if not self._pad:
             return
         d = self.model.d
@@ -409,7 +448,6 @@ class _PaddedTables(object):
                 P.data.copy_(Pp[:, :d])
                 if st is not None:
                     st.copy_(sp[:, :d])
-        torch.cuda.current_stream().wait_stream(self.stream)
 
 
 class _PipeRunner(_Runner):
@@ -445,13 +483,14 @@ class _PipeRunner(_Runner):
         stats = np.zeros((n, 3), dtype=np.int32)
         tr = np.zeros(2 + 6 * self.kg.T + 8 * self.kg.T + 64, dtype=np.uint64) \
             if trace_launch else None
-        self.stream.wait_stream(torch.cuda.current_stream())
+        self._order_begin()
         self._pad_in()
         L.check(L.lib().skge_pipe_runner_profile(
             self.handle, L.stream_ptr(self.stream), us.ctypes.data, stats.ctypes.data, n,
             int(trace_launch or 0), None if tr is None else tr.ctypes.data,
             0 if tr is None else len(tr)), "runner profile")
         self._pad_out()
+        self._order_end()
         if trace_launch:
             return us, stats, tr
         return us, stats
