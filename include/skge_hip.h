@@ -660,6 +660,26 @@ int skge_pipe_runner_hot_rows(const skge_pipe_runner_t *r);
 /* The batch kernel the runner launches: 0 k_pipe_batch, 1 k_pipe_fused,
  * 2 k_hole_pipe (-1: NULL runner) -- what a profile of its launches is named. */
 int skge_pipe_runner_kernel(const skge_pipe_runner_t *r);
+/* The plan of the runner skge_pipe_runner_create_ex (hole == 0, with flags) or
+ * skge_hole_pipe_runner_create (hole != 0) would build over these tables, T
+ * and nbatches -- decided where the constructors decide it, and answered
+ * without a device: no HIP call is made and no pointer of the tables is
+ * dereferenced (they are only tested for NULL, as the constructors test them).
+ * kernel: skge_pipe_runner_kernel's code; grouped: owner marks (more than 16k
+ * slot records per batch); e8 / w32: int8x4 entity / int32x2 relation sums;
+ * fft / pair: the HolE forms; kq: quads per lane (1, 2, 4); rel_reps: relation
+ * sum replicas; nlaunches: skge_pipe_runner_nlaunches' figure; device_bytes:
+ * what the runner allocates beside the caller's tables, an upper bound where
+ * hot rows are looked for (counted at the 256 the search may keep).  Refuses
+ * (SKGE_EINVAL and the constructors' error text) what they refuse about the
+ * flags, the tables, T, nbatches and the slot capacity.  Reads SKGE_PIPE_FUSED
+ * and SKGE_HPIPE_RREPS as the constructors do. */
+typedef struct skge_pipe_plan {
+  int kernel, grouped, e8, w32, fft, pair, kq, rel_reps, nlaunches;
+  uint64_t device_bytes;
+} skge_pipe_plan_t;
+int skge_pipe_runner_plan(const skge_table_t *ent, const skge_table_t *rel, int d, int64_t T,
+                          int nbatches, int flags, int hole, skge_pipe_plan_t *out);
 /* One epoch launched eagerly (trains like run(1)) with HIP events around every
  * launch: us_out[i] = launch i's duration (i = 0: negative draws, 1..nb1:
  * batches, nb1+1: flush, nb1+2: key advance); stats_out[3i..3i+2] = entity

@@ -10,6 +10,7 @@
 #include <utility>
 #include <vector>
 
+#include "skge_epoch_batches.h"
 #include "skge_host.h"
 
 namespace skge {
@@ -20,27 +21,6 @@ inline std::nullptr_t fail(const char* fmt, A... a) {
   if constexpr (sizeof...(A) == 0) set_error("%s", fmt);
   else set_error(fmt, a...);
   return nullptr;
-}
-
-// batch geometry of StochasticTrainer._optim (skge/base.py:1246-1268):
-// nbatches batches of bs = T / nbatches and the remainder, as (start, count)
-// (k_triples_of_epoch, skge_tripleloop.hip, re-derives a positive's batch on the device)
-struct EpochBatches {
-  int64_t bs = 0, maxb = 0;
-  std::vector<std::pair<int64_t, int64_t>> batches;
-  int size() const { return (int)batches.size(); }
-  const std::pair<int64_t, int64_t>& operator[](int k) const { return batches[k]; }
-};
-
-inline EpochBatches epoch_batches(int64_t T, int nbatches) {
-  EpochBatches b;
-  b.bs = T / nbatches;
-  for (int64_t s0 = 0; s0 < T; s0 += b.bs) {
-    const int64_t c = (s0 + b.bs <= T) ? b.bs : T - s0;
-    b.batches.push_back({s0, c});
-    b.maxb = std::max(b.maxb, c);
-  }
-  return b;
 }
 
 // The refusals every runner makes before its first HIP call.  Tmax and cap_min
@@ -75,6 +55,7 @@ struct GraphRunnerCore {
   int nnodes = 0;             // nodes of the captured graph
   std::vector<void*> bufs;
   bool alloc_ok = true;       // false once an alloc() has failed
+  size_t alloc_bytes = 0;     // bytes alloc() was asked for so far
 
   GraphRunnerCore() = default;
   GraphRunnerCore(const GraphRunnerCore&) = delete;
@@ -85,6 +66,7 @@ struct GraphRunnerCore {
   // before it reads it).  nullptr on failure (alloc_ok stays false).
   void* alloc(size_t bytes, bool zero) {
     if (zero && bytes < 4) bytes = 4;
+    alloc_bytes += bytes;
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) {
       alloc_ok = false;

@@ -148,6 +148,20 @@ inline int check_slots(const skge_table_t* t, long long nslots, const char* name
   return SKGE_OK;
 }
 
+// the arguments of a stand-alone epoch draw (skge_epoch_sample_ex / _multi,
+// skge_pipe_epoch_sample): out0 / out1 its two output arrays, ntries_min 1, or
+// 0 for the pipelined draw
+inline int check_sample_args(const void* trip, const void* set, const void* epoch_key,
+                             const void* out0, const void* out1, int64_t T, int64_t set_capacity,
+                             int n_ent, int ntries, int ntries_min) {
+  SKGE_CHECK_ARG(trip && set && epoch_key && out0 && out1, "NULL argument");
+  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
+  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
+                 "set capacity must be a power of 2 >= 2T");
+  SKGE_CHECK_ARG(n_ent > 0 && ntries >= ntries_min, "bad n_ent / ntries");
+  return SKGE_OK;
+}
+
 inline TripleSet triple_set_view(const void* set, int64_t capacity) {
   TripleSet ts;
   ts.slots = (const int4*)set;

@@ -372,11 +372,8 @@ extern "C" int skge_epoch_sample_multi(void* stream, const int* trip, int64_t T,
                                        int64_t set_capacity, int n_ent, int n_rel, uint64_t seed,
                                        const uint64_t* epoch_key, int ntries, int* pos, int* neg,
                                        const skge_sampler_t* smp, const skge_negatives_t* negs) {
-  SKGE_CHECK_ARG(trip && set && epoch_key && pos && neg, "NULL argument");
-  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
-  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
-                 "set capacity must be a power of 2 >= 2T");
-  SKGE_CHECK_ARG(n_ent > 0 && ntries >= 1, "bad n_ent / ntries");
+  if (int rc = check_sample_args(trip, set, epoch_key, pos, neg, T, set_capacity, n_ent, ntries, 1))
+    return rc;
   return launch_epoch_sample_multi(as_stream(stream), trip, (long long)T, seed, epoch_key,
                                    triple_set_view(set, set_capacity), n_ent, n_rel, ntries, pos,
                                    neg, smp, negs);
@@ -386,11 +383,9 @@ extern "C" int skge_epoch_sample_ex(void* stream, const int* trip, int64_t T, co
                                     int64_t set_capacity, int n_ent, uint64_t seed,
                                     const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1,
                                     const skge_sampler_t* smp) {
-  SKGE_CHECK_ARG(trip && set && epoch_key && rec && rec_n1, "NULL argument");
-  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
-  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
-                 "set capacity must be a power of 2 >= 2T");
-  SKGE_CHECK_ARG(n_ent > 0 && ntries >= 1, "bad n_ent / ntries");
+  if (int rc = check_sample_args(trip, set, epoch_key, rec, rec_n1, T, set_capacity, n_ent,
+                                 ntries, 1))
+    return rc;
   if (int rc = check_sampler(smp, "epoch sample")) return rc;
   return launch_epoch_sample(as_stream(stream), trip, (long long)T, seed, epoch_key,
                              triple_set_view(set, set_capacity), n_ent, ntries, (int4*)rec,

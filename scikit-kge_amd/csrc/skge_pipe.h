@@ -5,6 +5,7 @@
 // The protocol itself is described at the top of skge_pipeline.hip.
 #pragma once
 #include "skge_host.h"
+#include "skge_pipe_plan.h"
 #include "skge_row_update.h"
 
 namespace skge {
@@ -20,15 +21,8 @@ namespace skge {
 // batch size this runner accepts.
 constexpr int PACKED_MAX = 32767;
 enum : int { ERR_WAIT = 1, ERR_PACKED = 2 };
-// hot rows (PipeTab::hot): replicas per row; a row is hot when its expected
-// slots per batch are >= HOT_MIN and >= HOT_REL x the average row's; at most
-// HOT_MAX rows.  WN18 Zipf(1.1), nb = 100, same box: HOT_MIN 16 / 8 / 4 ->
-// 110.6 / 116.1 / 117.4 M triples/s (4 replicas); 16 replicas 108.2 M (the
-// readers' fold: 97 VGPRs, 4 waves per SIMD; 4 replicas: 74 VGPRs, 6).  The
-// relative bar keeps a uniform KG's rows at large batches out (WN18 nb = 2:
-// ~3.5 slots per row and batch; hot rows there cost 531 / 519 vs 540 M).
-// (HOT_MIN 2 / 3, HOT_REL 4: within noise of these, same box)
-constexpr int HOT_REPS = 4, HOT_MIN = 4, HOT_REL = 8, HOT_MAX = 256;
+// (HOT_REPS and the other hot-row constants, SLOT_BUF and the workgroup
+// sizes: skge_pipe_plan.h, beside the decisions that use them)
 
 struct PipeTab {               // entity table
   float* P;
@@ -87,7 +81,6 @@ struct FusedTab {
                       // into the row; z: (id of the launch that last wrote the row << 1) |
                       // the buffer it wrote; w: id of the last launch that claimed its apply
 };
-constexpr int SLOT_BUF = 1 << 30;
 
 struct PipeArgs {
   PipeTab E;
@@ -561,16 +554,6 @@ __device__ __forceinline__ void rel_publish(const PipeArgs& a, int w, int rd, in
   if (c && a.R.updated && l == 0) atomicAdd(shard_of(a.R.updated), 1);
   if (!W32 && c > PACKED_MAX && l == 0) atomicOr(a.err, ERR_PACKED);
 }
-
-// large batches (owner marks, k_pipe_batch's GRP instances): 3-wave
-// workgroups (WN18 nb = 2, same box: 508-510 -> 520 M triples/s; 128: 517 M;
-// nb = 100 unchanged by either, so it keeps SKGE_PIPE_WG)
-constexpr int PIPE_WG_GRP = 192;
-#ifndef SKGE_PIPE_WG
-#define SKGE_PIPE_WG 256   // threads per workgroup
-#endif
-
-constexpr int HPIPE_OCC = 2;   // HolE: scoring waves per SIMD the apply-workgroup cap assumes (direct form)
 
 // skge_hole_pipe.hip's launchers (host side)
 void launch_hole_pipe(int km, bool pair, bool fft, dim3 gr, dim3 bl, size_t lds, hipStream_t st,

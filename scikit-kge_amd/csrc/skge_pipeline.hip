@@ -37,6 +37,8 @@
 // result is bitwise identical to the two-launch loop (tested).
 #include <algorithm>
 #include <cstdlib>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "skge_graph_runner.h"
@@ -54,11 +56,12 @@ namespace skge {
 #define SKGE_HPIPE_HOT 1
 #endif
 
-// k_pipe_batch: the runners k_pipe_fused (below) does not take.  pipe_create's
-// r->fused is the rule: the fused kernel for one-GPU TransE (not HolE, not the
-// data-parallel form) with batches of up to 16k slot records, fewer than 2^30
-// entity rows and, by default, rows of up to 64 floats; SKGE_PIPE_FUSED=1
-// extends it to rows of up to 256 floats, SKGE_PIPE_FUSED=0 turns it off.
+// k_pipe_batch: the runners k_pipe_fused (below) does not take.  The rule is
+// pipe_plan's `fused` (skge_pipe_plan.h), and it is written nowhere else:
+// the fused kernel for one-GPU TransE (not HolE, not the data-parallel form)
+// with batches of up to 16k slot records, fewer than 2^30 entity rows and, by
+// default, rows of up to 64 floats; SKGE_PIPE_FUSED=1 extends it to rows of up
+// to 256 floats, SKGE_PIPE_FUSED=0 turns it off.
 // This kernel takes everything else: wider rows (the flagship's d = 200),
 // larger batches, the data-parallel form.  nA apply workgroups
 // (dispatched first: they start the hand-offs the scoring waves may wait on),
@@ -988,12 +991,13 @@ using namespace skge;
 
 // ---- pipelined runner ----
 struct skge_pipe_runner : GraphRunnerCore {
+  PipePlan plan;                   // the form, the launches, the buffers' bytes (skge_pipe_plan.h)
   int* err = nullptr;
   int* stats = nullptr;            // [nlaunch][3] (profile only)
   // the epoch's launches
   const int* trip = nullptr;
   long long T = 0;
-  int half = 0, n_ent = 0, ntries = 0, kq = 1;
+  int half = 0, n_ent = 0, ntries = 0;
   uint64_t seed = 0;
   uint64_t* epoch_key = nullptr;   // the caller's word
   uint64_t* key_copy = nullptr;    // graph runners: the word the epoch's launches read
@@ -1002,108 +1006,88 @@ struct skge_pipe_runner : GraphRunnerCore {
   Pools pl = {nullptr, nullptr, 0};   // the caller's type index (pool kinds; not owned)
   int4* rec = nullptr;
   int* rec_n1 = nullptr;
-  std::vector<PipeArgs> batch;     // nb1 batches + the flush
-  std::vector<int> grid;
-  bool w32 = false;                // int32x2 relation sums
-  bool e8 = false;                 // int8x4 entity sums (SKGE_ACC_I8X4: per-batch counts <= 127)
-  bool hole = false;               // HolE pairwise (k_hole_pipe, fp32 sums)
-  bool fft = false;                // HolE: correlations in the frequency domain (skge_hole_fft.h)
-  bool rfold = false;              // TransE: relation sums in replicas, k_rel_fold after each batch
-  size_t lds = 0;                  // HolE: dynamic LDS per workgroup
-  bool pair = false;               // HolE FFT, d = 200: two waves per positive (while 2 x B waves fit the chip)
-  bool fused = false;              // TransE: k_pipe_fused (nothing waits; d <= 64 by default)
+  std::vector<PipeArgs> batch;     // nb1 batches + the flush (plan.launch's, with the pointers)
   bool invalid = false;            // an error bit was read or a launch failed: run() refuses
-  bool dp = false;                 // data-parallel form (SKGE_PIPE_DP): driven launch by launch
-  int n_rows = 0, d = 0;           // fused: the entity table's geometry (k_fused_fin)
-  int nlaunch() const { return (int)batch.size() + 2; }
+  int nlaunch() const { return plan.nlaunch(); }
 };
 
-static void launch_fused(const skge_pipe_runner* r, dim3 gr, hipStream_t st, const PipeArgs& a) {
+// Runtime flags into template arguments: f(KQ, flags...) is called with an
+// std::integral_constant for kq (1, 2 or 4 quads per lane) and one per flag.
+// f launches its kernel for the combinations that kernel's *_exists predicate
+// admits and returns false for any other, which no plan reaches.
+template <class F, class... C>
+static bool with_flags(F& f, std::tuple<C...>) {
+  return f(C{}...);
+}
+template <class F, class... C, class... B>
+static bool with_flags(F& f, std::tuple<C...>, bool b, B... rest) {
+  return b ? with_flags(f, std::tuple<C..., std::true_type>{}, rest...)
+           : with_flags(f, std::tuple<C..., std::false_type>{}, rest...);
+}
+template <class F, class... B>
+static bool with_kq_flags(F& f, int kq, B... flags) {
+  if (kq <= 1) return with_flags(f, std::tuple<std::integral_constant<int, 1>>{}, flags...);
+  if (kq <= 2) return with_flags(f, std::tuple<std::integral_constant<int, 2>>{}, flags...);
+  return with_flags(f, std::tuple<std::integral_constant<int, 4>>{}, flags...);
+}
+
+// The instances that exist.  k_pipe_fused: rows of one quad per lane (the
+// plan's nq <= 64).  k_pipe_batch: no int8 sums with hot rows (a hub's count
+// leaves the int8 range), no hot rows in the data-parallel form (it keeps
+// every row in the tables).  k_pipe_dp_scatter: every combination.
+constexpr bool pipe_fused_exists(int kq) { return kq == 1; }
+constexpr bool pipe_batch_exists(bool e8, bool hot, bool dp) {
+  return !(e8 && hot) && !(dp && hot);
+}
+
+static bool no_instance(const char* kernel, const PipePlan& p, bool hot) {
+  set_error("pipelined runner: no %s instance for kq %d, w32 %d, e8 %d, grouped %d, hot %d, dp %d",
+            kernel, p.kq, p.w32, p.e8, p.grouped, hot, p.dp);
+  return false;
+}
+
+static bool launch_fused(const skge_pipe_runner* r, dim3 gr, hipStream_t st, const PipeArgs& a) {
   const dim3 bl(SKGE_PIPE_WG);
-  if (r->e8) {
-    if (r->w32) hipLaunchKernelGGL((k_pipe_fused<1, true, true>), gr, bl, 0, st, a);
-    else hipLaunchKernelGGL((k_pipe_fused<1, false, true>), gr, bl, 0, st, a);
-  } else {
-    if (r->w32) hipLaunchKernelGGL((k_pipe_fused<1, true, false>), gr, bl, 0, st, a);
-    else hipLaunchKernelGGL((k_pipe_fused<1, false, false>), gr, bl, 0, st, a);
-  }
+  auto go = [&](auto K, auto W32, auto E8) {
+    if constexpr (pipe_fused_exists(K())) {
+      hipLaunchKernelGGL((k_pipe_fused<K(), W32(), E8()>), gr, bl, 0, st, a);
+      return true;
+    } else {
+      return false;
+    }
+  };
+  const PipePlan& p = r->plan;
+  return with_kq_flags(go, p.kq, p.w32, p.e8) || no_instance("k_pipe_fused", p, false);
 }
 
 // k_pipe_batch: the instance for this runner's row width, sums and batch size
-static void launch_pipe_batch(const skge_pipe_runner* r, dim3 gr, hipStream_t st,
+// (own marks: large batches, the grouped owner-row apply; nhot: hot-row replicas)
+static bool launch_pipe_batch(const skge_pipe_runner* r, dim3 gr, hipStream_t st,
                               const PipeArgs& a) {
-#define SKGE_PB(K)                                                                        \
-  do {                                                                                    \
-    /* own marks: large batches (grouped owner-row apply); nhot: hot-row replicas */     \
-    const bool gp_ = a.E.own[0] != nullptr, hot_ = a.E.nhot > 0;                          \
-    const dim3 bl(gp_ ? PIPE_WG_GRP : SKGE_PIPE_WG);                      \
-    if (r->e8) {                                                                          \
-      if (gp_) {                                                                          \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, true, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, true, true>), gr, bl, 0, st, a);  \
-      } else {                                                                            \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, true>), gr, bl, 0, st, a);  \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, true>), gr, bl, 0, st, a);        \
-      }                                                                                   \
-    } else if (hot_) {                                                                    \
-      if (gp_) {                                                                          \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false, true, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, false, true, true>), gr, bl, 0, st, a); \
-      } else {                                                                            \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false, false, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, false, false, true>), gr, bl, 0, st, a); \
-      }                                                                                   \
-    } else if (gp_) {                                                                     \
-      if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false, true>), gr, bl, 0, st, a); \
-      else hipLaunchKernelGGL((k_pipe_batch<K, false, false, true>), gr, bl, 0, st, a);   \
-    } else {                                                                              \
-      if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false>), gr, bl, 0, st, a);   \
-      else hipLaunchKernelGGL((k_pipe_batch<K, false, false>), gr, bl, 0, st, a);         \
-    }                                                                                     \
-  } while (0)
-// the data-parallel instances (no hot rows in that form)
-#define SKGE_PBD(K)                                                                       \
-  do {                                                                                    \
-    const bool gp_ = a.E.own[0] != nullptr;                                               \
-    const dim3 bl(gp_ ? PIPE_WG_GRP : SKGE_PIPE_WG);                                      \
-    if (gp_) {                                                                            \
-      if (r->e8) {                                                                        \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, true, true, false, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, true, true, false, true>), gr, bl, 0, st, a); \
-      } else {                                                                            \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false, true, false, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, false, true, false, true>), gr, bl, 0, st, a); \
-      }                                                                                   \
-    } else {                                                                              \
-      if (r->e8) {                                                                        \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, true, false, false, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, true, false, false, true>), gr, bl, 0, st, a); \
-      } else {                                                                            \
-        if (r->w32) hipLaunchKernelGGL((k_pipe_batch<K, true, false, false, false, true>), gr, bl, 0, st, a); \
-        else hipLaunchKernelGGL((k_pipe_batch<K, false, false, false, false, true>), gr, bl, 0, st, a); \
-      }                                                                                   \
-    }                                                                                     \
-  } while (0)
-  if (r->dp) {
-    if (r->kq <= 1) SKGE_PBD(1);
-    else if (r->kq <= 2) SKGE_PBD(2);
-    else SKGE_PBD(4);
-  } else {
-    if (r->kq <= 1) SKGE_PB(1);
-    else if (r->kq <= 2) SKGE_PB(2);
-    else SKGE_PB(4);
-  }
-#undef SKGE_PBD
-#undef SKGE_PB
+  const PipePlan& p = r->plan;
+  const dim3 bl(p.threads());
+  auto go = [&](auto K, auto W32, auto E8, auto GRP, auto HOT, auto DP) {
+    if constexpr (pipe_batch_exists(E8(), HOT(), DP())) {
+      hipLaunchKernelGGL((k_pipe_batch<K(), W32(), E8(), GRP(), HOT(), DP()>), gr, bl, 0, st, a);
+      return true;
+    } else {
+      return false;
+    }
+  };
+  const bool hot = a.E.nhot > 0;
+  return with_kq_flags(go, p.kq, p.w32, p.e8, p.grouped, hot, p.dp) ||
+         no_instance("k_pipe_batch", p, hot);
 }
 
 // Enqueue one epoch: draw the negatives, nb1 batch launches, the flush (which
 // advances the key).  ev (profile(): nlaunch + 1 events) brackets every launch
 // and, in that eager epoch only, a key advance as a launch of its own (its
 // flush leaves the key alone), so us_out keeps its draw and advance entries;
-// stats (optional) collects per-launch claim / violation counts.
-static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t* ev, int* stats,
+// stats (optional) collects per-launch claim / violation counts.  false (and
+// the error text): a batch has no kernel instance.
+static bool enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t* ev, int* stats,
                           int trace_launch = -1, unsigned long long* trace = nullptr) {
+  const PipePlan& p = r->plan;
   int i = 0;
   if (ev) (void)hipEventRecord(ev[i], st);
   launch_pipe_sample(st, r->trip, r->T, r->half, r->seed, (const uint64_t*)r->epoch_key, r->set,
@@ -1121,17 +1105,15 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
     }
     if (trace && i == trace_launch) a.trace = trace;
     if (ev) a.key_next = nullptr;   // (k_pipe_advance below)
-    if (r->hole) {
-      launch_hole_pipe(km_for(a.d), r->pair, r->fft, dim3(r->grid[k]),
-                       dim3(r->pair ? 128 : SKGE_PIPE_WG), r->lds, st, a);
-    } else if (r->fused) {
-      launch_fused(r, dim3(r->grid[k]), st, a);
-    } else {
-      launch_pipe_batch(r, dim3(r->grid[k]), st, a);
+    const dim3 gr(p.launch[k].grid);
+    if (p.hole) {
+      launch_hole_pipe(km_for(a.d), p.pair, p.fft, gr, dim3(p.threads()), p.lds, st, a);
+    } else if (!(p.fused ? launch_fused(r, gr, st, a) : launch_pipe_batch(r, gr, st, a))) {
+      return false;
     }
-    if (r->rfold && a.count > 0) {
+    if (p.rfold && a.count > 0) {
       const size_t words = (size_t)a.R.rows * a.R.rw;
-      if (r->hole)   // fp32 sums + an int count per row
+      if (p.hole)   // fp32 sums + an int count per row
         launch_rel_fold_f(dim3((unsigned)std::min<size_t>((2 * words + 255) / 256, 4096)), st, a);
       else
         hipLaunchKernelGGL(k_rel_fold, dim3((unsigned)std::min<size_t>((words + 255) / 256, 4096)),
@@ -1143,6 +1125,7 @@ static void enqueue_epoch(const skge_pipe_runner* r, hipStream_t st, hipEvent_t*
     hipLaunchKernelGGL(k_pipe_advance, dim3(1), dim3(1), 0, st, r->epoch_key);
     (void)hipEventRecord(ev[i + 1], st);
   }
+  return true;
 }
 
 // Hot rows around a run: before the first launch g0 (from the epoch key) the
@@ -1186,12 +1169,13 @@ static void hot_io(const skge_pipe_runner* r, hipStream_t st, bool back) {
 
 // fused runner: every row back into the caller's tables (buffer 0), meta cleared
 static void fused_finalize(const skge_pipe_runner* r, hipStream_t st) {
-  if (!r->fused) return;
+  const PipePlan& p = r->plan;
+  if (!p.fused) return;
   const FusedTab& F = r->batch[0].F;
-  const long long n = (long long)r->n_rows * (r->d / 4);
+  const long long n = (long long)p.N * (p.d / 4);
   const unsigned blocks = (unsigned)std::max(1ll, std::min((n + 255) / 256, 8192ll));
-  hipLaunchKernelGGL(k_fused_fin, dim3(blocks), dim3(256), 0, st, F, r->n_rows, r->d);
-  (void)hipMemsetAsync(F.meta, 0, (size_t)r->n_rows * sizeof(int4), st);
+  hipLaunchKernelGGL(k_fused_fin, dim3(blocks), dim3(256), 0, st, F, p.N, p.d);
+  (void)hipMemsetAsync(F.meta, 0, p.bytes.ent_meta, st);
 }
 
 // Hot rows (PipeTab::hot): entities whose subject / object occurrences in the
@@ -1273,8 +1257,10 @@ static bool hot_negatives() {
 }
 
 static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const int* trip,
-                          long long T, int nb1, int N, int d, int row_words,
                           const skge_sampler_t* smp = nullptr) {
+  const PipeBytes& sz = r->plan.bytes;
+  const long long T = r->plan.T;
+  const int nb1 = r->plan.nb1, N = r->plan.N;
   t.hot = t.hot_rows = nullptr;
   t.nhot = 0;
   int* occ = nullptr;
@@ -1310,16 +1296,16 @@ static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const
     rows[j] = cand[j].second;
     h[rows[j]] = j;
   }
-  t.hw = (row_words + 15) / 16 * 16;   // 8-B words per replica row: whole 128-B lines
-  int* dh = (int*)r->alloc((size_t)N * 4, true);
-  int* dr = (int*)r->alloc((size_t)nh * 4, true);
+  t.hw = r->plan.hw;
+  int* dh = (int*)r->alloc(sz.ent_word, true);
+  int* dr = (int*)r->alloc(nh * sz.hot_row, true);
   for (int k = 0; k < 3; ++k) {
-    t.hsum[k] = (unsigned long long*)r->alloc((size_t)nh * HOT_REPS * t.hw * 8, true);
-    t.hcnt[k] = (int*)r->alloc((size_t)nh * HOT_REPS * 4, true);
+    t.hsum[k] = (unsigned long long*)r->alloc(nh * sz.hot_sum, true);
+    t.hcnt[k] = (int*)r->alloc(nh * sz.hot_cnt, true);
   }
   for (int k = 0; k < 2; ++k) {
-    t.hP[k] = (float*)r->alloc((size_t)nh * d * 4, true);
-    t.hA[k] = t.A ? (float*)r->alloc((size_t)nh * d * 4, true) : nullptr;
+    t.hP[k] = (float*)r->alloc(nh * sz.hot_val, true);
+    t.hA[k] = r->plan.ent_ada ? (float*)r->alloc(nh * sz.hot_val, true) : nullptr;
   }
   if (!r->alloc_ok ||
       hipMemcpy(dh, h.data(), (size_t)N * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1331,96 +1317,120 @@ static bool find_hot_rows(skge_pipe_runner* r, hipStream_t st, PipeTab& t, const
   return true;
 }
 
-static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
-                                       const skge_table_t* rel, int d, const int* trip, int64_t T,
-                                       const void* set, int64_t set_capacity, int nbatches,
-                                       uint64_t seed, uint64_t* epoch_key, float margin,
-                                       int ntries, int* nviol_total, int flags, bool hole, int af,
-                                       const skge_sampler_t* smp = nullptr) {
-  if (check_sampler(smp, "pipelined runner")) return nullptr;
-  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
-  if (flags & ~SKGE_PIPE_DP) {
-    set_error("pipelined runner: unknown flags %d", flags);
-    return nullptr;
+// What the plan takes from outside skge_pipe_plan.h: the environment switches
+// (read here and nowhere else) and the HolE kernels' LDS sizes.  No HIP call.
+static PipeEnv pipe_env(int d, bool hole) {
+  PipeEnv e;
+  if (const char* f = getenv("SKGE_PIPE_FUSED")) e.fused = atoi(f) != 0;
+  if (const char* q = getenv("SKGE_HPIPE_RREPS")) e.rreps = atoi(q);
+  e.hole_hot = SKGE_HPIPE_HOT != 0;
+  e.shard_words = NSHARD * SHARD_STRIDE;
+  if (hole) {
+    e.hole_fft = hole_use_fft(d);
+    e.lds_fft_wave = hole_fft_lds_bytes(d, 1);
+    e.lds_fft_wg = hole_fft_lds_bytes(d, SKGE_PIPE_WG / 64);
+    e.lds_direct_wg = (size_t)(SKGE_PIPE_WG / 64) * hole_pos_lds_floats(d) * sizeof(float);
   }
+  return e;
+}
+
+// What the runner refuses about its form and its tables' geometry, for
+// pipe_create and skge_pipe_runner_plan alike (kind: the sampler's).  No HIP
+// call, no pointer dereferenced.
+static bool pipe_check_tables(const skge_table_t* ent, const skge_table_t* rel, int d, int flags,
+                              bool hole, int af, int kind) {
+  if (flags & ~SKGE_PIPE_DP) return set_error("pipelined runner: unknown flags %d", flags), false;
   const bool dp = (flags & SKGE_PIPE_DP) != 0;
-  if (dp && hole) {
-    set_error("pipelined runner: the data-parallel form is TransE-L1 only");
-    return nullptr;
-  }
-  if (dp && kind != SKGE_SAMPLER_RANDOM) {
-    set_error("pipelined runner: the data-parallel form (SKGE_PIPE_DP) draws RANDOM negatives "
-              "only, not sampler kind %d", kind);
-    return nullptr;
-  }
-  if (!ent || !rel) {
-    set_error("pipelined runner: NULL table");
-    return nullptr;
-  }
+  if (dp && hole)
+    return set_error("pipelined runner: the data-parallel form is TransE-L1 only"), false;
+  if (dp && kind != SKGE_SAMPLER_RANDOM)
+    return set_error("pipelined runner: the data-parallel form (SKGE_PIPE_DP) draws RANDOM negatives "
+                "only, not sampler kind %d", kind), false;
+  if (!ent || !rel) return set_error("pipelined runner: NULL table"), false;
   skge_table_t relc = *rel;   // the relation encoding is the runner's own (checked below)
   if (relc.acc_mode == SKGE_ACC_I32X2) relc.acc_mode = SKGE_ACC_I16X4;
   skge_table_t entc = *ent;   // int8x4 entity sums: the runner's own encoding too
   if (entc.acc_mode == SKGE_ACC_I8X4) entc.acc_mode = SKGE_ACC_I16X4;
-  if (check_table(&entc, "ent", true) || check_table(&relc, "rel", true)) return nullptr;
+  if (check_table(&entc, "ent", true) || check_table(&relc, "rel", true)) return false;
   if (hole) {   // HolE: fp32 sums, quad rows (d % 4 == 0, d <= 256)
     if (ent->acc_mode != SKGE_ACC_F32 || rel->acc_mode != SKGE_ACC_F32 || d % 4 || d < 4 ||
         d > 256 || ent->width != d || rel->width != d || ent->acc_touched == nullptr ||
         rel->acc_touched != nullptr || rel->acc_replicas > 1 || ent->acc_replicas > 1 ||
-        ent->gate || rel->gate || af < 0 || af > 3) {
-      set_error("pipelined HolE runner: needs fp32 accumulators (entity table with slot "
-                "records, dense single-copy relation table), d %% 4 == 0, 4 <= d <= 256, no "
-                "gates");
-      return nullptr;
-    }
+        ent->gate || rel->gate || af < 0 || af > 3)
+      return set_error("pipelined HolE runner: needs fp32 accumulators (entity table with slot "
+                  "records, dense single-copy relation table), d %% 4 == 0, 4 <= d <= 256, no "
+                  "gates"), false;
   } else if ((ent->acc_mode != SKGE_ACC_I16X4 && ent->acc_mode != SKGE_ACC_I8X4) ||
       (rel->acc_mode != SKGE_ACC_I16X4 && rel->acc_mode != SKGE_ACC_I32X2) || d % 4 || d > 1024 ||
       ent->width != d || rel->width != d || ent->acc_touched == nullptr ||
       rel->acc_touched != nullptr || rel->acc_replicas > 1 || ent->acc_replicas > 1 ||
       ent->gate || rel->gate) {
-    set_error("pipelined runner: needs a packed (SKGE_ACC_I16X4) entity table with slot "
-              "records, a dense single-copy SKGE_ACC_I16X4 / SKGE_ACC_I32X2 relation table, "
-              "d %% 4 == 0, no gates");
-    return nullptr;
+    return set_error("pipelined runner: needs a packed (SKGE_ACC_I16X4) entity table with slot "
+                "records, a dense single-copy SKGE_ACC_I16X4 / SKGE_ACC_I32X2 relation table, "
+                "d %% 4 == 0, no gates"), false;
   }
-  // (any T -- the slot capacity bounds the batch -- and any set of >= 4 slots)
-  if (!check_runner_args("pipelined runner", trip, set, epoch_key, T, INT64_MAX, nbatches,
-                         set_capacity, 4, ntries, stream))
-    return nullptr;
+  return true;
+}
+
+// ... and about the batch: its slot records must fit the entity table's
+static bool pipe_check_batch(const skge_table_t* ent, int64_t T, int nbatches) {
   const int64_t bs = T / nbatches;
   if (4 * bs > ent->touched_cap || 4 * bs > (1ll << 30))
-    return fail("pipelined runner: batch too large for the slot capacity");
-  const EpochBatches batches = epoch_batches(T, nbatches);
-  const int nb1 = batches.size();
-  const int64_t maxb = batches.maxb;
-  std::unique_ptr<skge_pipe_runner> r(new skge_pipe_runner());
-  r->hole = hole;
-  r->dp = dp;
-  r->kind = kind;
-  if (kind != SKGE_SAMPLER_RANDOM)
-    r->pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
-  // HolE at d = 200 in the FFT form: two waves per positive (the pair form)
-  // while the batch's 2 x B scoring waves fit the chip's 4-wave-per-SIMD
-  // residency.  WN18 d = 200, same box: nb = 100 93.7 -> 106.7 M triples/s
-  // (14.6 -> 12.8 us per launch); nb = 2 (70k positives per launch) 157 ->
-  // 142 M, so off there
-  const bool hole_pair = hole && hole_use_fft(d) && d == 200 && 2 * maxb <= 4 * 4 * 256;
-  r->e8 = !hole && ent->acc_mode == SKGE_ACC_I8X4;
-  const int nq = d / 4;
-  const int N = ent->rows;
-  // large batches (more than 16k slot records): owner marks, k_pipe_batch's A
-  // role scans its slots 64 at a time
-  const bool grouped = !hole && 4 * bs > 4 * 4096;
-  // TransE below that: k_pipe_fused for rows of up to 64 floats (WN18 d = 50
-  // on its 64-wide padded tables: 10.52 -> 10.08 us per launch, same box),
-  // k_pipe_batch above (d = 200: 8.48 vs 9.78 us -- at 800-B rows the fused
-  // kernel's second-buffer loads and rotating copies cost more than its
-  // waits save).  SKGE_PIPE_FUSED=0 / 1 forces either (d <= 256).
-  {
-    const char* fe = getenv("SKGE_PIPE_FUSED");
-    const bool ok = !hole && !grouped && nq <= 64 && (long long)N < SLOT_BUF;
-    r->fused = ok && !dp && (fe ? atoi(fe) != 0 : nq <= 16);
+    return fail("pipelined runner: batch too large for the slot capacity"), false;
+  return true;
+}
+
+// The buffers of the plan's form into a: every size is the plan's.  false: an
+// allocation (or the hot rows' search) failed.
+static bool pipe_alloc(skge_pipe_runner* r, hipStream_t st, PipeArgs& a, const int* trip,
+                       const skge_sampler_t* smp) {
+  const PipePlan& p = r->plan;
+  const PipeBytes& sz = p.bytes;
+  bool ok = true;
+  PipeTab& t = a.E;
+  if (p.fused) {
+    // the second row buffer, the other two accumulator copies, the meta words
+    FusedTab& F = a.F;
+    F.P[1] = (float*)r->alloc(sz.ent_rows, true);
+    F.A[1] = p.ent_ada ? (float*)r->alloc(sz.ent_rows, true) : nullptr;
+    for (int k = 1; k < 3; ++k) {
+      F.sum[k] = r->alloc(sz.ent_sum, true);
+      F.cnt[k] = (int*)r->alloc(sz.ent_word, true);
+      F.touched[k] = (int*)r->alloc(sz.slots, true);
+    }
+    F.meta = (int4*)r->alloc(sz.ent_meta, true);
+  } else {
+    // a second accumulator copy, slot records, batch marks, done words
+    t.done = (int*)r->alloc(sz.ent_word, true);
+    t.sum[1] = (unsigned long long*)r->alloc(sz.ent_sum, true);
+    t.cnt[1] = (int*)r->alloc(sz.ent_word, true);
+    t.touched[1] = (int*)r->alloc(sz.slots, true);
+    t.pend[0] = (int*)r->alloc(sz.ent_word, true);
+    t.pend[1] = (int*)r->alloc(sz.ent_word, true);
+    if (p.grouped) {
+      t.own[0] = (int*)r->alloc(sz.ent_word, true);
+      t.own[1] = (int*)r->alloc(sz.ent_word, true);
+    }
+    if (r->alloc_ok && p.hot) ok = find_hot_rows(r, st, t, trip, hot_negatives() ? smp : nullptr);
   }
-  PipeArgs a = {};
+  RelTab& q = a.R;
+  q.P[1] = (float*)r->alloc(sz.rel_rows, true);
+  q.A[1] = p.rel_ada ? (float*)r->alloc(sz.rel_rows, true) : nullptr;
+  for (int k = 0; k < 3; ++k) q.acc[k] = (unsigned long long*)r->alloc(sz.rel_acc, true);
+  r->rec = (int4*)r->alloc(sz.rec, true);
+  r->rec_n1 = (int*)r->alloc(sz.rec_n1, true);
+  r->err = (int*)r->alloc(sz.err, true);
+  r->key_copy = p.dp ? nullptr : (uint64_t*)r->alloc(sz.key_copy, true);
+  r->stats = (int*)r->alloc(sz.stats, true);
+  a.nviol_shards = (int*)r->alloc(sz.viol, true);
+  return ok && r->alloc_ok;
+}
+
+// The launches' arguments: the caller's tables and the runner's buffers (a,
+// after pipe_alloc) under the plan's form, then one PipeArgs per launch.
+static void pipe_fill_args(skge_pipe_runner* r, PipeArgs a, const skge_table_t* ent,
+                           const skge_table_t* rel, float margin, int* nviol_total, int af) {
+  const PipePlan& p = r->plan;
   auto upd = [](const skge_table_t* s) {
     UpdParams u;
     u.opt = s->opt;
@@ -1431,192 +1441,135 @@ static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
     u.fdiv = s->fixed_div;
     return u;
   };
-  bool ok = true;
-  {
-    PipeTab& t = a.E;
-    t.P = ent->param;
-    t.A = ent->opt == SKGE_ADAGRAD ? ent->state : nullptr;
-    t.u = upd(ent);
-    t.claims = nullptr;
-    t.err = nullptr;   // set below, once r->err exists
-    t.sum[0] = reinterpret_cast<unsigned long long*>(ent->acc_sum);
-    t.cnt[0] = ent->acc_cnt;
-    t.touched[0] = ent->acc_touched;
-    if (r->fused) {
-      // the second row buffer, the other two accumulator copies, the meta words
-      FusedTab& F = a.F;
-      const size_t sb = (size_t)N * nq * (r->e8 ? 4 : 8);
-      F.P[0] = ent->param;
-      F.P[1] = (float*)r->alloc((size_t)N * d * 4, true);
-      F.A[0] = t.A;
-      F.A[1] = F.A[0] ? (float*)r->alloc((size_t)N * d * 4, true) : nullptr;
-      F.sum[0] = ent->acc_sum;
-      F.cnt[0] = ent->acc_cnt;
-      F.touched[0] = ent->acc_touched;
-      for (int k = 1; k < 3; ++k) {
-        F.sum[k] = r->alloc(sb, true);
-        F.cnt[k] = (int*)r->alloc((size_t)N * 4, true);
-        F.touched[k] = (int*)r->alloc((size_t)4 * bs * 4, true);
-      }
-      F.meta = (int4*)r->alloc((size_t)N * sizeof(int4), true);
-      r->n_rows = N;
-      r->d = d;
-    } else {
-      // a second accumulator copy, slot records, batch marks, done words
-      t.done = (int*)r->alloc((size_t)N * 4, true);
-      t.sum[1] = (unsigned long long*)r->alloc((size_t)N * nq * (hole ? 16 : (r->e8 ? 4 : 8)),
-                                               true);
-      t.cnt[1] = (int*)r->alloc((size_t)N * 4, true);
-      t.touched[1] = (int*)r->alloc((size_t)4 * bs * 4, true);
-      t.pend[0] = (int*)r->alloc((size_t)N * 4, true);
-      t.pend[1] = (int*)r->alloc((size_t)N * 4, true);
-      if (grouped) {
-        t.own[0] = (int*)r->alloc((size_t)N * 4, true);
-        t.own[1] = (int*)r->alloc((size_t)N * 4, true);
-      }
-      // (the data-parallel form keeps every row in the tables: no hot rows;
-      // HolE: the pair form only, fp32 sums of d floats per replica row)
-      if (r->alloc_ok && !r->e8 && !dp && (!hole || (hole_pair && SKGE_HPIPE_HOT)))
-        ok = find_hot_rows(r.get(), as_stream(stream), t, trip, T, nb1, N, d, hole ? d / 2 : nq,
-                           hot_negatives() ? smp : nullptr);
-    }
-    RelTab& q = a.R;
-    const int M = rel->rows;
-    const bool ada = rel->opt == SKGE_ADAGRAD;
-    q.rows = M;
-    // HolE (fp32 sums, float atomics): at large batches every relation row
-    // takes thousands of adds per launch, which serialise on its addresses;
-    // spread them over replicas (one per ~2k positives, <= 32; 1 at nb = 100)
-    q.reps = 1;
-    if (hole)
-      while (q.reps < 32 && (long long)q.reps * 2048 < bs) q.reps *= 2;
-    if (hole && getenv("SKGE_HPIPE_RREPS")) q.reps = std::max(1, atoi(getenv("SKGE_HPIPE_RREPS")));
-    // TransE, large batches (the A role's owner-mark regime): the same spread,
-    // one replica per ~256 expected adds into a row (bs / M), <= 16, folded by
-    // k_rel_fold after every batch launch (WN18 nb = 2: 16; nb = 100: 1)
-    if (grouped) {
-      const long long per_row = bs / std::max(1, M);
-      while (q.reps < 16 && (long long)q.reps * 256 < per_row) q.reps *= 2;
-    }
-    r->rfold = q.reps > 1;
-    q.folded = r->rfold ? 1 : 0;
-    r->w32 = rel->acc_mode == SKGE_ACC_I32X2;
-    // 8-B words per relation row: sums + count, whole 128-B lines (HolE: d
-    // floats, then the count as an int)
-    q.rw = hole ? ((d + 2) / 2 + 15) / 16 * 16 : ((r->w32 ? 2 * nq : nq) + 1 + 15) / 16 * 16;
-    q.u = upd(rel);
-    q.updated = nullptr;
-    q.P[0] = rel->param;
-    q.P[1] = (float*)r->alloc((size_t)M * d * 4, true);
-    q.A[0] = ada ? rel->state : nullptr;
-    q.A[1] = ada ? (float*)r->alloc((size_t)M * d * 4, true) : nullptr;
-    for (int k = 0; k < 3; ++k)
-      q.acc[k] = (unsigned long long*)r->alloc((size_t)q.reps * M * q.rw * 8, true);
+  PipeTab& t = a.E;
+  t.P = ent->param;
+  t.A = p.ent_ada ? ent->state : nullptr;
+  t.u = upd(ent);
+  t.err = r->err;
+  t.sum[0] = reinterpret_cast<unsigned long long*>(ent->acc_sum);
+  t.cnt[0] = ent->acc_cnt;
+  t.touched[0] = ent->acc_touched;
+  if (p.fused) {
+    FusedTab& F = a.F;
+    F.P[0] = ent->param;
+    F.A[0] = t.A;
+    F.sum[0] = ent->acc_sum;
+    F.cnt[0] = ent->acc_cnt;
+    F.touched[0] = ent->acc_touched;
   }
-  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), true);
-  r->rec_n1 = (int*)r->alloc((size_t)T * 4, true);
-  r->err = (int*)r->alloc(4, true);
-  r->key_copy = dp ? nullptr : (uint64_t*)r->alloc(8, true);
-  r->stats = (int*)r->alloc((size_t)(nb1 + 3) * 3 * NSHARD * SHARD_STRIDE * 4, true);
-  int* vsh = (int*)r->alloc((size_t)NSHARD * SHARD_STRIDE * 4, true);
-  if (!ok || !r->alloc_ok) return fail("pipelined runner: device allocation failed");
+  RelTab& q = a.R;
+  q.rows = p.M;
+  q.reps = p.reps;
+  q.folded = p.rfold ? 1 : 0;
+  q.rw = p.rw;
+  q.u = upd(rel);
+  q.P[0] = rel->param;
+  q.A[0] = p.rel_ada ? rel->state : nullptr;
+  a.rec = r->rec;
+  a.rec_n1 = r->rec_n1;
+  a.nb1 = p.nb1;
+  a.epoch_key = p.dp ? r->epoch_key : r->key_copy;
+  a.d = p.d;
+  a.margin = margin;
+  a.nviol_total = nviol_total;
+  a.err = r->err;
+  a.af = af;
+  // the relation row's loads and update on wave 1 (3 rows each; same box,
+  // two rounds: 103.8 -> 104.6 M triples/s)
+  a.pair_r1 = 1;
+  for (int b = 0; b <= p.nb1; ++b) {   // b == nb1: flush of the last batch (no scoring)
+    const PipeLaunch& L = p.launch[b];
+    a.b = b;
+    a.start = L.start;
+    a.count = L.count;
+    a.lo = 0;
+    a.hi = a.count;
+    a.key_next = !p.dp && b == p.nb1 ? r->epoch_key : nullptr;
+    a.prev_slots = L.prev_slots;
+    a.pprev_slots = L.pprev_slots;
+    a.nwork = L.nwork;
+    a.nA = L.nA;
+    r->batch.push_back(a);
+  }
+}
+
+// refuse, plan, allocate from the plan's sizes, fill PipeArgs from the plan, capture
+static skge_pipe_runner_t* pipe_create(void* stream, const skge_table_t* ent,
+                                       const skge_table_t* rel, int d, const int* trip, int64_t T,
+                                       const void* set, int64_t set_capacity, int nbatches,
+                                       uint64_t seed, uint64_t* epoch_key, float margin,
+                                       int ntries, int* nviol_total, int flags, bool hole, int af,
+                                       const skge_sampler_t* smp = nullptr) {
+  if (check_sampler(smp, "pipelined runner")) return nullptr;
+  const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
+  if (!pipe_check_tables(ent, rel, d, flags, hole, af, kind)) return nullptr;
+  // (any T -- the slot capacity bounds the batch -- and any set of >= 4 slots)
+  if (!check_runner_args("pipelined runner", trip, set, epoch_key, T, INT64_MAX, nbatches,
+                         set_capacity, 4, ntries, stream))
+    return nullptr;
+  if (!pipe_check_batch(ent, T, nbatches)) return nullptr;
+  hipStream_t st = as_stream(stream);
+  std::unique_ptr<skge_pipe_runner> r(new skge_pipe_runner());
+  r->plan = pipe_plan(ent, rel, d, T, nbatches, flags, hole, pipe_env(d, hole));
+  const PipePlan& p = r->plan;
+  r->kind = kind;
+  if (kind != SKGE_SAMPLER_RANDOM)
+    r->pl = {(const long long*)smp->pool_off, smp->pool_ent, smp->n_rel};
   r->trip = trip;
   r->T = T;
   r->half = perm_half(T);
-  r->n_ent = N;
+  r->n_ent = p.N;
   r->ntries = ntries;
   r->seed = seed;
   r->epoch_key = epoch_key;
   r->set = triple_set_view(set, set_capacity);
-  r->kq = (nq + 63) / 64;
-  a.rec = r->rec;
-  a.rec_n1 = r->rec_n1;
-  a.nb1 = nb1;
-  a.epoch_key = dp ? epoch_key : r->key_copy;
-  a.d = d;
-  a.margin = margin;
-  a.nviol_total = nviol_total;
-  a.nviol_shards = vsh;
-  a.stats_viol = nullptr;
-  a.trace = nullptr;
-  a.err = r->err;
-  a.E.err = r->err;
-  a.af = af;
-  r->fft = hole && hole_use_fft(d);
-  {
-    r->pair = hole_pair;
-    // the relation row's loads and update on wave 1 (3 rows each; same box,
-    // two rounds: 103.8 -> 104.6 M triples/s)
-    a.pair_r1 = 1;
-  }
-  a.tw = r->fft ? hole_fft_table(d) : nullptr;
-  if (r->fft && !a.tw) return fail("pipelined runner: HolE FFT twiddle table allocation failed");
-  r->lds = !hole ? 0
-           : r->pair ? hole_fft_lds_bytes(d, 1)
-           : r->fft ? hole_fft_lds_bytes(d, SKGE_PIPE_WG / 64)
-                    : (size_t)(SKGE_PIPE_WG / 64) * hole_pos_lds_floats(d) * sizeof(float);
-  const int WPB = r->pair ? 2 : (grouped ? PIPE_WG_GRP : SKGE_PIPE_WG) / 64;
-  for (int b = 0; b <= nb1; ++b) {   // b == nb1: flush of the last batch (no scoring)
-    a.b = b;
-    a.start = b < nb1 ? batches[b].first : 0;
-    a.count = b < nb1 ? (int)batches[b].second : 0;
-    a.lo = 0;
-    a.hi = a.count;
-    a.dprec = nullptr;
-    a.key_next = !dp && b == nb1 ? epoch_key : nullptr;
-    const int cprev = b >= 1 ? (int)batches[b - 1].second : 0;
-    a.prev_slots = 4 * cprev;
-    if (r->fused) {
-      // one kind of wave: relation rows, then max(this, the previous and the
-      // pre-previous batch's positives) work items.  The epoch starts clean (the
-      // flush zeroes both copies it leaves), so the first two launches have no
-      // pre-previous slots to zero
-      const int cpp = b >= 2 ? (int)batches[b - 2].second : 0;
-      a.pprev_slots = 4 * cpp;
-      a.nwork = a.count + std::max(cprev, cpp);   // scoring items, then slot groups
-      a.nA = 0;
-      r->batch.push_back(a);
-      r->grid.push_back(std::max(1, (rel->rows + a.nwork + WPB - 1) / WPB));
-      continue;
-    }
-    // A role: every relation row, then the previous batch's entity slots
-    // (owner marks: 64-slot groups)
-    const int a_items = rel->rows + a.E.nhot +
-                        (hole ? 4 * cprev
-                         : grouped ? (4 * cprev + 63) / 64 : 4 * cprev);
-    // HolE: the apply waves loop over their items within the residency the
-    // scoring waves leave (direct form: 2 waves per SIMD at ~180 VGPRs; FFT: 4
-    // -- caps 150 / 250 / 400 / 600 / 800 / 1100 on WN18 d = 200: 74.7 / 77.6 /
-    // 80.5 / 81.7 / 75.4 / 70.5 M triples/s; the flush has the chip to itself)
-    // (pair: two waves per positive, one positive per workgroup)
-    auto nBwaves = [&](long long cnt) { return r->pair ? 2 * cnt : (cnt + WPB - 1) / WPB * WPB; };
-    const int occ = r->pair ? std::max(4, HPIPE_OCC) : r->fft ? 4 : HPIPE_OCC;
-    int a_cap = hole && b < nb1 ? std::max(1, (occ * 4 * 256 - (int)nBwaves(batches[b].second)) / WPB - 8) : 16384;
-    // (large batches: more scoring waves than the chip holds -- they run in
-    // rounds anyway -- so the apply waves get a fixed share instead of the
-    // residency left over, which would be none: nb = 2 on WN18 had 4 apply
-    // waves for 283k slot records, 42 ms per epoch)
-    if (hole && b < nb1 && (long long)nBwaves(batches[b].second) > occ * 4 * 256)
-      a_cap = std::max(a_cap, 256);
-    a.nA = std::max(1, std::min((a_items + WPB - 1) / WPB, std::min(a_cap, 16384)));
-    const int nBb = r->pair ? std::max(1, std::min(a.count, 2 * 16384))
-                            : std::max(1, std::min((a.count + WPB - 1) / WPB, 16384));
-    r->batch.push_back(a);
-    r->grid.push_back(a.nA + (a.count > 0 ? nBb : 0));
-  }
-  hipStream_t st = as_stream(stream);
-  if (dp) {   // driven launch by launch by the caller (skge_pipe_runner_dp_*), no graph
+  PipeArgs a = {};
+  if (!pipe_alloc(r.get(), st, a, trip, smp))
+    return fail("pipelined runner: device allocation failed");
+  if (r->alloc_bytes != p.total(a.E.nhot))
+    return fail("pipelined runner: plan and allocations disagree (%zu bytes planned for %d hot "
+                "rows, %zu requested)", p.total(a.E.nhot), a.E.nhot, r->alloc_bytes);
+  if (a.E.nhot > 0) pipe_plan_launches(r->plan, a.E.nhot);   // the hubs' apply items
+  a.tw = p.fft ? hole_fft_table(d) : nullptr;
+  if (p.fft && !a.tw) return fail("pipelined runner: HolE FFT twiddle table allocation failed");
+  pipe_fill_args(r.get(), a, ent, rel, margin, nviol_total, af);
+  if (p.dp) {   // driven launch by launch by the caller (skge_pipe_runner_dp_*), no graph
     if (hipStreamSynchronize(st) != hipSuccess) return fail("hipStreamSynchronize failed");
     return r.release();
   }
   if (!r->begin_capture(st)) return nullptr;
-  enqueue_epoch(r.get(), st, nullptr, nullptr);
   int rc = SKGE_OK;
-  if (hipGetLastError() != hipSuccess) {
+  if (!enqueue_epoch(r.get(), st, nullptr, nullptr)) {
+    rc = SKGE_EINVAL;
+  } else if (hipGetLastError() != hipSuccess) {
     set_error("pipelined runner: a launch of the captured epoch failed");
     rc = SKGE_EHIP;
   }
   return r->end_capture(st, rc) ? r.release() : nullptr;
+}
+
+// The plan of the runner pipe_create would build, without a device: no HIP
+// call (include/skge_hip.h).  The same refusals, by the same checks.
+extern "C" int skge_pipe_runner_plan(const skge_table_t* ent, const skge_table_t* rel, int d,
+                                     int64_t T, int nbatches, int flags, int hole,
+                                     skge_pipe_plan_t* out) {
+  SKGE_CHECK_ARG(out, "pipelined runner: NULL plan");
+  if (!pipe_check_tables(ent, rel, d, flags, hole != 0, 0, SKGE_SAMPLER_RANDOM)) return SKGE_EINVAL;
+  SKGE_CHECK_ARG(T >= 1, "pipelined runner: T must be >= 1");
+  SKGE_CHECK_ARG(nbatches >= 1 && nbatches <= T, "pipelined runner: nbatches must be in [1, T]");
+  if (!pipe_check_batch(ent, T, nbatches)) return SKGE_EINVAL;
+  const PipePlan p = pipe_plan(ent, rel, d, T, nbatches, flags, hole != 0, pipe_env(d, hole != 0));
+  out->kernel = p.kernel();
+  out->grouped = p.grouped;
+  out->e8 = p.e8;
+  out->w32 = p.w32;
+  out->fft = p.fft;
+  out->pair = p.pair;
+  out->kq = p.kq;
+  out->rel_reps = p.reps;
+  out->nlaunches = p.nlaunch();
+  out->device_bytes = (uint64_t)p.device_bytes();
+  return SKGE_OK;
 }
 
 extern "C" skge_pipe_runner_t* skge_pipe_runner_create_ex(
@@ -1658,11 +1611,10 @@ extern "C" int skge_pipe_epoch_sample(void* stream, const int* trip, int64_t T, 
                                       const uint64_t* epoch_key, int ntries, int* rec, int* rec_n1,
                                       const skge_sampler_t* smp, const int* err,
                                       uint64_t* key_copy) {
-  SKGE_CHECK_ARG(trip && set && epoch_key && rec && rec_n1, "NULL argument");
-  SKGE_CHECK_ARG(T > 0 && T <= INT32_MAX, "T must be in [1, 2^31)");
-  SKGE_CHECK_ARG(set_capacity >= 2 * T && !(set_capacity & (set_capacity - 1)),
-                 "set capacity must be a power of 2 >= 2T");
-  SKGE_CHECK_ARG(n_ent > 0 && ntries >= 0, "bad n_ent / ntries");
+  // (ntries == 0 is accepted here: the draw launch then draws no negative)
+  if (int rc = check_sample_args(trip, set, epoch_key, rec, rec_n1, T, set_capacity, n_ent,
+                                 ntries, 0))
+    return rc;
   if (int rc = check_sampler(smp, "pipelined epoch sample")) return rc;
   const int kind = smp ? smp->kind : SKGE_SAMPLER_RANDOM;
   Pools pl = {nullptr, nullptr, 0};
@@ -1699,8 +1651,8 @@ static int refuse_invalid(const skge_pipe_runner* r) {
 }
 
 extern "C" int skge_pipe_runner_run(skge_pipe_runner_t* r, void* stream, int nepochs) {
-  SKGE_CHECK_ARG(r && (r->exec || r->dp), "bad runner");
-  SKGE_CHECK_ARG(!r->dp, "data-parallel runner: drive it with skge_pipe_runner_dp_*");
+  SKGE_CHECK_ARG(r && (r->exec || r->plan.dp), "bad runner");
+  SKGE_CHECK_ARG(!r->plan.dp, "data-parallel runner: drive it with skge_pipe_runner_dp_*");
   if (r->invalid) return refuse_invalid(r);
   hipStream_t st = as_stream(stream);
   hot_io(r, st, false);
@@ -1723,7 +1675,7 @@ extern "C" int skge_pipe_runner_profile(skge_pipe_runner_t* r, void* stream, flo
                                         int* stats_out, int n, int trace_launch,
                                         uint64_t* trace_out, int64_t trace_len) {
   SKGE_CHECK_ARG(r && us_out && stats_out, "NULL argument");
-  SKGE_CHECK_ARG(!r->dp, "profile(): not for the data-parallel form");
+  SKGE_CHECK_ARG(!r->plan.dp, "profile(): not for the data-parallel form");
   if (r->invalid) return refuse_invalid(r);
   const int nl = r->nlaunch();
   SKGE_CHECK_ARG(n >= nl, "output arrays need nlaunches entries");
@@ -1754,10 +1706,11 @@ extern "C" int skge_pipe_runner_profile(skge_pipe_runner_t* r, void* stream, flo
   }
   if (rc == SKGE_OK) {
     hot_io(r, st, false);
-    enqueue_epoch(r, st, ev.data(), r->stats, trace_launch, dtrace);
+    const bool ok = enqueue_epoch(r, st, ev.data(), r->stats, trace_launch, dtrace);
     hot_io(r, st, true);
     fused_finalize(r, st);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = SKGE_EHIP;
+    if (!ok) rc = SKGE_EINVAL;
   }
   if (rc == SKGE_OK) {
     for (int i = 0; i < nl; ++i) {
@@ -1792,7 +1745,7 @@ extern "C" int skge_pipe_runner_profile(skge_pipe_runner_t* r, void* stream, flo
 // the slice records -> dp_scatter(b, gathered records), then dp_batch(nb1)
 // (the flush) and dp_end.  Every call is stream-ordered and capturable. ----
 static void rel_fold_launch(const skge_pipe_runner* r, hipStream_t st, const PipeArgs& a) {
-  if (!r->rfold || a.count <= 0) return;
+  if (!r->plan.rfold || a.count <= 0) return;
   const size_t words = (size_t)a.R.rows * a.R.rw;
   hipLaunchKernelGGL(k_rel_fold, dim3((unsigned)std::min<size_t>((words + 255) / 256, 4096)),
                      dim3(256), 0, st, a);
@@ -1807,7 +1760,7 @@ extern "C" int skge_pipe_runner_nbatches(const skge_pipe_runner_t* r) {
 }
 
 extern "C" int skge_pipe_runner_dp_begin(skge_pipe_runner_t* r, void* stream) {
-  SKGE_CHECK_ARG(r && r->dp, "not a data-parallel pipelined runner");
+  SKGE_CHECK_ARG(r && r->plan.dp, "not a data-parallel pipelined runner");
   if (r->invalid) return refuse_invalid(r);
   long long blocks = (r->T + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -1820,7 +1773,7 @@ extern "C" int skge_pipe_runner_dp_begin(skge_pipe_runner_t* r, void* stream) {
 
 extern "C" int skge_pipe_runner_dp_batch(skge_pipe_runner_t* r, void* stream, int b, int lo,
                                          int hi, void* rec_out, int fold) {
-  SKGE_CHECK_ARG(r && r->dp, "not a data-parallel pipelined runner");
+  SKGE_CHECK_ARG(r && r->plan.dp, "not a data-parallel pipelined runner");
   if (r->invalid) return refuse_invalid(r);
   const int nb1 = (int)r->batch.size() - 1;
   SKGE_CHECK_ARG(b >= 0 && b <= nb1, "batch %d out of [0, %d]", b, nb1);
@@ -1830,10 +1783,9 @@ extern "C" int skge_pipe_runner_dp_batch(skge_pipe_runner_t* r, void* stream, in
   a.lo = lo;
   a.hi = hi;
   a.dprec = (uint32_t*)rec_out;
-  const int wpb = (a.E.own[0] ? PIPE_WG_GRP : SKGE_PIPE_WG) / 64;
-  const int nBb = hi > lo ? std::min((hi - lo + wpb - 1) / wpb, 16384) : 0;
   hipStream_t st = as_stream(stream);
-  launch_pipe_batch(r, dim3((unsigned)(a.nA + nBb)), st, a);
+  if (!launch_pipe_batch(r, dim3((unsigned)(a.nA + r->plan.score_groups(hi - lo))), st, a))
+    return SKGE_EINVAL;
   if (fold) rel_fold_launch(r, st, a);
   SKGE_CHECK_LAUNCH("dp batch");
   return SKGE_OK;
@@ -1841,7 +1793,7 @@ extern "C" int skge_pipe_runner_dp_batch(skge_pipe_runner_t* r, void* stream, in
 
 extern "C" int skge_pipe_runner_dp_scatter(skge_pipe_runner_t* r, void* stream, int b,
                                            const void* recs, int lo, int hi) {
-  SKGE_CHECK_ARG(r && r->dp, "not a data-parallel pipelined runner");
+  SKGE_CHECK_ARG(r && r->plan.dp, "not a data-parallel pipelined runner");
   if (r->invalid) return refuse_invalid(r);
   const int nb1 = (int)r->batch.size() - 1;
   SKGE_CHECK_ARG(b >= 0 && b < nb1, "batch %d out of [0, %d)", b, nb1);
@@ -1855,20 +1807,11 @@ extern "C" int skge_pipe_runner_dp_scatter(skge_pipe_runner_t* r, void* stream, 
   if (nrem > 0) {
     const dim3 gr((unsigned)std::max(1, std::min((nrem + 3) / 4, 16384))), bl(256);
     const uint32_t* rc = (const uint32_t*)recs;
-#define SKGE_DS(K)                                                                              \
-  do {                                                                                          \
-    if (r->e8) {                                                                                \
-      if (r->w32) hipLaunchKernelGGL((k_pipe_dp_scatter<K, true, true>), gr, bl, 0, st, a, rc);  \
-      else hipLaunchKernelGGL((k_pipe_dp_scatter<K, false, true>), gr, bl, 0, st, a, rc);        \
-    } else {                                                                                    \
-      if (r->w32) hipLaunchKernelGGL((k_pipe_dp_scatter<K, true, false>), gr, bl, 0, st, a, rc); \
-      else hipLaunchKernelGGL((k_pipe_dp_scatter<K, false, false>), gr, bl, 0, st, a, rc);       \
-    }                                                                                           \
-  } while (0)
-    if (r->kq <= 1) SKGE_DS(1);
-    else if (r->kq <= 2) SKGE_DS(2);
-    else SKGE_DS(4);
-#undef SKGE_DS
+    auto go = [&](auto K, auto W32, auto E8) {
+      hipLaunchKernelGGL((k_pipe_dp_scatter<K(), W32(), E8()>), gr, bl, 0, st, a, rc);
+      return true;
+    };
+    with_kq_flags(go, r->plan.kq, r->plan.w32, r->plan.e8);
   }
   rel_fold_launch(r, st, a);
   SKGE_CHECK_LAUNCH("dp scatter");
@@ -1876,7 +1819,7 @@ extern "C" int skge_pipe_runner_dp_scatter(skge_pipe_runner_t* r, void* stream, 
 }
 
 extern "C" int skge_pipe_runner_dp_end(skge_pipe_runner_t* r, void* stream) {
-  SKGE_CHECK_ARG(r && r->dp, "not a data-parallel pipelined runner");
+  SKGE_CHECK_ARG(r && r->plan.dp, "not a data-parallel pipelined runner");
   hipLaunchKernelGGL(k_pipe_advance, dim3(1), dim3(1), 0, as_stream(stream), r->epoch_key);
   SKGE_CHECK_LAUNCH("dp end");
   return SKGE_OK;
@@ -1896,7 +1839,7 @@ extern "C" int skge_pipe_runner_nlaunches(const skge_pipe_runner_t* r) {
 }
 
 extern "C" int skge_pipe_runner_kernel(const skge_pipe_runner_t* r) {
-  return r ? (r->hole ? 2 : (r->fused ? 1 : 0)) : -1;
+  return r ? r->plan.kernel() : -1;
 }
 
 extern "C" int skge_pipe_runner_hot_rows(const skge_pipe_runner_t* r) {

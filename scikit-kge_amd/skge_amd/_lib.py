@@ -60,6 +60,13 @@ class SkgeNegatives(ctypes.Structure):
 
 N_P = ctypes.POINTER(SkgeNegatives)
 
+
+class SkgePipePlan(ctypes.Structure):
+    """Mirror of skge_pipe_plan_t (skge_pipe_runner_plan: no GPU needed)."""
+    _fields_ = [(n, c_i) for n in ("kernel", "grouped", "e8", "w32", "fft", "pair", "kq",
+                                   "rel_reps", "nlaunches")] + [("device_bytes", c_u64)]
+
+
 # name -> (restype, argtypes); the exact set declared in include/skge_hip.h
 SIGNATURES = {
     "skge_abi_version": (c_i, []),
@@ -164,6 +171,8 @@ SIGNATURES = {
     "skge_pipe_runner_nlaunches": (c_i, [c_p]),
     "skge_pipe_runner_hot_rows": (c_i, [c_p]),
     "skge_pipe_runner_kernel": (c_i, [c_p]),
+    "skge_pipe_runner_plan": (c_i, [T_P, T_P, c_i, c_i64, c_i, c_i, c_i,
+                                    ctypes.POINTER(SkgePipePlan)]),
     "skge_pipe_runner_destroy": (None, [c_p]),
     "skge_shard_route_workspace_bytes": (c_sz, [c_i, c_i]),
     "skge_shard_route": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_sz]),

@@ -173,6 +173,14 @@ def _tail8(mu):
     return mu + 8.0 * mu ** 0.5 + 20.0
 
 
+def int8_entity_sums(kg, n_ent, batch, sampler=L.SKGE_SAMPLER_RANDOM, n_rel=None):
+    """The pipelined runners' entity sums in 8-bit fields (SKGE_ACC_I8X4: half
+    the atomic bytes; the apply checks every count): while every entity's
+    per-batch count is <= 127 under _tail8's bound, unless SKGE_PIPE_E8=0."""
+    return (packed_count_bound(kg, n_ent, batch, _tail8, sampler=sampler, n_rel=n_rel) <= 127 and
+            _os.environ.get("SKGE_PIPE_E8", "1") != "0")
+
+
 def _tail(mu):
     """Poisson/binomial upper tail used for the random parts of the count
     bounds: mu + 12 sqrt(mu) + 40 (never reached in practice; the applies
@@ -522,14 +530,10 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         from .transe import TransE
         if not isinstance(model, TransE):
             raise NotImplementedError("device_loop supports TransE (the north-star path) only")
-        dev = model.device
         self._setup(model, kg, nbatches, seed, ntries, stream, sampler)
         self.nviol_total = self._total(nviol_total, torch.int32)
         self._hold_state(updaters)
         bs = kg.T // nbatches
-        # the per-batch count bound of this runner's sampler kind
-        bound = lambda tail=None: packed_count_bound(kg, model.E.rows, bs, tail,
-                                                     sampler=self.sampler, n_rel=model.sz[2])
         self.hot_rows = 0   # pipelined TransE: entity rows with replicated sums (skewed KGs)
         # d % 4 != 0 (e.g. the reference's d = 50): the packed / pipelined
         # runners work on quads, so they run on zero-padded copies of the
@@ -545,7 +549,9 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         # sums while every row's per-batch count stays <= 32767 (the applies
         # flag a larger count, checked by synchronize())
         can_pack = bool(model.l1) and (model.d % 4 == 0 or self._pad) and not force_f32
-        self.count_bound = bound() if can_pack else 0
+        # (the per-batch count bound of this runner's sampler kind)
+        self.count_bound = packed_count_bound(kg, model.E.rows, bs, sampler=self.sampler,
+                                              n_rel=model.sz[2]) if can_pack else 0
         auto_packed = packed is None
         if packed is None:
             packed = can_pack and self.count_bound <= PACKED_MAX
@@ -555,58 +561,33 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         # the two-launch runner's packed relation sums: hot relations spread
         # over accumulator copies (0: not even 32 copies suffice)
         rel_reps = relation_replicas(kg, model.R.rows, bs) if packed else 1
-        E, R = model.params["E"], model.params["R"]
         can_pipe = packed and replicas <= 1 and pipelined is not False
         if pipelined and not can_pipe:
             raise ValueError("pipelined runner needs TransE-L1, d % 4 == 0, packed sums "
                              "and replicas == 1")
-        if can_pipe and pipelined is None:
-            # the pipelined runner's scratch (auto mode: only if it fits): the
-            # epoch's records and, per entity row, k_pipe_fused (rows of <= 64
-            # floats, batches of <= 16k slot records; skge_pipeline.hip) three
-            # accumulator copies, a second copy of E and its AdaGrad state and a
-            # meta word -- k_pipe_batch two accumulator copies (the table's and
-            # one more, packed 16- or 8-bit fields) and five words (done word,
-            # pending marks and owner marks of both copies)
-            torch.cuda.synchronize(dev)
-            torch.cuda.empty_cache()
-            wd = self.d_pad if self._pad else model.d
-            if wd <= 64 and 4 * bs <= 4 * 4096:
-                acc = E.rows * (E.width * 2 + 4) + 4 * 4 * bs
-                extra = 3 * acc + kg.T * 20 + (64 << 20) + E.rows * (16 + 8 * E.width)
-            else:
-                e8_est = (bound(_tail8) <= 127 and
-                          _os.environ.get("SKGE_PIPE_E8", "1") != "0")
-                acc = E.rows * ((wd // 4) * (4 if e8_est else 8) + 4) + 2 * 4 * 4 * bs
-                extra = 2 * acc + E.rows * 5 * 4 + kg.T * 20 + (256 << 20)
-            can_pipe = extra < torch.cuda.mem_get_info(dev)[0] * 0.9
         lib = L.lib()
         if can_pipe:
             # relation sums in 16-bit fields while a relation's per-batch count
             # fits them (faster: half the atomics), else int32x2; entity sums in
-            # 8-bit fields while every entity's per-batch count is <= 127 (half
-            # the atomic bytes again; the apply checks every count)
-            e8 = (bound(_tail8) <= 127 and
-                  _os.environ.get("SKGE_PIPE_E8", "1") != "0")
+            # 8-bit fields while every entity's per-batch count is <= 127
+            e8 = int8_entity_sums(kg, model.E.rows, bs, self.sampler, model.sz[2])
             self._tables(model, updaters, packed, 1, rel_w32=rel_reps != 1, ent_i8=e8,
                          pad=self._pad)
             self.ent_i8 = e8
+            wd = self.d_pad if self._pad else model.d
             try:
-                args = (self.te, self.tr, self.d_pad if self._pad else model.d) + \
-                    self._epoch_args() + (float(model.margin), self.ntries, L.ptr(self.nviol_total))
-                if self._smp is None:
-                    self._create("skge_pipe_runner", *args)
-                else:   # the typed / LCWA draw launch (flags 0)
-                    self._create("skge_pipe_runner", *(args + (0, self._smp)),
-                                 create="skge_pipe_runner_create_smp")
-                self.hot_rows = lib.skge_pipe_runner_hot_rows(self.handle)
-                self.kernel = ("k_pipe_batch",
-                               "k_pipe_fused")[lib.skge_pipe_runner_kernel(self.handle)]
-                return
+                if pipelined or self._pipe_fits(wd):   # (auto mode: only if it fits)
+                    self._create("skge_pipe_runner", self.te, self.tr, wd, *self._epoch_args(),
+                                 float(model.margin), self.ntries, L.ptr(self.nviol_total), 0,
+                                 self._smp, create="skge_pipe_runner_create_smp")
+                    self.hot_rows = lib.skge_pipe_runner_hot_rows(self.handle)
+                    self.kernel = ("k_pipe_batch",
+                                   "k_pipe_fused")[lib.skge_pipe_runner_kernel(self.handle)]
+                    return
             except L.SkgeError as e:
                 if not (pipelined is None and "allocation" in str(e)):
                     raise
-            # auto mode: out of device memory -> two-launch runner
+            # auto mode: it does not fit, or ran out of device memory -> two-launch runner
             self.accE = self.accR = self.te = self.tr = None
             torch.cuda.empty_cache()
         self.pipelined = False
@@ -623,10 +604,22 @@ class EpochRunner(_PaddedTables, _PipeRunner):
         self._tables(model, updaters, packed, max(int(replicas), rel_reps) if packed else replicas)
         args = (int(bool(model.l1)), self.te, self.tr, model.d) + self._epoch_args() + \
             (float(model.margin), self.ntries, None, L.ptr(self.nviol_total))
-        if self._smp is None:
-            self._create("skge_runner", *args)
-        else:
-            self._create("skge_runner", *(args + (self._smp,)), create="skge_runner_create_smp")
+        self._create("skge_runner", *(args + (self._smp,)), create="skge_runner_create_smp")
+
+    def _pipe_fits(self, d):
+        """Auto mode: the pipelined runner only if what it allocates beside the
+        tables just built (skge_pipe_runner_plan's device_bytes -- the C side's
+        own rule and sizes, hot-row buffers at their upper bound) fits in the
+        free device memory with room to spare: 64 MB for k_pipe_fused, 256 MB
+        for k_pipe_batch, and a tenth of what is free."""
+        dev = self.model.device
+        torch.cuda.synchronize(dev)
+        torch.cuda.empty_cache()
+        plan = L.SkgePipePlan()
+        L.check(L.lib().skge_pipe_runner_plan(self.te, self.tr, int(d), self.kg.T,
+                                              int(self.nbatches), 0, 0, plan), "pipelined plan")
+        slack = (64 << 20) if plan.kernel == 1 else (256 << 20)
+        return plan.device_bytes + slack < torch.cuda.mem_get_info(dev)[0] * 0.9
 
     def synchronize(self):
         if self.pipelined:
@@ -668,11 +661,8 @@ class HolePipeRunner(_PipeRunner):
                                       rout=reg["R"][1], fixed_div=reg["R"][2])
         args = (model._af_code(), self.te, self.tr, model.d) + self._epoch_args() + \
             (float(model.margin), self.ntries, L.ptr(self.nviol_total))
-        if self._smp is None:
-            self._create("skge_pipe_runner", *args, create="skge_hole_pipe_runner_create")
-        else:
-            self._create("skge_pipe_runner", *(args + (self._smp,)),
-                         create="skge_hole_pipe_runner_create_smp")
+        self._create("skge_pipe_runner", *(args + (self._smp,)),
+                     create="skge_hole_pipe_runner_create_smp")
         # hub rows (pair form, skewed KGs)
         self.hot_rows = L.lib().skge_pipe_runner_hot_rows(self.handle)
 

@@ -33,15 +33,13 @@ drives the same protocol over gloo with a NumPy compute stand-in
 (tests/dp_numpy.py).  Under the "nccl" backend (RCCL) the whole epoch --
 kernels and all-gathers -- is captured in one hipGraph per rank.
 """
-import os
-
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
 from .device import (_PaddedTables, _PipeRunner, packed_count_bound, relation_replicas,
-                     padded_width, _tail8, PACKED_MAX)
+                     padded_width, int8_entity_sums, PACKED_MAX)
 
 SKGE_PIPE_DP = 1   # skge_pipe_runner_create_ex flag (include/skge_hip.h)
 
@@ -214,8 +212,7 @@ class DataParallelRunner(_PaddedTables, _PipeRunner):
         if rel_reps == 0:
             raise ValueError("data-parallel runner: a relation's per-batch count exceeds what 32 "
                              "packed accumulator copies hold; use more batches")
-        e8 = (packed_count_bound(kg, model.E.rows, bs, _tail8) <= 127 and
-              os.environ.get("SKGE_PIPE_E8", "1") != "0")
+        e8 = int8_entity_sums(kg, model.E.rows, bs)
         # the one-GPU pipelined runner's tables (same encodings: the same sums)
         self._tables(model, updaters, True, 1, rel_w32=rel_reps != 1, ent_i8=e8, pad=self._pad)
         self.rec_bytes = int(L.lib().skge_pipe_dp_record_bytes(self.d))
