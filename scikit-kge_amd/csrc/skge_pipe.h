@@ -158,15 +158,25 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const float* T, int r
                                            0x00020000);
 }
 
-template <int KQ>
+template <int KQ, int AUX = AUX_SC1>
 __device__ __forceinline__ void load_row4_sc1(const float* T, int row, int d, float4 (&v)[KQ]) {
   const __amdgpu_buffer_rsrc_t rs = row_rsrc(T, row, d);
   const int l = lane_id();
 #pragma unroll
   for (int m = 0; m < KQ; ++m) {
-    const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, (64 * m + l) * 16, 0, AUX_SC1);
+    const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, (64 * m + l) * 16, 0, AUX);
     v[m] = *reinterpret_cast<const float4*>(&x);
   }
+}
+
+// The same with plain loads: a row as of the launch start.  Unlike load_row4
+// (skge_device.h), whose select hipcc turns into a branch around each load,
+// these loads are unconditional: a wait placed after them can count them
+// (s_waitcnt vmcnt(N) leaves the N youngest loads in flight only when every
+// path to the wait has issued them).
+template <int KQ>
+__device__ __forceinline__ void load_row4_buf(const float* T, int row, int d, float4 (&v)[KQ]) {
+  load_row4_sc1<KQ, 0>(T, row, d, v);
 }
 
 template <int KQ>
@@ -477,12 +487,19 @@ __device__ __forceinline__ void ensure_applied(const PipeTab& t, int pp, int row
 // before the count is read (kept in load_upd_row's shape: hipcc would sink
 // loads used only under `if (c)` below the count's wait).  Lanes past the row
 // end with zeros whether or not the row was updated (they enter the scores).
+//
+// In two halves, so that a caller can put other loads between them (the
+// scoring wave of k_pipe_batch: its entity rows are in flight while the
+// update runs).  rel_row_issue: every load, the count word (cw) included, and
+// no wait.  rel_row_finish: the count, then the update.
 template <int KQ, bool W32>
-__device__ __forceinline__ void rel_row(const RelTab& t, int row, int d, int rd, int ra,
-                                        float4 (&p)[KQ], float4 (&a)[KQ], int& c) {
+__device__ __forceinline__ void rel_row_issue(const RelTab& t, int row, int d, int rd, int ra,
+                                              float4 (&p)[KQ], float4 (&a)[KQ],
+                                              unsigned long long (&sv)[KQ],
+                                              unsigned long long (&sw)[KQ],
+                                              unsigned long long& cw) {
   const int l = lane_id(), nq = d >> 2;
   const unsigned long long* acc = t.acc[ra] + (size_t)row * t.rw;
-  unsigned long long sv[KQ], sw[KQ];
   if (W32) {
     const float4* prow = reinterpret_cast<const float4*>(t.P[rd] + (size_t)row * d);
     const float4* arow = reinterpret_cast<const float4*>(t.A[rd] + (size_t)row * d);
@@ -499,7 +516,17 @@ __device__ __forceinline__ void rel_row(const RelTab& t, int row, int d, int rd,
     load_upd_row<KQ>(t.P[rd] + (size_t)row * d, t.A[rd] ? t.A[rd] + (size_t)row * d : nullptr,
                      acc, d, p, a, sv);
   }
-  c = __builtin_amdgcn_readfirstlane((int)acc[W32 ? 2 * nq : nq]);
+  cw = acc[W32 ? 2 * nq : nq];
+}
+
+template <int KQ, bool W32>
+__device__ __forceinline__ void rel_row_finish(const RelTab& t, int d,
+                                               const unsigned long long (&sv)[KQ],
+                                               const unsigned long long (&sw)[KQ],
+                                               unsigned long long cw, float4 (&p)[KQ],
+                                               float4 (&a)[KQ], int& c) {
+  const int l = lane_id(), nq = d >> 2;
+  c = __builtin_amdgcn_readfirstlane((int)cw);
   if (c) {
     row_update<KQ, W32>(t.u, c, d, sv, sw, p, a);   // (zeroes the lanes past the row)
   }
@@ -508,6 +535,15 @@ __device__ __forceinline__ void rel_row(const RelTab& t, int row, int d, int rd,
     for (int m = 0; m < KQ; ++m)
       if (64 * m + l >= nq) p[m] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
+}
+
+// the two halves back to back
+template <int KQ, bool W32>
+__device__ __forceinline__ void rel_row(const RelTab& t, int row, int d, int rd, int ra,
+                                        float4 (&p)[KQ], float4 (&a)[KQ], int& c) {
+  unsigned long long sv[KQ], sw[KQ], cw;
+  rel_row_issue<KQ, W32>(t, row, d, rd, ra, p, a, sv, sw, cw);
+  rel_row_finish<KQ, W32>(t, d, sv, sw, cw, p, a, c);
 }
 
 __device__ __forceinline__ unsigned long long now_10ns() { return __builtin_amdgcn_s_memrealtime(); }

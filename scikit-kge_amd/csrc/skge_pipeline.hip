@@ -72,6 +72,21 @@ namespace skge {
 // slice bounds and the record branch in the shared instance cost 10.45 ->
 // 11.15 us per launch, same box: VERDICT r05 item 4's A/B)
 //
+// The scoring wave's loads, after its record: ONE burst in the order relation
+// row (sums, P, state, count word), four entity rows, pending marks and done
+// words (hot indices).  The relation operands are L2-hot and vector loads
+// return in order, so R_b[p]'s update (rel_row_finish, ~250 instructions with
+// four divides) runs behind a partial wait -- s_waitcnt vmcnt(6) in the
+// flagship's instance -- while the entity rows are still in flight; the first
+// full wait is where pend / unpub are formed.  Before, the relation loads
+// came last and the update sat behind the slowest entity row (flagship
+// 0.899 -> 0.888 ms per epoch, same box; profiles/score_chain/README.md).
+// That wait can only count loads every path has issued, so the burst has no
+// branch around a load: entity rows through per-row buffer descriptors
+// (load_row4_buf; lanes past the row read zeros), marks by all 64 lanes.
+// Measured there and not kept: the kernarg pointers of the burst pinned in
+// registers before the loop (0.891), the record through scalar loads (0.898).
+//
 // Waves per SIMD of the WN18 one-GPU instances (KQ = 1, no owner marks, no hot
 // rows, not data-parallel), pinned so that an edit which adds or frees a
 // register cannot silently move them; 0 leaves it to the register count.
@@ -211,29 +226,33 @@ void k_pipe_batch(PipeArgs a) {
     const int neg0 = __builtin_amdgcn_readfirstlane(r4.w);
     const int neg1 = __builtin_amdgcn_readfirstlane(r1);
     const int n0r = neg0 >= 0 ? neg0 : s, n1r = neg1 >= 0 ? neg1 : o;
-    // entity rows as of the launch start (plain loads), their pending marks,
-    // and the relation row this batch scores with
-    float4 es[KQ], eo[KQ], rp[KQ], fs[KQ], fo[KQ];
-    load_row4<KQ>(a.E.P, s, d, es);
-    load_row4<KQ>(a.E.P, o, d, eo);
-    load_row4<KQ>(a.E.P, n0r, d, fs);
-    load_row4<KQ>(a.E.P, n1r, d, fo);
+    // One burst of loads, the relation row's first (the kernel's header
+    // comment): R_b[p]'s update runs while the entity rows are in flight.
+    // No load of the burst has a branch around it.
+    float4 es[KQ], eo[KQ], rp[KQ], fs[KQ], fo[KQ], ra[KQ];
+    unsigned long long rsv[KQ], rsw[KQ], rcnt;
+    rel_row_issue<KQ, W32>(a.R, p, d, rd, ra_prev, rp, ra, rsv, rsw, rcnt);
+    __builtin_amdgcn_sched_barrier(0);
+    // entity rows as of the launch start (plain loads, zeros past the row)
+    load_row4_buf<KQ>(a.E.P, s, d, es);
+    load_row4_buf<KQ>(a.E.P, o, d, eo);
+    load_row4_buf<KQ>(a.E.P, n0r, d, fs);
+    load_row4_buf<KQ>(a.E.P, n1r, d, fo);
     // pending marks and the rows' done words in the same round trip: a pending
     // row whose update is already published needs only the re-read below (at
     // nb = 2 every row is pending; one done check per row in sequence had cost
-    // ~1.9 us per wave)
-    int mark = 0, dn = 0, hx = -1;
-    if (l < 4) {
-      const int rr = sel4(l, s, o, n0r, n1r);
-      mark = a.E.pend[pp][rr];
-      dn = __hip_atomic_load(a.E.done + rr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (HOT) hx = a.E.hot[rr];
-    }
+    // ~1.9 us per wave).  Lane l reads the words of row l & 3; lanes 0-3 count.
+    const int rr = sel4(l & 3, s, o, n0r, n1r);
+    const int mark = a.E.pend[pp][rr];
+    const int dn = __hip_atomic_load(a.E.done + rr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int hx = -1;
+    if (HOT) hx = a.E.hot[rr];
+    __builtin_amdgcn_sched_barrier(0);
     {
-      float4 ra[KQ];
       int c;
-      rel_row<KQ, W32>(a.R, p, d, rd, ra_prev, rp, ra, c);
+      rel_row_finish<KQ, W32>(a.R, d, rsv, rsw, rcnt, rp, ra, c);
     }
+    __builtin_amdgcn_sched_barrier(0);
     const uint64_t pend = __ballot(mark == gp) & 0xfull;
     const uint64_t unpub = pend & ~__ballot(dn == gp);   // pending and not yet published
     if (a.trace) tt[1] = now_10ns();
