@@ -37,7 +37,8 @@ def host_triples(xs):
         if len(xs) and len(xs[0]) == 2 and not np.isscalar(xs[0][0]):
             xs = [x for x, _ in xs]
         a = np.array(xs, dtype=np.int64)
-    return np.asarray(a).astype(np.int64).reshape(-1, 3)
+    # row-major whatever the caller's strides (a[:, [1, 0, 2]] is column-major)
+    return np.ascontiguousarray(np.asarray(a).reshape(-1, 3), dtype=np.int64)
 
 
 def score_triples(model, triples):

@@ -31,7 +31,9 @@ def triples_array(xs):
         else:
             a = np.array(xs, dtype=np.int64)
     a = np.asarray(a).reshape(-1, 3)
-    return a.astype(np.int32)
+    # row-major whatever the caller's strides (a[:, [1, 0, 2]] is column-major):
+    # the library reads 3 consecutive ints per triple
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def labels_array(xys):

@@ -56,7 +56,41 @@ def _int_query_vectors(model, E, R, S, Oo, P, direction):
         # tail: E_s W_p; head: W_p E_o
         return np.einsum("nj,njk->nk", a, R[P]) if direction == "tail" else \
             np.einsum("nkj,nj->nk", R[P], a)
+    if model in ("distmult", "complex"):
+        # tail: E_s * R_p; head: conj(R_p) * E_o (diag_ref.q_tail / q_head)
+        return int_diag_mul(model, a, R[P], False) if direction == "tail" else \
+            int_diag_mul(model, R[P], a, True)
     raise ValueError("unknown model %r" % (model,))
+
+
+def int_diag_mul(model, x, y, conj):
+    """int64 x * y (conj: conj(x) * y) over the last axis: elementwise for
+    DistMult, the complex product on interleaved (re, im) for ComplEx -- the
+    query vectors of tests/diag_ref.py (tail s * r, head conj(r) * o, relation
+    conj(s) * o); the score of a candidate row is its plain dot product with
+    one of them.
+
+    With entries in [-3, 3] an element of the product is at most 9 + 9 = 18
+    in magnitude and a score at most 3 * 18 d = 54 d, 55,296 at d = 1024: every
+    fp32 product, fma and partial sum of any evaluation order is an integer far
+    below 2^24, so a device result must EQUAL the int64 one."""
+    d = x.shape[-1]
+    lim = int(max(np.abs(x).max(initial=0), np.abs(y).max(initial=0)))
+    assert lim <= 3 and 2 * lim ** 3 * d < 2 ** 24
+    if model == "distmult":
+        return x * y
+    if d % 2:
+        raise ValueError("ComplEx needs an even width, not %d" % d)
+    a, b = x[..., 0::2], x[..., 1::2]
+    f, g = y[..., 0::2], y[..., 1::2]
+    out = np.empty(np.broadcast(x, y).shape, dtype=np.int64)
+    if conj:
+        out[..., 0::2] = a * f + b * g
+        out[..., 1::2] = a * g - b * f
+    else:
+        out[..., 0::2] = a * f - b * g
+        out[..., 1::2] = a * g + b * f
+    return out
 
 
 def _int_scores_batch(model, E, R, S, Oo, P, direction):

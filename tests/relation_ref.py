@@ -66,6 +66,9 @@ def int_relation_scores(model, E, R, pairs, l2=False):
         return q @ Ri.T
     if model == "rescal":
         return np.stack([((es @ Ri[j]) * eo).sum(axis=1) for j in range(M)], axis=1)
+    if model in ("distmult", "complex"):
+        # R_j . (conj(E_s) * E_o)  (diag_ref.q_rel; eval_ref.int_diag_mul's bound)
+        return X.int_diag_mul(model, es, eo, True) @ Ri.T
     raise ValueError("unknown model %r" % (model,))
 
 
