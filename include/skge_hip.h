@@ -44,8 +44,8 @@ enum {
 
 /* models (skge/transe.py, skge/hole.py, skge/rescal.py; DistMult and ComplEx:
  * HolE's tables and conventions with the trilinear score, csrc/skge_diag.h).
- * Code 4 is unassigned: every entry point accepts 0..3, 5 and 6 -- not
- * "<= 6" -- and answers 4 with SKGE_EINVAL like any unknown code.
+ * Code 4 is unassigned: every entry point accepts 0..3, 5, 6 and 7 -- not
+ * "<= 7" -- and answers 4 with SKGE_EINVAL like any unknown code.
  * skge_subgraph_rank takes 0..3 only.  SKGE_COMPLEX needs an even d: a row
  * holds d/2 complex components interleaved, (re, im) = (x[2j], x[2j+1]). */
 enum {
@@ -54,14 +54,33 @@ enum {
   SKGE_HOLE = 2,
   SKGE_RESCAL = 3,
   SKGE_DISTMULT = 5,
-  SKGE_COMPLEX = 6
+  SKGE_COMPLEX = 6,
+  /* RotatE (csrc/skge_rot.h): phi = -sum_j |E_s[j] * R_p[j] - E_o[j]| over the
+   * d/2 complex components of ComplEx's row layout (d even), TransE's raw
+   * pairwise margin loss, every component of R kept on the unit circle by
+   * SKGE_POST_UNITMOD.  Served: skge_pair_grad, skge_score, skge_rank_known,
+   * skge_topk, skge_rank_pools, skge_topk_pools and the pair loop runner.
+   * Refused with an error that names RotatE: the logistic entry points,
+   * skge_relrank / skge_reltopk, skge_subgraph_rank, skge_rank and every
+   * pipelined, two-launch, data-parallel and sharded runner. */
+  SKGE_ROTATE = 7
 };
 /* activation functions (skge/actfun.py:13-57) */
 enum { SKGE_AF_LINEAR = 0, SKGE_AF_SIGMOID = 1, SKGE_AF_TANH = 2, SKGE_AF_RELU = 3 };
 /* updaters (skge/param.py:124-155) */
 enum { SKGE_SGD = 0, SKGE_ADAGRAD = 1 };
 /* post-update projections (skge/param.py:161-174) */
-enum { SKGE_POST_NONE = 0, SKGE_POST_NORMALIZE = 1, SKGE_POST_NORMLESS1 = 2 };
+enum {
+  SKGE_POST_NONE = 0,
+  SKGE_POST_NORMALIZE = 1,
+  SKGE_POST_NORMLESS1 = 2,
+  /* every complex component (x[2j], x[2j+1]) of an updated row divided by its
+   * modulus, a zero component set to (1, 0); width even and <= 1024, fp32 or
+   * fixed-point sums.  Served by skge_accum_apply / skge_accum_apply2 /
+   * skge_update_rows (and so the per-batch step and the pair loop); every
+   * other consumer of a table refuses it by name */
+  SKGE_POST_UNITMOD = 3
+};
 /* accumulator encodings */
 enum {
   SKGE_ACC_F32 = 0,    /* acc_sum: fp32 [rows][width] */

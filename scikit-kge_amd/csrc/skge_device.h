@@ -14,10 +14,12 @@
 
 namespace skge {
 
-enum Model : int { TRANSE_L1 = 0, TRANSE_L2 = 1, HOLE = 2, RESCAL = 3, DISTMULT = 5, COMPLEX = 6 };
+enum Model : int {
+  TRANSE_L1 = 0, TRANSE_L2 = 1, HOLE = 2, RESCAL = 3, DISTMULT = 5, COMPLEX = 6, ROTATE = 7
+};
 enum Act : int { AF_LINEAR = 0, AF_SIGMOID = 1, AF_TANH = 2, AF_RELU = 3 };
 enum Opt : int { OPT_SGD = 0, OPT_ADAGRAD = 1 };
-enum Post : int { POST_NONE = 0, POST_NORMALIZE = 1, POST_NORMLESS1 = 2 };
+enum Post : int { POST_NONE = 0, POST_NORMALIZE = 1, POST_NORMLESS1 = 2, POST_UNITMOD = 3 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -90,6 +92,26 @@ __device__ __forceinline__ float adagrad_step_fast(float lr, float g, float a) {
 __device__ __forceinline__ float proj_scale_fast(int post, float ss) {
   return __builtin_amdgcn_rcpf(post == POST_NORMALIZE ? __builtin_amdgcn_sqrtf(ss)
                                                       : (ss < 1.0f ? 1.0f : ss));
+}
+
+// POST_UNITMOD on a row in the lane-strided layout (lane l holds elements
+// l + 64k): every complex component (x[2j], x[2j + 1]) divided by its modulus
+// sqrtf(re^2 + im^2), a zero component set to (1, 0).  The component's other
+// half is in lane l ^ 1 of the same register (one DPP quad permutation); both
+// lanes form the same modulus bits (re is squared into the fma, im is the
+// single multiply), so no wave reduction is needed.  The width is even (the
+// table checks), so no component straddles the row's end; the elements past it
+// come out as (1, 0) and are never stored.  Call with the whole wave active.
+template <int KM>
+__device__ __forceinline__ void unitmod_row(float (&p)[KM]) {
+  const bool im = lane_id() & 1;
+#pragma unroll
+  for (int k = 0; k < KM; ++k) {
+    const float o = dpp_f<0xb1>(p[k]);
+    const float re = im ? o : p[k], iv = im ? p[k] : o;
+    const float m = sqrtf(fmaf(re, re, iv * iv));
+    p[k] = m > 0.0f ? p[k] / m : (im ? 0.0f : 1.0f);
+  }
 }
 
 // logistic loss of one labelled triple (skge/hole.py:22-42, rescal.py:37-76):

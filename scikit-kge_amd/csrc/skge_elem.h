@@ -50,6 +50,9 @@ __device__ __forceinline__ float cconv_direct_k(const float* a, const float* b, 
 //   RESCAL   (ea W)_k = sum_j ea[j] W[j][k]    (W ea)_k = sum_j W[k][j] ea[j]
 //   DistMult ea[k] rp[k]                       ea[k] rp[k]
 //   ComplEx  (ea * rp)_k                       (conj(rp) * ea)_k
+//   RotatE   ComplEx's two: |r| = 1 gives |s * r - o| = |s - conj(r) * o|, so
+//            every candidate row is compared with the same vector (the score
+//            tile's RT_CMOD form, skge_rank_tile.h)
 // every sum one fma chain in ascending j.  ComplEx (skge_diag.h): * is the
 // complex product over the interleaved components, (re, im) = (x[2j], x[2j+1]),
 // d even; the tail form is d phi / d o, the head form d phi / d s.  With E_o
@@ -60,7 +63,7 @@ __device__ __forceinline__ float query_elem(int model, bool tail, const float* e
   if (model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2) return tail ? ea[k] + rp[k] : ea[k] - rp[k];
   if (model == SKGE_HOLE) return tail ? cconv_direct_k(rp, ea, d, k) : ccorr_direct_k(rp, ea, d, k);
   if (model == SKGE_DISTMULT) return ea[k] * rp[k];
-  if (model == SKGE_COMPLEX) {
+  if (model == SKGE_COMPLEX || model == SKGE_ROTATE) {
     const int kp = k ^ 1;   // the component's other half
     if (k & 1)   // im: Re a Im r + Im a Re r   |   Re r Im a - Im r Re a
       return tail ? fmaf(ea[kp], rp[k], ea[k] * rp[kp]) : fmaf(rp[kp], ea[k], -(rp[k] * ea[kp]));

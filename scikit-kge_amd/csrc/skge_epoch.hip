@@ -454,6 +454,9 @@ static int fill_sample_args(SampleArgs& a, int l1, const skge_table_t* ent, cons
   if ((rc = check_table(ent, "ent", true))) return rc;
   if ((rc = check_table(rel, "rel", true))) return rc;
   if ((rc = check_single(ent, "ent"))) return rc;
+  // TransE's tables only: a unit-modulus relation table is RotatE's
+  if (refuses_unitmod(ent, "two-launch runner") || refuses_unitmod(rel, "two-launch runner"))
+    return SKGE_EINVAL;
   SKGE_CHECK_ARG(ent->width == d && rel->width == d, "table widths must equal d");
   SKGE_CHECK_ARG(km_for(d) != 0, "d=%d unsupported", d);
   SKGE_CHECK_ARG(trip && set_slots && epoch_key, "NULL argument");

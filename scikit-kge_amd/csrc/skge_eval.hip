@@ -71,7 +71,7 @@ __global__ __launch_bounds__(128) void k_rank_query(RankArgs a) {
     float* qt = a.Q + (size_t)(2 * i) * d;
     float* qh = a.Q + (size_t)(2 * i + 1) * d;
     const float* W = a.R + (size_t)p * d * d;
-    const bool l1 = a.model == SKGE_TRANSE_L1 || a.model == SKGE_TRANSE_L2;
+    const int form = rank_form(a.model);
     for (int k = l; k < d; k += 64) {
       const float vt = query_elem(a.model, true, es, rp, W, d, k);
       const float vh = query_elem(a.model, false, eo, rp, W, d, k);
@@ -82,8 +82,12 @@ __global__ __launch_bounds__(128) void k_rank_query(RankArgs a) {
     }
     __builtin_amdgcn_wave_barrier();
     if (l == 0) {   // tail: entity o under q_tail; head: entity s under q_head
-      a.tgt[2 * i] = l1 ? rank_score<true>(lqt, eo, d) : rank_score<false>(lqt, eo, d);
-      a.tgt[2 * i + 1] = l1 ? rank_score<true>(lqh, es, d) : rank_score<false>(lqh, es, d);
+      a.tgt[2 * i] = form == RT_L1     ? rank_score_form<RT_L1>(lqt, eo, d)
+                     : form == RT_CMOD ? rank_score_form<RT_CMOD>(lqt, eo, d)
+                                       : rank_score_form<RT_DOT>(lqt, eo, d);
+      a.tgt[2 * i + 1] = form == RT_L1     ? rank_score_form<RT_L1>(lqh, es, d)
+                         : form == RT_CMOD ? rank_score_form<RT_CMOD>(lqh, es, d)
+                                           : rank_score_form<RT_DOT>(lqh, es, d);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -202,17 +206,17 @@ struct RankArgs2 {
 
 // one workgroup: 64 query vectors x one entity slice of the counting tile
 // (skge_rank_tile.h)
-template <bool L1>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_rank_count2(RankArgs2 a) {
   const int ebeg = blockIdx.y * a.eslice, eend = min(a.N, ebeg + a.eslice);
   const RankRows m = {(int)blockIdx.x * RT_QB, a.nv};
-  rank_count_tile<L1>(a.E, a.d, a.Q, a.tgt, a.raw, ebeg, eend, m);
+  rank_count_tile<FORM>(a.E, a.d, a.Q, a.tgt, a.raw, ebeg, eend, m);
 }
 
 // filtered correction + the ranks: one thread per query vector, its known
 // answers (CSR, the true entity excluded by the caller) scored with the
 // counting pass's arithmetic (sequential k)
-template <bool L1>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_rank_known(const float* __restrict__ E, int d, int nq,
                                                     const float* __restrict__ Q,
                                                     const float* __restrict__ tgt,
@@ -231,7 +235,7 @@ __global__ __launch_bounds__(256) void k_rank_known(const float* __restrict__ E,
   const float t = tgt[v];
   int dec = 0;
   for (int i = off[qi]; i < off[qi + 1]; ++i) {
-    if (rank_score<L1>(q, E + (size_t)ent[i] * d, d) > t) ++dec;
+    if (rank_score_form<FORM>(q, E + (size_t)ent[i] * d, d) > t) ++dec;
   }
   ranks[4 * qi + 2 * dir] = 1 + raw[v];
   ranks[4 * qi + 2 * dir + 1] = 1 + raw[v] - dec;
@@ -260,6 +264,11 @@ void launch_rank_query(hipStream_t st, int model, const float* E, const float* R
 // vector Q[v]}, v < nv (skge_host.h)
 void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d, const float* Q,
                        const float* tgt, int nv, int* raw) {
+  launch_rank_count_form(st, l1 ? RT_L1 : RT_DOT, T, rows, d, Q, tgt, nv, raw);
+}
+// ... with the score's form named (RT_L1, RT_DOT or RT_CMOD, skge_rank_tile.h)
+void launch_rank_count_form(hipStream_t st, int form, const float* T, int rows, int d,
+                            const float* Q, const float* tgt, int nv, int* raw) {
   RankArgs2 b;
   b.E = T;
   b.N = rows;
@@ -271,10 +280,12 @@ void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d,
   const int qb = (nv + RT_QB - 1) / RT_QB;   // query blocks x entity slices
   const SlicePlan p = slice_plan(qb, (rows + RT_EB - 1) / RT_EB);
   b.eslice = p.per * RT_EB;
-  if (l1)
-    hipLaunchKernelGGL((k_rank_count2<true>), dim3(qb, p.ns), dim3(256), 0, st, b);
+  if (form == RT_L1)
+    hipLaunchKernelGGL((k_rank_count2<RT_L1>), dim3(qb, p.ns), dim3(256), 0, st, b);
+  else if (form == RT_CMOD)
+    hipLaunchKernelGGL((k_rank_count2<RT_CMOD>), dim3(qb, p.ns), dim3(256), 0, st, b);
   else
-    hipLaunchKernelGGL((k_rank_count2<false>), dim3(qb, p.ns), dim3(256), 0, st, b);
+    hipLaunchKernelGGL((k_rank_count2<RT_DOT>), dim3(qb, p.ns), dim3(256), 0, st, b);
 }
 
 }  // namespace skge
@@ -301,14 +312,17 @@ extern "C" int skge_rank_known(void* stream, int model, const float* E, const fl
   hipStream_t st = as_stream(stream);
   SKGE_CHECK_HIP(hipMemsetAsync(raw, 0, (size_t)2 * nq * sizeof(int), st));
   launch_rank_query(st, model, E, R, N, d, queries, nq, Q, tgt);
-  const bool l1 = model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2;
-  launch_rank_count(st, l1, E, N, d, Q, tgt, 2 * nq, raw);
+  const int form = rank_form(model);
+  launch_rank_count_form(st, form, E, N, d, Q, tgt, 2 * nq, raw);
   const int kb = (2 * nq + 255) / 256;
-  if (l1)
-    hipLaunchKernelGGL((k_rank_known<true>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
+  if (form == RT_L1)
+    hipLaunchKernelGGL((k_rank_known<RT_L1>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
+                       tail_off, tail_ent, head_off, head_ent, ranks_out);
+  else if (form == RT_CMOD)
+    hipLaunchKernelGGL((k_rank_known<RT_CMOD>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
                        tail_off, tail_ent, head_off, head_ent, ranks_out);
   else
-    hipLaunchKernelGGL((k_rank_known<false>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
+    hipLaunchKernelGGL((k_rank_known<RT_DOT>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
                        tail_off, tail_ent, head_off, head_ent, ranks_out);
   SKGE_CHECK_LAUNCH("rank (known answers)");
   return SKGE_OK;
@@ -323,6 +337,8 @@ extern "C" int skge_rank(void* stream, int model, const float* E, const float* R
                          void* workspace, size_t ws_bytes, int* ranks_out) {
   SKGE_CHECK_ARG(E && R && queries && ranks_out, "NULL argument");
   SKGE_CHECK_MODEL(model, d);
+  // (the first round's counting kernel; skge_rank_known serves RotatE)
+  SKGE_REFUSE_ROTATE(model, "skge_rank");
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && nq >= 0, "bad sizes (d <= 1024)");
   if (nq == 0) return SKGE_OK;
   SKGE_CHECK_ARG(workspace && ws_bytes >= skge_rank_workspace_bytes(nq, d),

@@ -18,6 +18,7 @@
 #include "skge_hole.h"
 #include "skge_hole_fft.h"
 #include "skge_host.h"
+#include "skge_rot.h"
 #include "skge_sampler.h"
 
 namespace skge {
@@ -510,6 +511,52 @@ __device__ __forceinline__ bool diag_pair(const PairArgs& a, int i, const int (&
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// RotatE pair (skge_rot.h): TransE's conventions -- raw scores, violation
+// nscore + margin > pscore (strict), entity rows (sp, op, sn, on), relation
+// rows (pp, pn), rows on one id merged (acc_two) -- with, per pair,
+// u = E[s] * R[p] - E[o] and w = u / |u| per component:
+//   score  -sum_j |u_j|
+//   positive (gradient of -phi): E[s] <- conj(R[p]) * w   E[o] <- -w   R[p] <- conj(E[s]) * w
+//   negative (gradient of +phi): the same three, negated
+// Registers only: no LDS.
+// ---------------------------------------------------------------------------
+template <int KM>
+__device__ __forceinline__ bool rot_pair(const PairArgs& a, int i, const int (&ix)[6]) {
+  const int d = a.d;
+  const int sp = ix[0], op = ix[1], pp = ix[2], sn = ix[3], on = ix[4], pn = ix[5];
+  float es[KM], eo[KM], rp[KM], fs[KM], fo[KM], rn[KM];
+  load_row<KM>(a.E, sp, d, es);
+  load_row<KM>(a.E, op, d, eo);
+  load_row<KM>(a.R, pp, d, rp);
+  load_row<KM>(a.E, sn, d, fs);
+  load_row<KM>(a.E, on, d, fo);
+  load_row<KM>(a.R, pn, d, rn);
+  float wp[KM], wn[KM], t[KM];
+  diag_mul<COMPLEX, KM>(es, rp, t);
+  rot_sub<KM>(t, eo, wp);
+  diag_mul<COMPLEX, KM>(fs, rn, t);
+  rot_sub<KM>(t, fo, wn);
+  const float pscore = -rot_unit<KM>(wp), nscore = -rot_unit<KM>(wn);
+  if (lane_id() == 0) {
+    if (a.pscore) a.pscore[i] = pscore;
+    if (a.nscore) a.nscore[i] = nscore;
+  }
+  if (!(nscore + a.margin > pscore)) return false;
+  float x[KM], y[KM];
+  diag_cmul<COMPLEX, KM>(rp, wp, x);
+  diag_cmul<COMPLEX, KM>(rn, wn, t);
+  rot_neg<KM>(y, t);
+  acc_two<KM>(a.accE, sp, x, sn, y, d);
+  rot_neg<KM>(x, wp);
+  acc_two<KM>(a.accE, op, x, on, wn, d);
+  diag_cmul<COMPLEX, KM>(es, wp, x);
+  diag_cmul<COMPLEX, KM>(fs, wn, t);
+  rot_neg<KM>(y, t);
+  acc_two<KM>(replica(a.accR, i), pp, x, pn, y, d);
+  return true;
+}
+
 // E.violations[u] += 1 for each distinct u in {sn, on, sp, op} of a violating
 // pair (skge/transe.py:78-83): lane j < 4 takes one entity and counts it
 // unless an earlier lane holds the same id
@@ -547,6 +594,8 @@ __global__ __launch_bounds__(256) void k_pair_grad(PairArgs a) {
       v = hole_pair<KM>(a, i, sw, ix);
     else if constexpr (is_diag(MODEL))
       v = diag_pair<MODEL, KM>(a, i, ix);
+    else if constexpr (MODEL == ROTATE)
+      v = rot_pair<KM>(a, i, ix);
     else
       v = rescal_pair<KM>(a, i, sw, ix);
     const Accum aR = replica(a.accR, i);   // dense relation tables may spread over copies
@@ -1069,6 +1118,153 @@ int launch_diag_pos(hipStream_t st, int model, int af, const skge_table_t* ent,
 }
 
 // ---------------------------------------------------------------------------
+// RotatE pairwise, one positive and BOTH of its pairs per wave (device pair
+// loop; k_diag_pos's records, slots and counts: pair 2j = ((s,o,p), (s',o,p)),
+// pair 2j+1 = ((s,o,p), (s,o',p))).  The wave reads E[s], E[o], R[p] once and
+// one entity row per corruption -- 5 row loads, all issued before the first
+// product -- forms S = E[s] * R[p] once for the positive and the o-corruption,
+// and scores with rot_pair's arithmetic (skge_rot.h), so the margin decisions
+// are the pair path's:
+//   wp = unit(S - E[o])   w0 = unit(E[s'] * R[p] - E[o])   w1 = unit(S - E[o'])
+// A violating pair's rows are rot_pair's, each with its own rounding (ids that
+// coincide within a pair are merged there by acc_two's float sum -- always
+// (o, o) and (p, p) of pair 2j, (s, s) and (p, p) of pair 2j+1), with
+// A = conj(R[p]) * wp and D = conj(E[s]) * wp:
+//   E[s] : [v0] A (- conj(R[p]) * w0 if s' == s)   + [v1] (A - conj(R[p]) * w1)
+//   E[o] : [v0] (-wp + w0)                         + [v1] -wp (+ w1 if o' == o)
+//   R[p] : [v0] (D - conj(E[s']) * w0)             + [v1] (D - conj(E[s]) * w1)
+//   E[s']: -conj(R[p]) * w0     E[o']: w1
+// and the two terms of a row go out as ONE add per element (diag_acc_row2):
+// the float sum, or in the deterministic mode the sum of the two fixed-point
+// roundings, which is bit for bit what the explicit pairs add.  No LDS.
+// ---------------------------------------------------------------------------
+struct RotPosArgs {
+  const float* E;
+  const float* R;
+  Accum accE, accR;
+  const int4* rec;   // the epoch's records (s, o, p, s' or -1)
+  const int* rec_n1; // o' or -1
+  long long start;   // this batch: positives [start, start + count)
+  int count, d;
+  float margin;
+  int* nviol;        // this batch's gate word: += violating pairs
+};
+
+template <int KM>
+__global__ __launch_bounds__(256) void k_rot_pos(RotPosArgs a) {
+  const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6, l = lane_id();
+  const int d = a.d;
+  int nv = 0;
+  for (int j = blockIdx.x * wpb + wave; j < a.count; j += gridDim.x * wpb) {
+    const int4 r4 = a.rec[a.start + j];
+    const int s = uni(r4.x), o = uni(r4.y), p = uni(r4.z), neg0 = uni(r4.w);
+    const int neg1 = uni(a.rec_n1[a.start + j]);
+    // a corruption that was not drawn reads the row it would have replaced
+    const int n0r = neg0 >= 0 ? neg0 : s, n1r = neg1 >= 0 ? neg1 : o;
+    float es[KM], eo[KM], rp[KM], fs[KM], fo[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.E, o, d, eo);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, n0r, d, fs);
+    load_row<KM>(a.E, n1r, d, fo);
+    float wp[KM], w0[KM], w1[KM], t[KM];
+    diag_mul<COMPLEX, KM>(es, rp, t);    // S, for the positive and the o-corruption
+    rot_sub<KM>(t, eo, wp);
+    rot_sub<KM>(t, fo, w1);
+    diag_mul<COMPLEX, KM>(fs, rp, t);
+    rot_sub<KM>(t, eo, w0);
+    const float pscore = -rot_unit<KM>(wp);
+    const float s0 = -rot_unit<KM>(w0), s1 = -rot_unit<KM>(w1);
+    const int v0 = uni((neg0 >= 0 && s0 + a.margin > pscore) ? 1 : 0);
+    const int v1 = uni((neg1 >= 0 && s1 + a.margin > pscore) ? 1 : 0);
+    const bool ms = neg0 == s, mo = neg1 == o;   // a corruption that drew the id it replaces
+    const Accum aR = replica(a.accR, j);
+    if (l < 4)
+      commit_slot(a.accE,
+                  sel4(l, s, o, neg0, neg1),
+                  sel4(l, v0 * (ms ? 2 : 1) + 2 * v1, 2 * v0 + v1 * (mo ? 2 : 1), ms ? 0 : v0,
+                       mo ? 0 : v1),
+                  4 * j + l);
+    else if (l == 4)
+      commit_slot(aR, p, 2 * (v0 + v1), j);
+    if (v0 + v1 == 0) continue;
+    nv += v0 + v1;
+    float A[KM], x[KM], y[KM];
+    // E[s] and E[s']
+    diag_cmul<COMPLEX, KM>(rp, wp, A);
+    diag_cmul<COMPLEX, KM>(rp, w0, t);
+    if (ms) rot_diff<KM>(x, A, t);
+    else diag_scale<KM>(x, 1.0f, A);
+    if (v0 && !ms) {
+      float n[KM];
+      rot_neg<KM>(n, t);
+      acc_row<KM>(a.accE, neg0, n, d);
+    }
+    diag_cmul<COMPLEX, KM>(rp, w1, t);
+    rot_diff<KM>(y, A, t);
+    diag_acc_row2<KM>(a.accE, s, x, v0 != 0, y, v1 != 0, d);
+    // E[o] and E[o']
+    rot_diff<KM>(x, w0, wp);             // -wp + w0
+    if (mo) rot_diff<KM>(y, w1, wp);
+    else rot_neg<KM>(y, wp);
+    diag_acc_row2<KM>(a.accE, o, x, v0 != 0, y, v1 != 0, d);
+    if (v1 && !mo) acc_row<KM>(a.accE, neg1, w1, d);
+    // R[p]
+    diag_cmul<COMPLEX, KM>(es, wp, A);   // D
+    diag_cmul<COMPLEX, KM>(fs, w0, t);
+    rot_diff<KM>(x, A, t);
+    diag_cmul<COMPLEX, KM>(es, w1, t);
+    rot_diff<KM>(y, A, t);
+    diag_acc_row2<KM>(aR, p, x, v0 != 0, y, v1 != 0, d);
+  }
+  __shared__ int lds_nv;
+  block_count_add(a.nviol, nv, &lds_nv);   // one atomic per workgroup
+}
+
+bool rot_pos_ok(int model, const skge_table_t* ent, const skge_table_t* rel, int d) {
+  return model == SKGE_ROTATE && d >= 2 && d <= 256 && d % 2 == 0 && ent && rel &&
+         ent->width == d && rel->width == d &&
+         (ent->acc_mode == SKGE_ACC_F32 || ent->acc_mode == SKGE_ACC_FX64) &&
+         (rel->acc_mode == SKGE_ACC_F32 || rel->acc_mode == SKGE_ACC_FX64) &&
+         ent->acc_replicas <= 1 && ent->acc_sum && ent->acc_cnt && rel->acc_sum && rel->acc_cnt;
+}
+
+// one batch of the RotatE device pair loop (slots: 4 * count entity, count
+// relation)
+int launch_rot_pos(hipStream_t st, const skge_table_t* ent, const skge_table_t* rel, int d,
+                   const int4* rec, const int* rec_n1, long long start, int count, float margin,
+                   int* nviol) {
+  int rc;
+  if ((rc = check_table(ent, "ent", true)) || (rc = check_table(rel, "rel", true)) ||
+      (rc = check_slots(ent, 4ll * count, "ent")) || (rc = check_slots(rel, count, "rel")))
+    return rc;
+  SKGE_CHECK_ARG(rot_pos_ok(SKGE_ROTATE, ent, rel, d), "RotatE positive kernel: unsupported tables");
+  SKGE_CHECK_ARG(rec && rec_n1 && nviol && count >= 0, "bad argument");
+  if (count == 0) return SKGE_OK;
+  RotPosArgs a = {};
+  a.E = ent->param;
+  a.R = rel->param;
+  a.accE = accum_of(ent);
+  a.accR = accum_of(rel);
+  a.rec = rec;
+  a.rec_n1 = rec_n1;
+  a.start = start;
+  a.count = count;
+  a.d = d;
+  a.margin = margin;
+  a.nviol = nviol;
+  const int blocks = std::max(1, std::min((count + 3) / 4, 8192));
+  switch (km_for(d)) {
+    case 1: hipLaunchKernelGGL((k_rot_pos<1>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_rot_pos<2>), dim3(blocks), dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_rot_pos<3>), dim3(blocks), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((k_rot_pos<4>), dim3(blocks), dim3(256), 0, st, a); break;
+  }
+  SKGE_CHECK_LAUNCH("rotate positive kernel");
+  return SKGE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // logistic loss: HolE skge/hole.py:22-42, RESCAL skge/rescal.py:37-76
 // (logistic(): skge_device.h).  A triple with relation -1 is SKIPPED
 // (skge_triple_grad in skge_hip.h): its slots name no row, coef 0, nothing
@@ -1585,8 +1781,9 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
   int blocks = (a.P + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   if (blocks < 1) blocks = 1;
-  // TransE, DistMult and ComplEx work in registers: no LDS to cap their occupancy
-  size_t lds = (MODEL == TRANSE_L1 || MODEL == TRANSE_L2 || is_diag(MODEL))
+  // TransE, DistMult, ComplEx and RotatE work in registers: no LDS to cap their
+  // occupancy
+  size_t lds = (MODEL == TRANSE_L1 || MODEL == TRANSE_L2 || is_diag(MODEL) || MODEL == ROTATE)
                    ? 0 : (size_t)4 * 6 * 64 * km * 4;
   const int path = MODEL == HOLE ? hole_step_path(a.d, logistic_mode, a.record != 0)
                                  : SKGE_PATH_GENERIC;
@@ -1630,12 +1827,17 @@ static int launch_pair(const PairArgs& a, int km, hipStream_t st, bool logistic_
     SKGE_CHECK_LAUNCH("hole fast pair launch");
     return SKGE_OK;
   }
-#define SKGE_LP(K)                                                                             \
-  case K:                                                                                      \
-    if (logistic_mode)                                                                         \
-      hipLaunchKernelGGL((k_triple_grad<MODEL, K>), dim3(blocks), dim3(threads), lds, st, a); \
-    else                                                                                       \
-      hipLaunchKernelGGL((k_pair_grad<MODEL, K>), dim3(blocks), dim3(threads), lds, st, a);   \
+  // (RotatE has no logistic step: skge_triple_grad refuses it, and no
+  // k_triple_grad instance is built for it)
+#define SKGE_LP(K)                                                                               \
+  case K:                                                                                        \
+    if constexpr (MODEL != ROTATE) {                                                             \
+      if (logistic_mode) {                                                                       \
+        hipLaunchKernelGGL((k_triple_grad<MODEL, K>), dim3(blocks), dim3(threads), lds, st, a); \
+        break;                                                                                   \
+      }                                                                                          \
+    }                                                                                            \
+    hipLaunchKernelGGL((k_pair_grad<MODEL, K>), dim3(blocks), dim3(threads), lds, st, a);       \
     break;
   switch (km) {
     SKGE_LP(1)
@@ -1719,6 +1921,7 @@ extern "C" int skge_pair_grad(void* stream, int model, int af, const skge_table_
     case SKGE_HOLE: return launch_pair<HOLE>(a, km, st, false);
     case SKGE_DISTMULT: return launch_pair<DISTMULT>(a, km, st, false);
     case SKGE_COMPLEX: return launch_pair<COMPLEX>(a, km, st, false);
+    case SKGE_ROTATE: return launch_pair<ROTATE>(a, km, st, false);
     default: return launch_pair<RESCAL>(a, km, st, false);
   }
 }
@@ -1728,6 +1931,7 @@ extern "C" int skge_triple_grad(void* stream, int model, const skge_table_t* ent
                                 int T, float* score, float* coef, float* loss) {
   int rc = check_model_tables(model, ent, rel, d);
   if (rc) return rc;
+  SKGE_REFUSE_ROTATE(model, "logistic step");
   SKGE_CHECK_ARG(model == SKGE_HOLE || model == SKGE_RESCAL || model_diag(model),
                  "logistic loss is defined for HolE, RESCAL, DistMult and ComplEx only");
   SKGE_CHECK_ARG(T >= 0, "T < 0");

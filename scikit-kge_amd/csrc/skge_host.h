@@ -67,19 +67,46 @@ inline int km_for(int d) {
   return 0;
 }
 
-// the model codes of include/skge_hip.h: 0..3, 5, 6 (4 is unassigned)
+// the model codes of include/skge_hip.h: 0..3, 5, 6, 7 (4 is unassigned)
 inline bool model_known(int model) {
   return (model >= SKGE_TRANSE_L1 && model <= SKGE_RESCAL) || model == SKGE_DISTMULT ||
-         model == SKGE_COMPLEX;
+         model == SKGE_COMPLEX || model == SKGE_ROTATE;
 }
+// rows of d/2 interleaved complex components: ComplEx and RotatE
+inline bool model_complex_rows(int model) { return model == SKGE_COMPLEX || model == SKGE_ROTATE; }
 // DistMult / ComplEx: HolE's table shapes and slot maps, skge_diag.h's scores
 inline bool model_diag(int model) { return model == SKGE_DISTMULT || model == SKGE_COMPLEX; }
-// the model's code and width: ComplEx rows hold d/2 interleaved (re, im) pairs
+// the model's code and width: ComplEx and RotatE rows hold d/2 interleaved
+// (re, im) pairs
 #define SKGE_CHECK_MODEL(model, d)                                                       \
   do {                                                                                   \
     SKGE_CHECK_ARG(::skge::model_known(model), "unknown model %d", model);               \
     SKGE_CHECK_ARG((model) != SKGE_COMPLEX || (d) % 2 == 0, "ComplEx needs an even d (%d)", d); \
+    SKGE_CHECK_ARG((model) != SKGE_ROTATE || (d) % 2 == 0, "RotatE needs an even d (%d)", d); \
   } while (0)
+// an entry point RotatE is not served by (include/skge_hip.h, SKGE_ROTATE)
+#define SKGE_REFUSE_ROTATE(model, who)                                                   \
+  SKGE_CHECK_ARG((model) != SKGE_ROTATE, "%s: RotatE is not served here", who)
+
+// SKGE_POST_UNITMOD is applied by the row applies of skge_update.hip only
+// (update_row, apply_row, apply_row_rep_block).  Every other consumer of a
+// table would read "not NONE and not NORMALIZE" as normless1, so it refuses the
+// code by name first: true (and the error text) when t carries it.
+inline bool refuses_unitmod(const skge_table_t* t, const char* who) {
+  if (!t || t->post != SKGE_POST_UNITMOD) return false;
+  set_error("%s: post SKGE_POST_UNITMOD (unit-modulus components, RotatE's relation table) is "
+            "not served here; use the per-batch step or the pair loop", who);
+  return true;
+}
+// what a table with SKGE_POST_UNITMOD must be for the row applies
+inline int check_unitmod(const skge_table_t* t) {
+  if (t->post != SKGE_POST_UNITMOD) return SKGE_OK;
+  SKGE_CHECK_ARG(t->width % 2 == 0 && t->width <= 1024,
+                 "post SKGE_POST_UNITMOD needs an even width <= 1024 (%d)", t->width);
+  SKGE_CHECK_ARG(t->acc_mode == SKGE_ACC_F32 || t->acc_mode == SKGE_ACC_FX64,
+                 "post SKGE_POST_UNITMOD needs fp32 or fixed-point sums (acc_mode %d)", t->acc_mode);
+  return SKGE_OK;
+}
 
 int* dev_err_word();   // skge_update.hip: the device error word (Accum::err)
 inline Accum accum_of(const skge_table_t* t) {
@@ -181,6 +208,9 @@ void launch_rank_query(hipStream_t st, int model, const float* E, const float* R
                        const int* queries, int nq, float* Q, float* tgt);
 void launch_rank_count(hipStream_t st, bool l1, const float* T, int rows, int d, const float* Q,
                        const float* tgt, int nv, int* raw);
+// ... with the form named: RT_L1, RT_DOT or RT_CMOD (skge_rank_tile.h)
+void launch_rank_count_form(hipStream_t st, int form, const float* T, int rows, int d,
+                            const float* Q, const float* tgt, int nv, int* raw);
 
 // skge_topk.hip: the top-k selection and merge, for callers that select rows
 // of another table (skge_relation.hip).  For query vectors Q [nq][d] the k best
@@ -271,6 +301,13 @@ bool diag_pos_ok(int model, int af, const skge_table_t* ent, const skge_table_t*
 int launch_diag_pos(hipStream_t st, int model, int af, const skge_table_t* ent,
                     const skge_table_t* rel, int d, const int4* rec, const int* rec_n1,
                     long long start, int count, float margin, int* nviol);
+
+// skge_grad.hip: RotatE pairwise, one positive (both of its pairs) per wave
+// (k_rot_pos): even d <= 256, fp32 or fixed-point sums, one entity copy
+bool rot_pos_ok(int model, const skge_table_t* ent, const skge_table_t* rel, int d);
+int launch_rot_pos(hipStream_t st, const skge_table_t* ent, const skge_table_t* rel, int d,
+                   const int4* rec, const int* rec_n1, long long start, int count, float margin,
+                   int* nviol);
 
 // The RESCAL W updater's step after the fused front (skge_rescal.hip
 // k_rescal_front_fused): W[p] from relation p's split-K dW partial tiles,

@@ -22,7 +22,8 @@
 // one wave straight from the records (k_hole_pos, skge_grad.hip): the same
 // pairs, contributions and counts, 7 correlations per positive instead of 12.
 // DistMult and ComplEx (d <= 256) do the same with k_diag_pos: 5 row reads per
-// positive instead of 12, one accumulator add per distinct row.
+// positive instead of 12, one accumulator add per distinct row; RotatE with
+// k_rot_pos.
 #include <cstdlib>
 #include <vector>
 
@@ -150,6 +151,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
   if (check_sampler(smp, "pair runner")) return nullptr;
   if (!model_known(model)) return fail("pair runner: unknown model");
   if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
+  if (model == SKGE_ROTATE && d % 2) return fail("pair runner: RotatE needs an even d");
   if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity,
                          2 * T, ntries, stream))
     return nullptr;
@@ -175,6 +177,9 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
   // pairs)
   const char* dg = getenv("SKGE_DIAG_PAIRS");
   const bool dpos = !(dg && atoi(dg)) && diag_pos_ok(model, af, ent, rel, d);
+  // RotatE: the same with k_rot_pos (SKGE_ROT_PAIRS=1 keeps the explicit pairs)
+  const char* rg = getenv("SKGE_ROT_PAIRS");
+  const bool tpos = !(rg && atoi(rg)) && rot_pos_ok(model, ent, rel, d);
   const int nb = batches.size();
   // RESCAL: every batch's relation buckets built once per epoch, up front (the
   // items do not depend on the parameters); SKGE_RESCAL_EPOCH_BUCKETS=0 keeps
@@ -186,7 +191,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
                     : skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
   r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
   r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
-  if (!hpos && !dpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
+  if (!hpos && !dpos && !tpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
   if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
   if (!r->alloc_ok) return fail("pair runner: device allocation failed");
@@ -214,11 +219,12 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
     const long long start = batches[k].first;
     const int count = (int)batches[k].second;
     int* gate = r->nviol + k;
-    if (hpos || dpos) {
-      rc = hpos ? launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin,
-                                  gate, nullptr, nullptr)
-                : launch_diag_pos(st, model, af, ent, rel, d, r->rec, r->rec_n1, start, count,
-                                  margin, gate);
+    if (hpos || dpos || tpos) {
+      rc = hpos   ? launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin,
+                                    gate, nullptr, nullptr)
+           : dpos ? launch_diag_pos(st, model, af, ent, rel, d, r->rec, r->rec_n1, start, count,
+                                    margin, gate)
+                  : launch_rot_pos(st, ent, rel, d, r->rec, r->rec_n1, start, count, margin, gate);
       if (!rc) {
         skge_table_t t[2] = {*ent, *rel};
         t[0].gate = gate;
@@ -286,6 +292,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
   if (check_sampler(smp, "pair runner")) return nullptr;
   if (!model_known(model)) return fail("pair runner: unknown model");
   if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
+  if (model == SKGE_ROTATE && d % 2) return fail("pair runner: RotatE needs an even d");
   int K = 0;
   if (check_negatives(negs, smp, rel->rows, "pair runner", &K)) return nullptr;
   // pairs, their 3 ids and their 4 entity slots are indexed with ints

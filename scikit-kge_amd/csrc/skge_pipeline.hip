@@ -1366,6 +1366,9 @@ static bool pipe_check_tables(const skge_table_t* ent, const skge_table_t* rel, 
     return set_error("pipelined runner: the data-parallel form (SKGE_PIPE_DP) draws RANDOM negatives "
                 "only, not sampler kind %d", kind), false;
   if (!ent || !rel) return set_error("pipelined runner: NULL table"), false;
+  // (the pipelined row updates read any projection but normalize as normless1)
+  if (refuses_unitmod(ent, "pipelined runner") || refuses_unitmod(rel, "pipelined runner"))
+    return false;
   skge_table_t relc = *rel;   // the relation encoding is the runner's own (checked below)
   if (relc.acc_mode == SKGE_ACC_I32X2) relc.acc_mode = SKGE_ACC_I16X4;
   skge_table_t entc = *ent;   // int8x4 entity sums: the runner's own encoding too

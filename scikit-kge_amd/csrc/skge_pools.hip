@@ -119,7 +119,7 @@ struct PoolRankArgs {
   PoolWork pw;
 };
 
-template <bool L1>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_rank_count_pool(PoolRankArgs a) {
   __shared__ int s_vec[RT_QB];
   if ((int)blockIdx.x >= *a.pw.n_items) return;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_rank_count_pool(PoolRankArgs a) {
   const RankPoolRows m = {a.pw.order + vbeg, vcnt, pool >= 0 ? a.pw.pool_ent + base : nullptr,
                           s_vec};
   if (threadIdx.x < RT_QB) s_vec[threadIdx.x] = m.vec(threadIdx.x);
-  rank_count_tile<L1>(a.E, a.d, a.Q, a.tgt, a.raw, ebeg, eend, m);
+  rank_count_tile<FORM>(a.E, a.d, a.Q, a.tgt, a.raw, ebeg, eend, m);
 }
 
 // e is an entry of the ascending list p[0 .. n)
@@ -148,7 +148,7 @@ __device__ __forceinline__ bool pool_has(const int* __restrict__ p, int n, int e
 // filtered correction + the ranks: k_rank_known's form (one thread per query
 // vector, its known answers scored with the counting pass's arithmetic); an
 // answer counts only when the vector's pool holds it
-template <bool L1>
+template <int FORM>
 __global__ __launch_bounds__(256) void k_rank_known_pool(
     const float* __restrict__ E, int d, int nq, const float* __restrict__ Q,
     const float* __restrict__ tgt, const int* __restrict__ raw, const int* __restrict__ vec_pool,
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_rank_known_pool(
   for (int i = off[qi]; i < off[qi + 1]; ++i) {
     const int e = ent[i];
     if (pool >= 0 && !pool_has(mem, nmem, e)) continue;
-    if (rank_score<L1>(q, E + (size_t)e * d, d) > t) ++dec;
+    if (rank_score_form<FORM>(q, E + (size_t)e * d, d) > t) ++dec;
   }
   ranks[4 * qi + 2 * dir] = 1 + raw[v];
   ranks[4 * qi + 2 * dir + 1] = 1 + raw[v] - dec;
@@ -228,24 +228,27 @@ extern "C" int skge_rank_pools(void* stream, int model, const float* E, const fl
   const int rc = launch_pool_group(st, vec_pool, nv, n_pools, RT_QB, pool_off, pool_ent, gws, &a.pw);
   if (rc != SKGE_OK) return rc;
   launch_rank_query(st, model, E, R, N, d, queries, nq, Q, tgt);
-  const bool l1 = model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2;
+  const int form = rank_form(model);
   const int max_items = pool_items_max(nv, n_pools, RT_QB);
   // a pool has at most N candidates; one with fewer tiles than slices leaves
   // the others empty
   a.pw.ns = slice_plan(max_items, (N + RT_EB - 1) / RT_EB).ns;
   const dim3 grid(max_items, a.pw.ns);
   const int kb = (nv + 255) / 256;
-  if (l1) {
-    hipLaunchKernelGGL((k_rank_count_pool<true>), grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_rank_known_pool<true>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
-                       vec_pool, pool_off, pool_ent, tail_off, tail_ent, head_off, head_ent,
-                       ranks_out);
-  } else {
-    hipLaunchKernelGGL((k_rank_count_pool<false>), grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_rank_known_pool<false>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt, raw,
-                       vec_pool, pool_off, pool_ent, tail_off, tail_ent, head_off, head_ent,
-                       ranks_out);
-  }
+#define SKGE_RP(F)                                                                              \
+  do {                                                                                          \
+    hipLaunchKernelGGL((k_rank_count_pool<F>), grid, dim3(256), 0, st, a);                      \
+    hipLaunchKernelGGL((k_rank_known_pool<F>), dim3(kb), dim3(256), 0, st, E, d, nq, Q, tgt,    \
+                       raw, vec_pool, pool_off, pool_ent, tail_off, tail_ent, head_off,         \
+                       head_ent, ranks_out);                                                    \
+  } while (0)
+  if (form == RT_L1)
+    SKGE_RP(RT_L1);
+  else if (form == RT_CMOD)
+    SKGE_RP(RT_CMOD);
+  else
+    SKGE_RP(RT_DOT);
+#undef SKGE_RP
   SKGE_CHECK_LAUNCH("rank (pools)");
   return SKGE_OK;
 }

@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "skge_device.h"
+
 namespace skge {
 
 constexpr int RT_QB = 64;    // query vectors per workgroup of the counting pass
@@ -17,6 +19,33 @@ constexpr int RT_EB = 128;   // candidates per LDS tile
 constexpr int RT_KC = 32;    // dims per LDS chunk
 constexpr int RT_PADE = RT_EB + 4;   // rows stay 16-B aligned (the Q image: QB + 4)
 enum { RT_L1 = 0, RT_L2SQ = 1, RT_DOT = 2 };   // -sum|q - e|, -sum (q - e)^2, sum e q
+// RotatE: -sum_j |q_j - e_j| over the d/2 complex components (x[2j], x[2j + 1])
+// of a row, the modulus sqrtf(t0^2 + t1^2) as sqrtf(fmaf(t0, t0, t1 * t1)),
+// t = q - e.  d is even and so is RT_KC: a component never straddles a row's
+// end or an LDS chunk.
+constexpr int RT_CMOD = 3;
+
+// the form a model's ranking entry points score with (both TransE codes as L1)
+__host__ __device__ __forceinline__ int rank_form(int model) {
+  return model == TRANSE_L1 || model == TRANSE_L2 ? RT_L1 : (model == ROTATE ? RT_CMOD : RT_DOT);
+}
+
+// rank_score (skge_device.h) by form; RT_CMOD: the tile's chain, one complex
+// component per step in ascending order
+template <int FORM>
+__device__ __forceinline__ float rank_score_form(const float* __restrict__ q,
+                                                 const float* __restrict__ e, int d) {
+  if constexpr (FORM == RT_CMOD) {
+    float acc = 0.0f;
+    for (int k = 0; k + 1 < d; k += 2) {
+      const float t0 = q[k] - e[k], t1 = q[k + 1] - e[k + 1];
+      acc = acc - sqrtf(fmaf(t0, t0, t1 * t1));
+    }
+    return acc;
+  } else {
+    return rank_score<FORM == RT_L1>(q, e, d);
+  }
+}
 
 // dims k .. k + 3 of a row of width d, zeros past d and for a row that is not
 // there (ok false: nothing is read).  stage_load4 (skge_stage.h) is the MFMA
@@ -49,6 +78,41 @@ struct RankRows {
   __device__ __forceinline__ int row(int e) const { return e; }
   __device__ __forceinline__ int kept(int i) const { return vec(i); }
 };
+
+// RT_CMOD's pass over one staged chunk of kn dims (kn even): two dims, one
+// complex component, per step
+template <int QB>
+__device__ __forceinline__ void cmod_chunk(float (*sQ)[QB + 4], float (*sE)[RT_PADE],
+                                           int te, int tq, int kn, float (&acc)[8][QB / 16]) {
+  constexpr int TQ = QB / 16;
+  for (int k = 0; k + 1 < kn; k += 2) {
+    const float4 ra = *reinterpret_cast<const float4*>(&sE[k][te]);
+    const float4 rb = *reinterpret_cast<const float4*>(&sE[k][te + 4]);
+    const float4 ia = *reinterpret_cast<const float4*>(&sE[k + 1][te]);
+    const float4 ib = *reinterpret_cast<const float4*>(&sE[k + 1][te + 4]);
+    const float er[8] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
+    const float ei[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
+    float qr[TQ], qi[TQ];
+    if constexpr (TQ == 4) {
+      const float4 a4 = *reinterpret_cast<const float4*>(&sQ[k][tq]);
+      const float4 b4 = *reinterpret_cast<const float4*>(&sQ[k + 1][tq]);
+      qr[0] = a4.x, qr[1] = a4.y, qr[2] = a4.z, qr[3] = a4.w;
+      qi[0] = b4.x, qi[1] = b4.y, qi[2] = b4.z, qi[3] = b4.w;
+    } else {
+      const float2 a2 = *reinterpret_cast<const float2*>(&sQ[k][tq]);
+      const float2 b2 = *reinterpret_cast<const float2*>(&sQ[k + 1][tq]);
+      qr[0] = a2.x, qr[1] = a2.y;
+      qi[0] = b2.x, qi[1] = b2.y;
+    }
+#pragma unroll
+    for (int x = 0; x < 8; ++x)
+#pragma unroll
+      for (int y = 0; y < TQ; ++y) {
+        const float t0 = qr[y] - er[x], t1 = qi[y] - ei[x];
+        acc[x][y] = acc[x][y] - sqrtf(fmaf(t0, t0, t1 * t1));
+      }
+  }
+}
 
 // One tile, by a workgroup of 256 threads: out[x][y] = the score of candidate
 // e0 + te + x < eend under vector m.vec(tq + y), te = 8 (tid & 15), tq =
@@ -107,6 +171,10 @@ __device__ __forceinline__ void score_tile(const float* E, int d, const float* Q
     }
     __syncthreads();
     const int kn = min(RT_KC, d - k0);
+    if constexpr (FORM == RT_CMOD) {
+      cmod_chunk<QB>(sQ, sE, te, tq, kn, acc);
+      continue;
+    }
     for (int k = 0; k < kn; ++k) {
       const float4 e4a = *reinterpret_cast<const float4*>(&sE[k][te]);
       const float4 e4b = *reinterpret_cast<const float4*>(&sE[k][te + 4]);
@@ -144,7 +212,7 @@ __device__ __forceinline__ void score_tile(const float* E, int d, const float* Q
 // eend, scoring strictly above tgt[v]} for the 64 vectors of mapping m.  The
 // scores are rank_score's, so the true entity never outranks itself; counts
 // go to LDS and then to raw by integer atomics.
-template <bool L1, class Map>
+template <int FORM, class Map>
 __device__ __forceinline__ void rank_count_tile(const float* E, int d, const float* Q,
                                                 const float* tgt, int* raw, int ebeg, int eend,
                                                 const Map m) {
@@ -162,7 +230,7 @@ __device__ __forceinline__ void rank_count_tile(const float* E, int d, const flo
   int cnt[4] = {0, 0, 0, 0};
   for (int e0 = ebeg; e0 < eend; e0 += RT_EB) {
     float acc[8][4];
-    score_tile<L1 ? RT_L1 : RT_DOT, RT_QB>(E, d, Q, e0, eend, m, sQ, sE, acc);
+    score_tile<FORM, RT_QB>(E, d, Q, e0, eend, m, sQ, sE, acc);
 #pragma unroll
     for (int y = 0; y < 4; ++y) {
       const float t = s_tgt[tq + y];

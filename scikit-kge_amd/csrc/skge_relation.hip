@@ -259,6 +259,8 @@ extern "C" int skge_relrank(void* stream, int model, const float* E, const float
   SKGE_CHECK_ARG(E && R && queries && ranks_out, "NULL argument");
   SKGE_CHECK_ARG(!known_off || known_rel, "NULL argument (known_rel with known_off given)");
   SKGE_CHECK_MODEL(model, d);
+  // |s * r_j - o| has no single query vector against the relation table
+  SKGE_REFUSE_ROTATE(model, "relation prediction");
   SKGE_CHECK_ARG(N > 0 && M >= 1 && d > 0 && d <= 1024 && nq >= 0,
                  "bad sizes (N = %d, M = %d, d = %d <= 1024, nq = %d)", N, M, d, nq);
   if (nq == 0) return SKGE_OK;
@@ -309,6 +311,8 @@ extern "C" int skge_reltopk(void* stream, int model, const float* E, const float
   SKGE_CHECK_ARG(E && R && pairs && rel_out && score_out, "NULL argument");
   SKGE_CHECK_ARG(!excl_off || excl_rel, "NULL argument (excl_rel with excl_off given)");
   SKGE_CHECK_MODEL(model, d);
+  // |s * r_j - o| has no single query vector against the relation table
+  SKGE_REFUSE_ROTATE(model, "relation prediction");
   SKGE_CHECK_ARG(N > 0 && M >= 1 && d > 0 && d <= 1024 && nq >= 0,
                  "bad sizes (N = %d, M = %d, d = %d <= 1024, nq = %d)", N, M, d, nq);
   SKGE_CHECK_ARG(k >= 1 && k <= TK_KMAX, "k = %d outside 1 .. %d", k, TK_KMAX);

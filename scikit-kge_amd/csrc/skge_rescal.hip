@@ -2096,6 +2096,10 @@ bool rs_small_bucket(int M, int n) { return M <= SB_MAXM && n <= SB_MAXN; }
 static int rescal_front(hipStream_t st, const skge_table_t* ent, const skge_table_t* rel, int d,
                         const int* a, int na, const int* b, int n, const RescalWs& ws,
                         bool bucketed = false) {
+  // every RESCAL step comes through here: its row updates (k_rescal_fold, the W
+  // steps) read any projection but normalize as normless1
+  if (refuses_unitmod(ent, "RESCAL step") || refuses_unitmod(rel, "RESCAL step"))
+    return SKGE_EINVAL;
   const int M = rel->rows;
   if (bucketed) {
     // the epoch's buckets were built up front (rescal_epoch_bucket)

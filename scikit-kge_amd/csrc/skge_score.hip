@@ -13,6 +13,8 @@
 //                     folded with R_p per lane, then the wave sum
 //   k_score_diag      DistMult / ComplEx: E_s . (conj(R_p) * E_o) on rows in
 //                     registers (skge_diag.h), the step kernels' expression
+//   k_score_rot       RotatE: -sum_j |E_s[j] * R_p[j] - E_o[j]| on rows in
+//                     registers (skge_rot.h), the step kernels' expression
 //   k_score_rescal    RESCAL: the triples are grouped by relation on the device
 //                     (launch_pool_group: histogram, scan, scatter); an item is
 //                     up to QB triples of ONE relation, scored by the MFMA
@@ -27,6 +29,7 @@
 #include "skge_elem.h"
 #include "skge_host.h"
 #include "skge_hole.h"
+#include "skge_rot.h"
 #include "skge_pools.h"
 #include "skge_rescal_tile.h"
 #include "skge_transe_l1.h"
@@ -173,6 +176,40 @@ static void launch_score_diag(hipStream_t st, int blocks, const ScoreArgs& a) {
 #undef SKGE_SC_D
 }
 
+// ---- RotatE: the step kernels' score (skge_rot.h), one wave per triple, rows
+// in registers ----
+template <int KM>
+__global__ __launch_bounds__(256) void k_score_rot(ScoreArgs a) {
+  const int wpb = blockDim.x >> 6, d = a.d;
+  for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < a.n; i += gridDim.x * wpb) {
+    const int s = uni(a.trip[3 * (size_t)i]), o = uni(a.trip[3 * (size_t)i + 1]);
+    const int p = uni(a.trip[3 * (size_t)i + 2]);
+    float es[KM], eo[KM], rp[KM], t[KM], u[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, o, d, eo);
+    diag_mul<COMPLEX, KM>(es, rp, t);
+    rot_sub<KM>(t, eo, u);
+    const float sc = -rot_unit<KM>(u);
+    if (lane_id() == 0) a.out[i] = sc;
+  }
+}
+
+static void launch_score_rot(hipStream_t st, int blocks, const ScoreArgs& a) {
+#define SKGE_SC_R(K) \
+  case K: hipLaunchKernelGGL((k_score_rot<K>), dim3(blocks), dim3(256), 0, st, a); break;
+  switch (km_for(a.d)) {
+    SKGE_SC_R(1)
+    SKGE_SC_R(2)
+    SKGE_SC_R(3)
+    SKGE_SC_R(4)
+    SKGE_SC_R(8)
+    default:
+    SKGE_SC_R(16)
+  }
+#undef SKGE_SC_R
+}
+
 // ---- RESCAL ----
 __global__ __launch_bounds__(256) void k_score_rel(const int* __restrict__ trip, int n,
                                                    int* __restrict__ rel) {
@@ -223,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void k_score_rescal(ScoreRescalArgs a) {
 static int score_rescal_qb(int n, int M) { return (long long)n >= 64ll * M ? 128 : 32; }
 
 static bool score_sizes_ok(int model, long long n, int M, int d) {
-  return model_known(model) && (model != SKGE_COMPLEX || d % 2 == 0) && n >= 0 && n <= INT_MAX / 4 && M >= 1 && d >= 1 && d <= 1024;
+  return model_known(model) && (!model_complex_rows(model) || d % 2 == 0) && n >= 0 && n <= INT_MAX / 4 && M >= 1 && d >= 1 && d <= 1024;
 }
 
 }  // namespace skge
@@ -291,6 +328,11 @@ extern "C" int skge_score(void* stream, int model, const float* E, const float* 
       hipLaunchKernelGGL(k_score_hole, dim3(blocks), dim3(256), (size_t)4 * 2 * d * sizeof(float),
                          st, a);
     SKGE_CHECK_LAUNCH("score (HolE)");
+    return SKGE_OK;
+  }
+  if (model == SKGE_ROTATE) {
+    launch_score_rot(st, blocks, a);
+    SKGE_CHECK_LAUNCH("score (RotatE)");
     return SKGE_OK;
   }
   if (model_diag(model)) {

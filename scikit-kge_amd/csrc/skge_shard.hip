@@ -422,6 +422,7 @@ extern "C" int skge_shard_score(void* stream, const skge_table_t* rel, int d, co
                                 const int* req_pos, float margin, void* contrib, int* vshards) {
   int rc;
   if ((rc = check_table(rel, "rel", true))) return rc;
+  if (refuses_unitmod(rel, "sharded runner")) return SKGE_EINVAL;
   SKGE_CHECK_ARG(rel->acc_mode == SKGE_ACC_I16X4 && rel->acc_touched == nullptr &&
                      rel->width == d,
                  "rel: dense packed accumulator of width d needed");
@@ -457,6 +458,7 @@ extern "C" int skge_shard_accum(void* stream, const skge_table_t* ent_shard, int
                                 const void* contrib, int64_t n) {
   int rc;
   if ((rc = check_table(ent_shard, "ent", true))) return rc;
+  if (refuses_unitmod(ent_shard, "sharded runner")) return SKGE_EINVAL;
   SKGE_CHECK_ARG(G >= 1 && G <= SHARD_MAX_RANKS, "G must be 1..%d", SHARD_MAX_RANKS);
   SKGE_CHECK_ARG(ent_shard->acc_mode == SKGE_ACC_I16X4 && ent_shard->acc_touched &&
                      ent_shard->acc_replicas <= 1,

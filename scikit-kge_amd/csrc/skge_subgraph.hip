@@ -402,6 +402,7 @@ extern "C" int skge_subgraph_rank(void* stream, int model, const float* E, const
   SKGE_CHECK_ARG(E && R && X, "NULL table");
   SKGE_CHECK_ARG(queries && skip_tail && skip_head && ans_off && ans_sub && ranks_out && found_out,
                  "NULL argument");
+  SKGE_REFUSE_ROTATE(model, "subgraph ranking");
   SKGE_CHECK_ARG(model >= 0 && model <= 3, "unknown model %d", model);
   SKGE_CHECK_ARG(N > 0 && d > 0 && d <= 1024 && S > 0 && nq >= 0,
                  "bad sizes (S > 0, d <= 1024)");

@@ -225,6 +225,8 @@ void launch_topk_select(hipStream_t st, int model, const float* T, int rows, int
     launch_select<RT_L1>(st, p, a, gather);
   else if (model == SKGE_TRANSE_L2)
     launch_select<RT_L2SQ>(st, p, a, gather);
+  else if (model == SKGE_ROTATE)
+    launch_select<RT_CMOD>(st, p, a, gather);
   else
     launch_select<RT_DOT>(st, p, a, gather);
   launch_list_merge(st, lists, nq, p.ns, k, ent_out, score_out);

@@ -242,6 +242,8 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_ex(
     uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp) {
   if (!ent || !rel) return fail("triple runner: NULL table");
   if (check_sampler(smp, "triple runner")) return nullptr;
+  if (model == SKGE_ROTATE)
+    return fail("triple runner: RotatE is not served here (its scores are <= 0: no logistic loss)");
   if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
     return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
                 "and ComplEx)");
@@ -336,6 +338,8 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_multi(
     const skge_negatives_t* negs) {
   if (!ent || !rel) return fail("triple runner: NULL table");
   if (check_sampler(smp, "triple runner")) return nullptr;
+  if (model == SKGE_ROTATE)
+    return fail("triple runner: RotatE is not served here (its scores are <= 0: no logistic loss)");
   if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
     return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
                 "and ComplEx)");

@@ -96,7 +96,9 @@ __device__ __forceinline__ void update_row(const TableDev& t, int row, const flo
     p[k] = e < w ? pv : 0.0f;
     ss += p[k] * p[k];
   }
-  if (t.post != POST_NONE) {
+  if (t.post == POST_UNITMOD) {
+    unitmod_row<KM>(p);   // every complex component onto the unit circle (skge_device.h)
+  } else if (t.post != POST_NONE) {
     ss = wave_sum(ss);
     const float nrm = t.post == POST_NORMALIZE ? sqrtf(ss)              // param.py:165-166
                                                : (ss < 1.0f ? 1.0f : ss); // param.py:171-173
@@ -197,7 +199,9 @@ __device__ __forceinline__ void apply_row(const TableDev& t, int row, bool upd) 
     p[k] = pv;
     ss += pv * pv;
   }
-  if (t.post != POST_NONE && upd) {
+  if (t.post == POST_UNITMOD && upd) {
+    unitmod_row<KM>(p);
+  } else if (t.post != POST_NONE && upd) {
     ss = wave_sum(ss);
     const float nrm = t.post == POST_NORMALIZE ? sqrtf(ss) : (ss < 1.0f ? 1.0f : ss);
 #pragma unroll
@@ -429,7 +433,9 @@ __device__ __forceinline__ void apply_row_rep_block(const TableDev& t, int row, 
         ss += p[k] * p[k];
       }
     }
-    if (t.post != POST_NONE && upd) {
+    if (MODE != ACC_I16X4 && t.post == POST_UNITMOD && upd) {
+      unitmod_row<KR>(p);   // (packed sums refuse the code on the host: check_unitmod)
+    } else if (t.post != POST_NONE && upd) {
       ss = wave_sum(ss);
       if (MODE == ACC_I16X4) {
         const float inv = proj_scale_fast(t.post, ss);
@@ -940,7 +946,8 @@ extern "C" int skge_update_rows(void* stream, const skge_table_t* t, const float
   if (rc) return rc;
   SKGE_CHECK_ARG(t->opt == SKGE_SGD || t->opt == SKGE_ADAGRAD, "unknown updater %d", t->opt);
   SKGE_CHECK_ARG(t->opt == SKGE_SGD || t->state, "AdaGrad needs state");
-  SKGE_CHECK_ARG(t->post >= 0 && t->post <= 2, "unknown post %d", t->post);
+  SKGE_CHECK_ARG(t->post >= 0 && t->post <= 3, "unknown post %d", t->post);
+  if ((rc = check_unitmod(t))) return rc;
   SKGE_CHECK_ARG(U >= 0, "U < 0");
   if (U == 0) return SKGE_OK;
   SKGE_CHECK_ARG(g && idx, "g/idx NULL");
@@ -1041,7 +1048,8 @@ extern "C" int skge_accum_apply(void* stream, const skge_table_t* tables, int nt
     if (rc) return rc;
     if ((rc = check_slots(t, nslots[i], "table"))) return rc;
     SKGE_CHECK_ARG(t->opt == SKGE_SGD || t->state, "AdaGrad needs state");
-    SKGE_CHECK_ARG(t->post >= 0 && t->post <= 2, "unknown post %d", t->post);
+    SKGE_CHECK_ARG(t->post >= 0 && t->post <= 3, "unknown post %d", t->post);
+    if ((rc = check_unitmod(t))) return rc;
     if (slots_of(i) == 0) continue;
     if (km_for(t->width) == 0) {
       SKGE_CHECK_ARG(t->post == SKGE_POST_NONE, "projection needs width <= 1024");
@@ -1083,6 +1091,9 @@ bool rescal_pair_mfma_selected(int d, int M) { return rescal_use_mfma(d, M); }
 
 extern "C" int skge_step_path(int model, int logistic, int d, int n_rel, int n_items) {
   SKGE_CHECK_ARG(model_known(model), "unknown model %d", model);
+  // RotatE steps run one form (k_pair_grad's register kernel) at every width:
+  // there is no path to report, and the call keeps answering code 7 as it did
+  SKGE_REFUSE_ROTATE(model, "skge_step_path");
   SKGE_CHECK_ARG(!logistic || model == SKGE_HOLE || model == SKGE_RESCAL || model_diag(model),
                  "logistic loss is defined for HolE, RESCAL, DistMult and ComplEx only");
   const int km = d > 0 ? km_for(d) : 0;

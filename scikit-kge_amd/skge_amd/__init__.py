@@ -1,7 +1,7 @@
 """skge_amd -- MI355X-native (HIP/gfx950) scikit-kge training hot path.
 
 Drop-in for skge's model / updater / trainer protocol: TransE, HolE, RESCAL,
-DistMult, ComplEx, StochasticTrainer, PairwiseStochasticTrainer, SGD, AdaGrad,
+DistMult, ComplEx, RotatE, StochasticTrainer, PairwiseStochasticTrainer, SGD, AdaGrad,
 RandomModeSampler, CorruptedSampler, LCWASampler.  Every numeric step runs in libskgehip.so."""
 from .version import __version__
 from .base import Model, StochasticTrainer, PairwiseStochasticTrainer, set_deterministic, deterministic
@@ -10,7 +10,8 @@ from .hole import HolE
 from .rescal import RESCAL
 from .distmult import DistMult
 from .complex import ComplEx
-from .param import Parameter, SGD, AdaGrad, normalize, normless1
+from .rotate import RotatE
+from .param import Parameter, SGD, AdaGrad, normalize, normless1, unitmod
 from .sample import RandomModeSampler, CorruptedSampler, LCWASampler, type_index
 from .eval import (FilteredRankingEval, TransEEval, HolEEval, compute_scores, ranking_scores,
                    relation_ranking_scores, pool_csr, type_pools)

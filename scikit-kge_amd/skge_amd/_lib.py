@@ -16,9 +16,10 @@ LIB_PATH = os.environ.get("SKGE_LIB_PATH") or os.path.join(_HERE, "libskgehip.so
 
 SKGE_TRANSE_L1, SKGE_TRANSE_L2, SKGE_HOLE, SKGE_RESCAL = 0, 1, 2, 3
 SKGE_DISTMULT, SKGE_COMPLEX = 5, 6   # 4 is unassigned (refused everywhere)
+SKGE_ROTATE = 7
 SKGE_AF_LINEAR, SKGE_AF_SIGMOID, SKGE_AF_TANH, SKGE_AF_RELU = 0, 1, 2, 3
 SKGE_SGD, SKGE_ADAGRAD = 0, 1
-SKGE_POST_NONE, SKGE_POST_NORMALIZE, SKGE_POST_NORMLESS1 = 0, 1, 2
+SKGE_POST_NONE, SKGE_POST_NORMALIZE, SKGE_POST_NORMLESS1, SKGE_POST_UNITMOD = 0, 1, 2, 3
 SKGE_ACC_F32, SKGE_ACC_I16X4, SKGE_ACC_I32X2, SKGE_ACC_FX64, SKGE_ACC_I8X4 = 0, 1, 2, 3, 4
 SKGE_SAMPLER_RANDOM, SKGE_SAMPLER_TYPED, SKGE_SAMPLER_LCWA = 0, 1, 2
 # skge_step_path: path | KM << 8

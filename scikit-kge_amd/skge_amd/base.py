@@ -349,6 +349,9 @@ class StochasticTrainer(object):
         self.hyperparams[param_id] = value
 
     def fit(self, xs, ys):
+        if self.model._kernel_model() == L.SKGE_ROTATE:
+            # scores <= 0: the logistic loss needs a gamma offset (not built)
+            raise ValueError("RotatE has no logistic trainer; use PairwiseStochasticTrainer")
         if self.device_loop:
             from .device import (_require_logistic_model, device_sampler_args,
                                  logistic_device_optim)

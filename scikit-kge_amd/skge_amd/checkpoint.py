@@ -39,7 +39,8 @@ from . import actfun as AF
 MODEL_MODULES = {"TransE": "skge.transe", "HolE": "skge.hole", "RESCAL": "skge.rescal",
                  # not reference classes: the same layout under the names the
                  # reference would use, so both round-trip through this module
-                 "DistMult": "skge.distmult", "ComplEx": "skge.complex"}
+                 "DistMult": "skge.distmult", "ComplEx": "skge.complex",
+                 "RotatE": "skge.rotate"}
 _ACTFUNS = ("ActivationFunction", "Linear", "Sigmoid", "Tanh", "ReLU", "Softplus")
 _NUMPY_GLOBALS = {
     ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
@@ -175,10 +176,11 @@ def load_reference(fname):
     from .transe import TransE
     from .distmult import DistMult
     from .complex import ComplEx
+    from .rotate import RotatE
     with open(fname, "rb") as f:
         cname, hp, params, _ = read_reference_state(f)
     cls = {"TransE": TransE, "HolE": HolE, "RESCAL": RESCAL, "DistMult": DistMult,
-           "ComplEx": ComplEx}[cname]
+           "ComplEx": ComplEx, "RotatE": RotatE}[cname]
     m = cls.__new__(cls)
     m.__setstate__({"hyperparams": hp, "params": params})
     return m

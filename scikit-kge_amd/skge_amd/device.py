@@ -716,6 +716,9 @@ class PairLoopRunner(_Runner):
 
 
 def _require_logistic_model(model):
+    if model._kernel_model() == L.SKGE_ROTATE:
+        raise ValueError("RotatE has no logistic trainer: its scores are <= 0, so the loss needs "
+                         "a gamma offset; train it with PairwiseStochasticTrainer")
     if model._kernel_model() not in (L.SKGE_HOLE, L.SKGE_RESCAL, L.SKGE_DISTMULT,
                                      L.SKGE_COMPLEX):
         raise NotImplementedError("%s has no logistic loss in the reference"
@@ -852,8 +855,10 @@ def make_runner(model, updaters, kg, nbatches, seed=0, ntries=100, nviol_total=N
     from .transe import TransE
     from .base import deterministic
     from .distmult import DistMult
-    if isinstance(model, DistMult) and runner in ("pipe", "epoch", "hole_pipe"):
-        # DistMult / ComplEx train on the pair loop only (k_diag_pos)
+    from .rotate import RotatE
+    if isinstance(model, (DistMult, RotatE)) and runner in ("pipe", "epoch", "hole_pipe"):
+        # DistMult / ComplEx / RotatE train on the pair loop only (k_diag_pos,
+        # k_rot_pos)
         raise ValueError("device runner %r is TransE's or HolE's; %s needs 'pairs' (or 'auto')"
                          % (runner, type(model).__name__))
     if runner == "pipe":

@@ -180,7 +180,8 @@ class DataParallelRunner(_PaddedTables, _PipeRunner):
                  capture=None):
         from .transe import TransE
         from .distmult import DistMult
-        if isinstance(model, DistMult):
+        from .rotate import RotatE
+        if isinstance(model, (DistMult, RotatE)):
             raise ValueError("data-parallel runner: TransE-L1 only; %s trains on one device with "
                              "device_runner='pairs'" % type(model).__name__)
         if not isinstance(model, TransE) or not model.l1 or model.d > 1024:

@@ -26,7 +26,8 @@ def _model_code(model):
     from .hole import HolE
     from .rescal import RESCAL
     from .distmult import DistMult
-    if isinstance(model, DistMult):   # ComplEx too: its own code
+    from .rotate import RotatE
+    if isinstance(model, (DistMult, RotatE)):   # ComplEx too: its own code
         return model.model_code, model.params["R"]
     if isinstance(model, TransE):
         return L.SKGE_TRANSE_L1, model.params["R"]
@@ -35,6 +36,15 @@ def _model_code(model):
     if isinstance(model, RESCAL):
         return L.SKGE_RESCAL, model.params["W"]
     raise NotImplementedError("no evaluator for %s" % type(model).__name__)
+
+
+def refuse_rotate(model, what):
+    """ValueError for the questions RotatE is not served with: |s * r_j - o|
+    has no single query vector against the relation table, and the subgraph
+    ranks take the reference's three models."""
+    from .rotate import RotatE
+    if isinstance(model, RotatE):
+        raise ValueError("%s is not served for RotatE" % what)
 
 
 def check_triple_ids(triples, n_ent, n_rel, what="triples"):
@@ -329,6 +339,7 @@ class FilteredRankingEval(object):
         evaluator's order (as ranks()).  A rank is 1 + #relations scoring
         strictly higher; the filtered rank skips every other p' with
         (s, o, p') known.  One ``skge_relrank`` call (csrc/skge_relation.hip)."""
+        refuse_rotate(model, "relation_ranks (relation prediction)")
         code, rel = _model_code(model)
         dev = model.device
         q = [(s, o, p) for p, sos in self.idx.items() for (s, o) in sos]

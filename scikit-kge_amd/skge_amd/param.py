@@ -87,8 +87,33 @@ def normless1(M, idx=None):
     return M
 
 
+def unitmod(M, idx=None):
+    """Every complex component (x[2j], x[2j + 1]) of a row divided by its
+    modulus; a zero component becomes (1, 0).  RotatE's relation table: each
+    component stays a rotation.  Host arrays and device Parameters as
+    normalize."""
+    if isinstance(M, Parameter):
+        return _project_device(M, idx, L.SKGE_POST_UNITMOD)
+    if M.shape[-1] % 2:
+        raise ValueError("unitmod needs an even width, not %d" % M.shape[-1])
+    rows = M if idx is None else M[idx]
+    re, im = rows[..., 0::2], rows[..., 1::2]
+    m = np.sqrt(re * re + im * im)
+    zero = m == 0
+    safe = np.where(zero, 1.0, m)
+    out = np.empty_like(rows)
+    out[..., 0::2] = np.where(zero, 1.0, re / safe)
+    out[..., 1::2] = np.where(zero, 0.0, im / safe)
+    if idx is None:
+        return out
+    M[idx] = out
+    return M
+
+
 POST_CODES = {None: L.SKGE_POST_NONE, normalize: L.SKGE_POST_NORMALIZE,
-              normless1: L.SKGE_POST_NORMLESS1}
+              normless1: L.SKGE_POST_NORMLESS1, unitmod: L.SKGE_POST_UNITMOD}
+# the registry by name (checkpoints, documentation)
+POSTS = {"normalize": normalize, "normless1": normless1, "unitmod": unitmod}
 
 
 def post_code(post):
@@ -96,7 +121,7 @@ def post_code(post):
         return POST_CODES[post]
     except KeyError:
         raise ValueError("unsupported post projection %r (device path supports "
-                         "normalize / normless1)" % (post,))
+                         "normalize / normless1 / unitmod)" % (post,))
 
 
 def _device_init(shape, method, dev):

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .eval import _model_code, check_pool_ids, check_triple_ids, pool_csr, type_pools
+from .eval import _model_code, refuse_rotate, check_pool_ids, check_triple_ids, pool_csr, type_pools
 from .util import triples_array
 
 K_MAX = 128
@@ -72,6 +72,7 @@ class LinkPredictor(object):
         filtered=True excludes every known relation of (s, o); exclude: per
         query an iterable of further relation ids."""
         model = self.model
+        refuse_rotate(model, "LinkPredictor.relations (relation prediction)")
         code, rel = _model_code(model)
         if self.scoring == "model":
             code = model._kernel_model()

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .eval import _model_code, check_triple_ids, compute_scores
+from .eval import _model_code, check_triple_ids, compute_scores, refuse_rotate
 from .util import triples_array
 
 SUBTYPE = Enum("SUBTYPE", "SPO POS")   # skge/subgraphs.py:4
@@ -227,6 +227,7 @@ class SubgraphRankingEval(object):
                 "entities of a scan over all triples per query; it is not carried over")
         if sub_dist not in ("avg", "var"):
             raise ValueError("sub_dist must be 'avg' or 'var', not %r" % (sub_dist,))
+        refuse_rotate(model, "subgraph ranking")
         L.require_gpu()
         code, rel = _model_code(model)
         E = model.params["E"]
