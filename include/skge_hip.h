@@ -59,7 +59,8 @@ enum {
    * d/2 complex components of ComplEx's row layout (d even), TransE's raw
    * pairwise margin loss, every component of R kept on the unit circle by
    * SKGE_POST_UNITMOD.  Served: skge_pair_grad, skge_score, skge_rank_known,
-   * skge_topk, skge_rank_pools, skge_topk_pools and the pair loop runner.
+   * skge_topk, skge_rank_pools, skge_topk_pools, the pair loop runner and the
+   * self-adversarial entry points (skge_sadv_*).
    * Refused with an error that names RotatE: the logistic entry points,
    * skge_relrank / skge_reltopk, skge_subgraph_rank, skge_rank and every
    * pipelined, two-launch, data-parallel and sharded runner. */
@@ -261,7 +262,11 @@ int skge_accum_apply(void *stream, const skge_table_t *tables, int ntables, cons
  * needs a workspace of skge_pair_step_workspace_bytes(model, P, rel->rows, d)
  * bytes (0 for the other models): for d <= 1024 and <= 8192 relations the
  * triples are grouped by relation and W[p] E[o], E[s] W[p] and dW run as fp32
- * MFMA GEMMs (skge_rescal.hip), otherwise as per-pair GEMVs.
+ * MFMA GEMMs (skge_rescal.hip), otherwise as per-pair GEMVs.  The workspace
+ * must hold finite floats on entry (zero it once after allocating; the calls
+ * leave it finite): a skipped pair's stale rows are discarded by a zero
+ * coefficient, which does not discard a NaN.  The same holds for
+ * skge_triple_step; the runners zero their own workspace at create.
  */
 size_t skge_pair_step_workspace_bytes(int model, int P, int M, int d);
 int skge_pair_step(void *stream, int model, int af, const skge_table_t *ent,
@@ -564,6 +569,54 @@ skge_triple_runner_t *skge_triple_runner_create_multi(void *stream, int model,
                                                       int ntries, float *loss_total,
                                                       const skge_sampler_t *smp,
                                                       const skge_negatives_t *negs);
+
+/*
+ * Self-adversarial negative-sampling loss for the distance models (TransE-L1,
+ * TransE-L2, RotatE; phi <= 0), over the records of skge_epoch_sample_multi:
+ * positive j = pos3[j] = (s, o, p) with K = n * nmodes slots negK[j][k], slot k
+ * corrupting position modes[k % nmodes] with the id it holds; a slot holding
+ * -1 is absent (no part in the softmax, the loss, the gradient or the counts).
+ *   L_j   = -log sigmoid(gamma + phi_pos) - sum_k w_k log sigmoid(-(gamma + phi_k))
+ *   w_k   = softmax over the valid slots of alpha * phi_k (max-subtracted); a
+ *           constant: no gradient flows through it.  alpha = 0: 1 / Kv.
+ *   c_pos = -sigmoid(-(gamma + phi_pos)),  c_k = w_k sigmoid(gamma + phi_k)
+ * Each of the 1 + Kv triples of a positive contributes c * d phi / d row to
+ * its rows s, o and p (the model's own directions: TransE's signs /
+ * differences, RotatE's unit vectors) and counts as one occurrence of each;
+ * the apply takes the library's mean over occurrences, then the updater and
+ * the projection.  There is no margin test, no gate and no violation count.
+ * One wave per positive (k_sadv_pos, csrc/skge_grad.hip).  Slot map: ent
+ * (2 + K) j + {0: s, 1: o, 2 + k: slot k's entity}, rel (1 + K) j + {0: p,
+ * 1 + k: slot k's relation}.
+ * skge_sadv_grad: scores, coefficients and accumulators for skge_accum_collect;
+ *   *loss += sum_j L_j; optional outputs pscore [P], nscore [P][K] and coef
+ *   [P][1 + K] (c_pos, then c_k), an absent slot's score and coefficient 0.
+ * skge_sadv_step: the same launch and the apply of both tables (every batch
+ *   steps).
+ * skge_sadv_runner_create: the device loop -- per epoch one
+ *   skge_epoch_sample_multi draw, per batch one launch on the records and one
+ *   apply, the losses added into *loss_total, *epoch_key += 1; (1, {0, 1}) is
+ *   taken too, as K = 2.  Driven by skge_pair_runner_run / _nlaunches / _destroy.
+ * Refused (SKGE_EINVAL / NULL, the text names what is wrong): any other model,
+ * odd d for RotatE, d > 1024, negatives outside skge_negatives_t's bounds,
+ * alpha < 0, non-finite gamma / alpha, packed accumulators, a replicated entity
+ * accumulator, fewer touched slots than the map needs (with the count needed),
+ * SKGE_POST_UNITMOD on a table it cannot serve.
+ */
+int skge_sadv_grad(void *stream, int model, const skge_table_t *ent, const skge_table_t *rel,
+                   int d, const int *pos3, const int *negK, int P, const skge_negatives_t *negs,
+                   float gamma, float alpha, float *pscore, float *nscore, float *coef,
+                   float *loss);
+int skge_sadv_step(void *stream, int model, const skge_table_t *ent, const skge_table_t *rel,
+                   int d, const int *pos3, const int *negK, int P, const skge_negatives_t *negs,
+                   float gamma, float alpha, float *loss);
+skge_pair_runner_t *skge_sadv_runner_create(void *stream, int model, const skge_table_t *ent,
+                                            const skge_table_t *rel, int d, const int *trip,
+                                            int64_t T, const void *set, int64_t set_capacity,
+                                            int nbatches, uint64_t seed, uint64_t *epoch_key,
+                                            float gamma, float alpha, int ntries,
+                                            float *loss_total, const skge_sampler_t *smp,
+                                            const skge_negatives_t *negs);
 
 /*
  * Pipelined epoch runner for TransE-L1 with packed accumulators (the

@@ -1773,6 +1773,323 @@ int launch_transe_pos_multi(hipStream_t st, int l1, const skge_table_t* ent,
 }
 
 // ---------------------------------------------------------------------------
+// Self-adversarial negative-sampling loss, TransE-L1 / -L2 and
+// RotatE: one wave per positive and its K <= 64 slots, straight from
+// k_epoch_sample_multi's records (pos3 [.][3], negK [.][K]; slot k corrupts
+// position modes[k % nmodes] with negK's id, -1: the slot is absent).
+//
+//   L_j = -log sigmoid(gamma + phi_pos) - sum_k w_k log sigmoid(-(gamma + phi_k))
+//   w_k = softmax over the valid slots of alpha phi_k   (a constant: no gradient)
+//   c_pos = -sigmoid(-(gamma + phi_pos))      c_k = w_k sigmoid(gamma + phi_k)
+//
+// Pass 1 scores the positive and every valid slot with the explicit kernels'
+// expressions (transe_pair / rot_pair: the same per-lane chain and wave_sum, so
+// the same bits as skge_pair_grad's scores); lane k keeps phi_k.  The softmax
+// is a wave max, expf, a wave sum; lane k forms c_k.  Pass 2 reads each valid
+// slot's corrupted row a second time, recomputes its triple's directions
+// (rows += c * d phi / d row, in the library's convention: TransE's
+// transe.py:103-121 signs / differences, RotatE's rot_unit w), adds the
+// corrupted row's share to its accumulator and sums the other two positions'
+// shares in registers; s, o and p are then added once each with the
+// positive's share.  No LDS and no K-dependent registers.
+// Every valid triple counts as an occurrence of each of its three rows:
+//   E[s]: 1 + #(valid slots of mode 1, 2)   E[o]: 1 + #(modes 0, 2)
+//   R[p]: 1 + #(modes 0, 1)                 the corrupted row: 1
+// (a corrupted id equal to s or o, or held by two slots, is separate adds and
+// separate counts on one row: the list's occurrences).  Slots: entity
+// (2 + K) j + {0: s, 1: o, 2 + k}, relation (1 + K) j + {0: p, 1 + k}; a slot
+// that adds nothing is -1.  No margin test, no gate, E.violations untouched.
+// ---------------------------------------------------------------------------
+enum SadvForm : int { SADV_L1 = 0, SADV_L2 = 1, SADV_ROT = 2 };
+
+struct SadvArgs {
+  const float* E;
+  const float* R;
+  Accum accE, accR;
+  const int* pos3;   // [.][3]
+  const int* negK;   // [.][K]
+  long long start;   // this batch: positives [start, start + count)
+  int count, d;
+  Negatives ng;
+  float gamma, alpha;
+  float* pscore;     // optional [count]
+  float* nscore;     // optional [count][K], 0 for an absent slot
+  float* coef;       // optional [count][1 + K]: c_pos, then c_k (0 for an absent slot)
+  float* loss;       // optional: += sum_j L_j
+};
+
+// wave_sum's tree with fmaxf: every lane ends with the same maximum
+__device__ __forceinline__ float wave_max(float v) {
+  v = fmaxf(v, dpp_f<0xb1>(v));
+  v = fmaxf(v, dpp_f<0x4e>(v));
+  v = fmaxf(v, dpp_f<0x141>(v));
+  v = fmaxf(v, dpp_f<0x140>(v));
+  return fmaxf(fmaxf(lane_f(v, 0), lane_f(v, 16)), fmaxf(lane_f(v, 32), lane_f(v, 48)));
+}
+
+// -log sigmoid(x) = max(-x, 0) + log1p(exp(-|x|))
+__device__ __forceinline__ float neg_log_sigmoid(float x) {
+  return fmaxf(-x, 0.0f) + log1pf(expf(-fabsf(x)));
+}
+
+// phi of the triple whose rows are (fs, rn, fo)
+template <int KM, int FORM>
+__device__ __forceinline__ float sadv_score(const float (&fs)[KM], const float (&rn)[KM],
+                                            const float (&fo)[KM]) {
+  if constexpr (FORM == SADV_ROT) {
+    float t[KM], u[KM];
+    diag_mul<COMPLEX, KM>(fs, rn, t);
+    rot_sub<KM>(t, fo, u);
+    return -rot_unit<KM>(u);
+  } else {
+    float ns = 0.0f;
+#pragma unroll
+    for (int q = 0; q < KM; ++q) {
+      const float vn = (fs[q] + rn[q]) - fo[q];   // transe.py:32
+      ns += FORM == SADV_L1 ? fabsf(vn) : vn * vn;
+    }
+    return -wave_sum(ns);
+  }
+}
+
+// d phi / d (E_s, E_o, R_p) of that triple, in the library's convention
+template <int KM, int FORM>
+__device__ __forceinline__ void sadv_dirs(const float (&fs)[KM], const float (&rn)[KM],
+                                          const float (&fo)[KM], float (&Ds)[KM], float (&Do)[KM],
+                                          float (&Dp)[KM]) {
+  if constexpr (FORM == SADV_ROT) {
+    float t[KM];
+    diag_mul<COMPLEX, KM>(fs, rn, t);
+    rot_sub<KM>(t, fo, Do);
+    // w; the returned sum of moduli is unused here (pass 1 took the score): its
+    // accumulation and wave_sum have no side effects and are removed as dead code
+    (void)rot_unit<KM>(Do);
+    diag_cmul<COMPLEX, KM>(rn, Do, t);       // conj(r) * w
+    rot_neg<KM>(Ds, t);
+    diag_cmul<COMPLEX, KM>(fs, Do, t);       // conj(s) * w
+    rot_neg<KM>(Dp, t);
+  } else {
+#pragma unroll
+    for (int q = 0; q < KM; ++q) {
+      const float tn = (fo[q] - rn[q]) - fs[q];                  // transe.py:103
+      const float h = FORM == SADV_L1 ? signf_np(tn) : tn;       // transe.py:117 / 121
+      Ds[q] = h;
+      Do[q] = -h;
+      Dp[q] = h;
+    }
+  }
+}
+
+template <int KM, int FORM>
+__global__ __launch_bounds__(256) void k_sadv_pos(SadvArgs a) {
+  const int wave = threadIdx.x >> 6, wpb = blockDim.x >> 6, l = lane_id();
+  const int d = a.d, K = a.ng.K;
+  float lsum = 0.0f;
+  for (int j = blockIdx.x * wpb + wave; j < a.count; j += gridDim.x * wpb) {
+    const long long g = a.start + j;
+    const int* nk = a.negK + g * K;
+    const int s = uni(a.pos3[3 * g]), o = uni(a.pos3[3 * g + 1]), p = uni(a.pos3[3 * g + 2]);
+    float es[KM], rp[KM], eo[KM], cur[KM], nxt[KM];
+    load_row<KM>(a.E, s, d, es);
+    load_row<KM>(a.R, p, d, rp);
+    load_row<KM>(a.E, o, d, eo);
+    int c = uni(nk[0]), mode = slot_mode(a.ng, 0);
+#pragma unroll
+    for (int q = 0; q < KM; ++q) nxt[q] = 0.0f;   // (an absent slot's row is never read)
+    if (c >= 0) load_row<KM>(mode == 2 ? a.R : a.E, c, d, nxt);
+    const float pphi = sadv_score<KM, FORM>(es, rp, eo);
+    // ---- pass 1: lane k keeps phi_k ----
+    float myphi = 0.0f;
+    bool myvalid = false;
+    for (int k = 0; k < K; ++k) {
+      const int ck = c, mk = mode;
+#pragma unroll
+      for (int q = 0; q < KM; ++q) cur[q] = nxt[q];
+      // the next slot's row ahead of this slot's reduction; after the last
+      // slot, pass 2's first
+      const int kn = k + 1 < K ? k + 1 : 0;
+      c = uni(nk[kn]);
+      mode = slot_mode(a.ng, kn);
+      if (c >= 0) load_row<KM>(mode == 2 ? a.R : a.E, c, d, nxt);
+      if (ck < 0) continue;
+      float fs[KM], rn[KM], fo[KM];
+#pragma unroll
+      for (int q = 0; q < KM; ++q) {
+        fs[q] = mk == 0 ? cur[q] : es[q];
+        fo[q] = mk == 1 ? cur[q] : eo[q];
+        rn[q] = mk == 2 ? cur[q] : rp[q];
+      }
+      const float sc = sadv_score<KM, FORM>(fs, rn, fo);
+      if (l == k) {
+        myphi = sc;
+        myvalid = true;
+      }
+    }
+    // ---- softmax over the valid lanes, coefficients, loss ----
+    const float ax = myvalid ? a.alpha * myphi : -INFINITY;
+    const float mx = wave_max(ax);
+    const float ex = myvalid ? expf(ax - mx) : 0.0f;
+    const float Z = wave_sum(ex);
+    const float wk = myvalid ? ex / Z : 0.0f;
+    const float xk = a.gamma + myphi;
+    const float cneg = myvalid ? wk * (1.0f / (1.0f + expf(-xk))) : 0.0f;
+    const float lk = myvalid ? wk * neg_log_sigmoid(-xk) : 0.0f;
+    const float xp = a.gamma + pphi;
+    const float cpos = -(1.0f / (1.0f + expf(xp)));
+    lsum += neg_log_sigmoid(xp) + wave_sum(lk);
+    if (l == 0) {
+      if (a.pscore) a.pscore[j] = pphi;
+      if (a.coef) a.coef[(long long)(1 + K) * j] = cpos;
+    }
+    if (l < K) {
+      if (a.nscore) a.nscore[(long long)K * j + l] = myphi;
+      if (a.coef) a.coef[(long long)(1 + K) * j + 1 + l] = cneg;
+    }
+    // ---- pass 2: the gradients ----
+    const Accum aR = replica(a.accR, g);
+    const long long eb = (long long)(2 + K) * j, rb = (long long)(1 + K) * j;
+    float as[KM], ao[KM], ap[KM], Ds[KM], Do[KM], Dp[KM];
+#pragma unroll
+    for (int q = 0; q < KM; ++q) as[q] = ao[q] = ap[q] = 0.0f;
+    int cs = 1, co = 1, cp = 1;   // the positive, then the slots that keep the position
+    for (int k = 0; k < K; ++k) {
+      const int ck = c, mk = mode;
+#pragma unroll
+      for (int q = 0; q < KM; ++q) cur[q] = nxt[q];
+      if (k + 1 < K) {
+        c = uni(nk[k + 1]);
+        mode = slot_mode(a.ng, k + 1);
+        if (c >= 0) load_row<KM>(mode == 2 ? a.R : a.E, c, d, nxt);
+      }
+      // the corrupted position's own row and slot (the other table's slot is -1)
+      if (l == 0) commit_slot(a.accE, ck, ck >= 0 && mk != 2 ? 1 : 0, (int)(eb + 2 + k));
+      if (l == 1) commit_slot(aR, ck, ck >= 0 && mk == 2 ? 1 : 0, (int)(rb + 1 + k));
+      if (ck < 0) continue;
+      const float cf = lane_f(cneg, k);
+      float fs[KM], rn[KM], fo[KM], x[KM];
+#pragma unroll
+      for (int q = 0; q < KM; ++q) {
+        fs[q] = mk == 0 ? cur[q] : es[q];
+        fo[q] = mk == 1 ? cur[q] : eo[q];
+        rn[q] = mk == 2 ? cur[q] : rp[q];
+      }
+      sadv_dirs<KM, FORM>(fs, rn, fo, Ds, Do, Dp);
+#pragma unroll
+      for (int q = 0; q < KM; ++q) {
+        const float xs = cf * Ds[q], xo = cf * Do[q], xr = cf * Dp[q];
+        x[q] = mk == 0 ? xs : (mk == 1 ? xo : xr);
+        as[q] += mk != 0 ? xs : 0.0f;
+        ao[q] += mk != 1 ? xo : 0.0f;
+        ap[q] += mk != 2 ? xr : 0.0f;
+      }
+      if (mk == 2) acc_row<KM>(aR, ck, x, d);
+      else acc_row<KM>(a.accE, ck, x, d);
+      cs += mk != 0 ? 1 : 0;
+      co += mk != 1 ? 1 : 0;
+      cp += mk != 2 ? 1 : 0;
+    }
+    sadv_dirs<KM, FORM>(es, rp, eo, Ds, Do, Dp);
+#pragma unroll
+    for (int q = 0; q < KM; ++q) {
+      as[q] += cpos * Ds[q];
+      ao[q] += cpos * Do[q];
+      ap[q] += cpos * Dp[q];
+    }
+    acc_row<KM>(a.accE, s, as, d);
+    acc_row<KM>(a.accE, o, ao, d);
+    acc_row<KM>(aR, p, ap, d);
+    if (l == 0) commit_slot(a.accE, s, cs, (int)eb);
+    if (l == 1) commit_slot(a.accE, o, co, (int)(eb + 1));
+    if (l == 2) commit_slot(aR, p, cp, (int)rb);
+  }
+  __shared__ float lds_loss;
+  if (a.loss) block_sum_add(a.loss, lsum, &lds_loss);   // one atomic per workgroup
+}
+
+// what every self-adversarial entry point refuses before any launch; *K = the
+// slots per positive
+int check_sadv(const char* who, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
+               const skge_negatives_t* negs, const skge_sampler_t* smp, float gamma, float alpha,
+               int* K) {
+  SKGE_CHECK_ARG(model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2 || model == SKGE_ROTATE,
+                 "%s: the self-adversarial loss is defined for TransE-L1, TransE-L2 and RotatE "
+                 "(distance scores <= 0); model code %d is none of them", who, model);
+  SKGE_CHECK_ARG(model != SKGE_ROTATE || d % 2 == 0, "%s: RotatE needs an even d (%d)", who, d);
+  SKGE_CHECK_ARG(d >= 1 && km_for(d) != 0, "%s: d=%d unsupported (1..1024)", who, d);
+  SKGE_CHECK_ARG(std::isfinite(gamma) && std::isfinite(alpha),
+                 "%s: gamma %g / alpha %g must be finite", who, (double)gamma, (double)alpha);
+  SKGE_CHECK_ARG(alpha >= 0.0f, "%s: alpha %g must be >= 0", who, (double)alpha);
+  SKGE_CHECK_ARG(ent && rel, "%s: NULL table", who);
+  int rc;
+  if ((rc = check_negatives(negs, smp, rel->rows, who, K))) return rc;
+  if ((rc = check_table(ent, "ent", true)) || (rc = check_table(rel, "rel", true)) ||
+      (rc = check_f32(ent, "ent")) || (rc = check_f32(rel, "rel")) ||
+      (rc = check_single(ent, "ent")) || (rc = check_unitmod(ent)) || (rc = check_unitmod(rel)))
+    return rc;
+  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "%s: table widths %d / %d differ from d %d",
+                 who, ent->width, rel->width, d);
+  return SKGE_OK;
+}
+
+// one batch of the loss: positives [start, start + count) of pos3 / negK
+// (check_sadv first; slots per positive: 2 + K entity, 1 + K relation)
+int launch_sadv_pos(hipStream_t st, int model, const skge_table_t* ent, const skge_table_t* rel,
+                    int d, const int* pos3, const int* negK, long long start, int count,
+                    const Negatives& ng, float gamma, float alpha, float* pscore, float* nscore,
+                    float* coef, float* loss) {
+  int rc;
+  SKGE_CHECK_ARG(pos3 && negK && count >= 0 && start >= 0 && ng.K >= 1 && ng.K <= 64,
+                 "self-adversarial launch: bad argument");
+  SKGE_CHECK_ARG((long long)(2 + ng.K) * count <= INT32_MAX,
+                 "self-adversarial launch: %d positives of %d slots pass 2^31 slot records", count,
+                 ng.K);
+  if ((rc = check_slots(ent, (long long)(2 + ng.K) * count, "ent")) ||
+      (rc = check_slots(rel, (long long)(1 + ng.K) * count, "rel")))
+    return rc;
+  if (count == 0) return SKGE_OK;
+  SadvArgs a = {};
+  a.E = ent->param;
+  a.R = rel->param;
+  a.accE = accum_of(ent);
+  a.accR = accum_of(rel);
+  a.pos3 = pos3;
+  a.negK = negK;
+  a.start = start;
+  a.count = count;
+  a.d = d;
+  a.ng = ng;
+  a.gamma = gamma;
+  a.alpha = alpha;
+  a.pscore = pscore;
+  a.nscore = nscore;
+  a.coef = coef;
+  a.loss = loss;
+  const int blocks = std::max(1, std::min((count + 3) / 4, 8192));
+  const int form = model == SKGE_ROTATE ? SADV_ROT : (model == SKGE_TRANSE_L1 ? SADV_L1 : SADV_L2);
+#define SKGE_SADV(KM)                                                                           \
+  case KM:                                                                                      \
+    if (form == SADV_ROT)                                                                       \
+      hipLaunchKernelGGL((k_sadv_pos<KM, SADV_ROT>), dim3(blocks), dim3(256), 0, st, a);        \
+    else if (form == SADV_L1)                                                                   \
+      hipLaunchKernelGGL((k_sadv_pos<KM, SADV_L1>), dim3(blocks), dim3(256), 0, st, a);         \
+    else                                                                                        \
+      hipLaunchKernelGGL((k_sadv_pos<KM, SADV_L2>), dim3(blocks), dim3(256), 0, st, a);         \
+    break;
+  switch (km_for(d)) {
+    SKGE_SADV(1)
+    SKGE_SADV(2)
+    SKGE_SADV(3)
+    SKGE_SADV(4)
+    SKGE_SADV(8)
+    default:
+    SKGE_SADV(16)
+  }
+#undef SKGE_SADV
+  SKGE_CHECK_LAUNCH("self-adversarial launch");
+  return SKGE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
 template <int MODEL>
@@ -1976,4 +2293,35 @@ extern "C" int skge_rescal_wgrad(void* stream, const skge_table_t* ent, const sk
                      ent->param, accum_of(rel), d, trip_a, coef_a, n_a, trip_b, coef_b, n_b);
   SKGE_CHECK_LAUNCH("rescal wgrad launch");
   return SKGE_OK;
+}
+
+extern "C" int skge_sadv_grad(void* stream, int model, const skge_table_t* ent,
+                              const skge_table_t* rel, int d, const int* pos3, const int* negK,
+                              int P, const skge_negatives_t* negs, float gamma, float alpha,
+                              float* pscore, float* nscore, float* coef, float* loss) {
+  int K = 0;
+  if (int rc = check_sadv("skge_sadv_grad", model, ent, rel, d, negs, nullptr, gamma, alpha, &K))
+    return rc;
+  SKGE_CHECK_ARG(P >= 0, "skge_sadv_grad: P < 0");
+  if (int rc = check_slots(ent, (long long)(2 + K) * P, "ent")) return rc;
+  if (int rc = check_slots(rel, (long long)(1 + K) * P, "rel")) return rc;
+  if (P == 0) return SKGE_OK;
+  SKGE_CHECK_ARG(pos3 && negK, "skge_sadv_grad: pos3 / negK NULL");
+  return launch_sadv_pos(as_stream(stream), model, ent, rel, d, pos3, negK, 0, P,
+                         negatives_of(negs), gamma, alpha, pscore, nscore, coef, loss);
+}
+
+extern "C" int skge_sadv_step(void* stream, int model, const skge_table_t* ent,
+                              const skge_table_t* rel, int d, const int* pos3, const int* negK,
+                              int P, const skge_negatives_t* negs, float gamma, float alpha,
+                              float* loss) {
+  int rc = skge_sadv_grad(stream, model, ent, rel, d, pos3, negK, P, negs, gamma, alpha, nullptr,
+                          nullptr, nullptr, loss);
+  if (rc || P == 0) return rc;
+  const int K = negs->n * negs->nmodes;
+  skge_table_t t[2] = {*ent, *rel};
+  t[0].gate = nullptr;   // every batch steps
+  t[1].gate = nullptr;
+  const int ns[2] = {(2 + K) * P, (1 + K) * P};
+  return skge_accum_apply(stream, t, 2, ns);
 }

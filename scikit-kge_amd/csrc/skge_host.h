@@ -132,7 +132,10 @@ inline int check_table(const skge_table_t* t, const char* name, bool need_acc) {
   SKGE_CHECK_ARG(t->acc_mode != SKGE_ACC_FX64 || (t->width <= 1024 && t->acc_replicas <= 1),
                  "%s: the deterministic (fixed-point) accumulator needs width <= 1024 and one "
                  "copy", name);
-  SKGE_CHECK_ARG(t->acc_mode == SKGE_ACC_F32 || (t->width % 4 == 0 && t->width <= 1024),
+  // (the fixed-point sums are one int64 per element, added and applied element
+  // by element -- acc_row, mean_row, apply_row: any width, bounded above)
+  SKGE_CHECK_ARG(t->acc_mode == SKGE_ACC_F32 || t->acc_mode == SKGE_ACC_FX64 ||
+                     (t->width % 4 == 0 && t->width <= 1024),
                  "%s: packed accumulator needs width %% 4 == 0 and <= 1024", name);
   // packed sums are TransE-L1's exact integer sign sums: no regularisation
   // terms and the occurrence count as the divisor (the packed applies' fast
@@ -282,6 +285,23 @@ int launch_transe_pos_multi(hipStream_t st, int l1, const skge_table_t* ent,
                             const skge_table_t* rel, int d, const int* pos3, const int* negK,
                             long long start, int count, const Negatives& ng, float margin,
                             int* nviol);
+
+// skge_grad.hip: the self-adversarial loss (TransE-L1 / -L2, RotatE), one wave
+// per positive and its K slots (k_sadv_pos).  check_sadv: what every entry
+// point of the loss refuses before any launch, by name (the model, odd d for
+// RotatE, d > 1024, non-finite gamma / alpha, alpha < 0, check_negatives' list,
+// packed sums, a replicated entity table, check_unitmod); *K = n * nmodes.
+// launch_sadv_pos: batch positives [start, start + count) scored, weighted and
+// accumulated (slots per positive: 2 + K entity, 1 + K relation; a smaller
+// table is refused with the count needed); *loss += the batch's loss; pscore
+// [count], nscore [count][K], coef [count][1 + K] optional.
+int check_sadv(const char* who, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
+               const skge_negatives_t* negs, const skge_sampler_t* smp, float gamma, float alpha,
+               int* K);
+int launch_sadv_pos(hipStream_t st, int model, const skge_table_t* ent, const skge_table_t* rel,
+                    int d, const int* pos3, const int* negK, long long start, int count,
+                    const Negatives& ng, float gamma, float alpha, float* pscore, float* nscore,
+                    float* coef, float* loss);
 
 // skge_grad.hip: HolE pairwise, one positive (both of its pairs) per wave
 bool hole_pos_ok(int af, const skge_table_t* ent, const skge_table_t* rel, int d);

@@ -193,7 +193,9 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
   r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
   if (!hpos && !dpos && !tpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
+  // an absent negative by a zero coefficient, which only discards FINITE stale values
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
   if (!r->alloc_ok) return fail("pair runner: device allocation failed");
   int* pos = r->pairs;
   int* neg = r->pairs ? r->pairs + (size_t)T * 6 : nullptr;
@@ -325,7 +327,9 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
   int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
   if (!tpos) r->pairs = (int*)r->alloc((size_t)T * K * 6 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
+  // an absent negative by a zero coefficient, which only discards FINITE stale values
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
   if (!r->alloc_ok) return fail("pair runner: device allocation failed");
   int* pos = r->pairs;
   int* neg = r->pairs ? r->pairs + (size_t)T * K * 3 : nullptr;
@@ -372,6 +376,57 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
       rc = SKGE_EHIP;
     }
   }
+  return r->end_capture(st, rc) ? r.release() : nullptr;
+}
+
+// The self-adversarial loop (TransE-L1 / -L2, RotatE): the
+// multi-negative draw, then per batch ONE k_sadv_pos launch straight on the
+// records and one apply of both tables, without a gate; the batches' losses
+// are added into *loss_total, key + 1 at the epoch's end.  The runner struct
+// is the pair loop's, so run / nlaunches / destroy are shared.
+extern "C" skge_pair_runner_t* skge_sadv_runner_create(
+    void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
+    const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
+    uint64_t seed, uint64_t* epoch_key, float gamma, float alpha, int ntries, float* loss_total,
+    const skge_sampler_t* smp, const skge_negatives_t* negs) {
+  if (check_sampler(smp, "sadv runner")) return nullptr;
+  int K = 0;
+  if (check_sadv("sadv runner", model, ent, rel, d, negs, smp, gamma, alpha, &K)) return nullptr;
+  // a batch's 2 + K entity slots per positive are indexed with ints
+  if (!check_runner_args("sadv runner", trip, set, epoch_key, T, INT32_MAX / (2 + K), nbatches,
+                         set_capacity, 2 * T, ntries, stream))
+    return nullptr;
+  hipStream_t st = as_stream(stream);
+  const EpochBatches batches = epoch_batches(T, nbatches);
+  if (ent->acc_touched && (long long)(2 + K) * batches.maxb > ent->touched_cap)
+    return fail("sadv runner: entity accumulator needs (2 + K) * batch_size = %lld touched slots, "
+                "has %lld", (long long)(2 + K) * batches.maxb, (long long)ent->touched_cap);
+  if (rel->acc_touched && (long long)(1 + K) * batches.maxb > rel->touched_cap)
+    return fail("sadv runner: relation accumulator needs (1 + K) * batch_size = %lld touched "
+                "slots, has %lld", (long long)(1 + K) * batches.maxb, (long long)rel->touched_cap);
+  const int nb = batches.size();
+  std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
+  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
+  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
+  if (!r->alloc_ok) return fail("sadv runner: device allocation failed");
+  const Negatives ng = negatives_of(negs);
+  const TripleSet ts = triple_set_view(set, set_capacity);
+  if (!r->begin_capture(st)) return nullptr;
+  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
+                                     rel->rows, ntries, pos3, negK, smp, negs);
+  for (int k = 0; k < nb && !rc; ++k) {
+    const int count = (int)batches[k].second;
+    rc = launch_sadv_pos(st, model, ent, rel, d, pos3, negK, batches[k].first, count, ng, gamma,
+                         alpha, nullptr, nullptr, nullptr, loss_total);
+    if (!rc) {
+      skge_table_t t[2] = {*ent, *rel};
+      t[0].gate = nullptr;
+      t[1].gate = nullptr;
+      const int ns[2] = {(2 + K) * count, (1 + K) * count};
+      rc = skge_accum_apply(stream, t, 2, ns);
+    }
+  }
+  if (!rc) rc = skge_epoch_advance(stream, epoch_key);
   return r->end_capture(st, rc) ? r.release() : nullptr;
 }
 

@@ -282,7 +282,9 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_ex(
     r->trip = (int*)r->alloc((size_t)T * 9 * sizeof(int), false);
     r->ys = (float*)r->alloc((size_t)T * 3 * sizeof(float), false);
   }
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
+  // an absent negative by a zero coefficient, which only discards FINITE stale values
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
   if (!r->alloc_ok) return fail("triple runner: device allocation failed");
   const TripleSet ts = triple_set_view(set, set_capacity);
   if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
@@ -370,7 +372,9 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_multi(
   int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
   r->trip = (int*)r->alloc((size_t)T * (1 + K) * 3 * sizeof(int), false);
   r->ys = (float*)r->alloc((size_t)T * (1 + K) * sizeof(float), false);
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, false);
+  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
+  // an absent negative by a zero coefficient, which only discards FINITE stale values
+  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
   if (!r->alloc_ok) return fail("triple runner: device allocation failed");
   const TripleSet ts = triple_set_view(set, set_capacity);
   if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture

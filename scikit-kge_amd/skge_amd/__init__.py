@@ -4,7 +4,8 @@ Drop-in for skge's model / updater / trainer protocol: TransE, HolE, RESCAL,
 DistMult, ComplEx, RotatE, StochasticTrainer, PairwiseStochasticTrainer, SGD, AdaGrad,
 RandomModeSampler, CorruptedSampler, LCWASampler.  Every numeric step runs in libskgehip.so."""
 from .version import __version__
-from .base import Model, StochasticTrainer, PairwiseStochasticTrainer, set_deterministic, deterministic
+from .base import (Model, StochasticTrainer, PairwiseStochasticTrainer, SelfAdversarialTrainer,
+                   set_deterministic, deterministic)
 from .transe import TransE
 from .hole import HolE
 from .rescal import RESCAL

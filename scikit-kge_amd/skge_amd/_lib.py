@@ -145,6 +145,11 @@ SIGNATURES = {
                                             c_i, c_u64, c_p, c_f, c_i, c_p, S_P, N_P]),
     "skge_triple_runner_create_multi": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64,
                                               c_i, c_u64, c_p, c_i, c_p, S_P, N_P]),
+    "skge_sadv_grad": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, N_P, c_f, c_f, c_p, c_p, c_p,
+                             c_p]),
+    "skge_sadv_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, N_P, c_f, c_f, c_p]),
+    "skge_sadv_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
+                                      c_p, c_f, c_f, c_i, c_p, S_P, N_P]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,

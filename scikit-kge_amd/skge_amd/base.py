@@ -285,7 +285,9 @@ class Model(object):
             return None
         ws = getattr(self, "_ws", None)
         if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            # zero-filled: RESCAL's kernels multiply the rows of an absent negative by
+            # a zero coefficient, which only discards finite stale values
+            ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
             self._ws = ws
         return ws
 
@@ -300,6 +302,70 @@ class Model(object):
         L.check(lib.skge_triple_step(L.stream_ptr(), self._kernel_model(), te, tr, self.d,
                                      L.ptr(trip), L.ptr(ys), T, L.ptr(ws), nbytes, L.ptr(loss)),
                 "triple_step")
+
+
+    # ---- self-adversarial negative-sampling loss (TransE, RotatE) ----
+    def _require_sadv(self):
+        if self._kernel_model() not in SADV_MODELS:
+            raise ValueError("%s has no self-adversarial loss: it is defined for the distance "
+                             "models TransE and RotatE (scores <= 0); train %s with "
+                             "StochasticTrainer or PairwiseStochasticTrainer"
+                             % (type(self).__name__, type(self).__name__))
+
+    def _sadv_args(self, pos, negK, modes):
+        """Device records and the skge_negatives_t of positives pos [P, 3] =
+        (s, o, p) with their slots negK [P, K]; slot k corrupts position
+        modes[k % len(modes)] with the id it holds, -1: the slot is absent."""
+        from .device import MAX_SLOTS, negatives_struct
+        self._require_sadv()
+        dev = self.device
+        pos = torch.as_tensor(np.asarray(pos.cpu() if torch.is_tensor(pos) else pos),
+                              dtype=torch.int32).reshape(-1, 3).to(dev).contiguous()
+        P = pos.shape[0]
+        negK = torch.as_tensor(np.asarray(negK.cpu() if torch.is_tensor(negK) else negK),
+                               dtype=torch.int32).reshape(P, -1).to(dev).contiguous()
+        K = negK.shape[1]
+        modes = [int(m) for m in modes]
+        if K < 1 or K > MAX_SLOTS or K % len(modes):
+            raise ValueError("self-adversarial loss: K = %d slots per positive; 1 <= K <= %d and a "
+                             "multiple of len(modes) = %d" % (K, MAX_SLOTS, len(modes)))
+        negs = negatives_struct(K // len(modes), modes, self.params[self.rel_id].rows)
+        return pos, negK, P, K, negs
+
+    def _sadv_gradients(self, pos, negK, modes):
+        """Self-adversarial gradients of positives with K slots each (see
+        _sadv_args).  Returns {pid: (grad rows [U, d] fp32,
+        sorted unique idx [U] int64)} -- the mean over each row's occurrences
+        among the 1 + Kv triples of every positive -- and sets self.loss;
+        the scores and coefficients stay in _pscore [P], _nscore [P, K] and
+        _coef [P, 1 + K] (c_pos, then c_k; an absent slot holds 0)."""
+        pos, negK, P, K, negs = self._sadv_args(pos, negK, modes)
+        dev = self.device
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._pscore = torch.empty(P, dtype=torch.float32, device=dev)
+        self._nscore = torch.empty((P, K), dtype=torch.float32, device=dev)
+        self._coef = torch.empty((P, 1 + K), dtype=torch.float32, device=dev)
+        te, tr = self._tables("sadv", slots=((2 + K) * P, (1 + K) * P))
+        L.check(L.lib().skge_sadv_grad(L.stream_ptr(), self._kernel_model(), te, tr, self.d,
+                                       L.ptr(pos), L.ptr(negK), P, negs, float(self.gamma),
+                                       float(self.alpha), L.ptr(self._pscore),
+                                       L.ptr(self._nscore), L.ptr(self._coef), L.ptr(loss)),
+                "sadv_grad")
+        self.loss = float(loss.item())
+        return {"E": self._collect("E", te), self.rel_id: self._collect(self.rel_id, tr)}
+
+    def _sadv_step(self, pos, negK, modes, updaters, loss):
+        """score + coefficients + grad + update in one skge_sadv_step; the
+        batch's loss is added into the device word `loss`."""
+        pos, negK, P, K, negs = self._sadv_args(pos, negK, modes)
+        te, tr = self._tables("sadv", updaters, slots=((2 + K) * P, (1 + K) * P))
+        L.check(L.lib().skge_sadv_step(L.stream_ptr(), self._kernel_model(), te, tr, self.d,
+                                       L.ptr(pos), L.ptr(negK), P, negs, float(self.gamma),
+                                       float(self.alpha), L.ptr(loss)), "sadv_step")
+
+
+# the distance models (scores <= 0) the self-adversarial loss is defined for
+SADV_MODELS = (L.SKGE_TRANSE_L1, L.SKGE_TRANSE_L2, L.SKGE_ROTATE)
 
 
 class StochasticTrainer(object):
@@ -570,3 +636,118 @@ class PairwiseStochasticTrainer(StochasticTrainer):
         if grads is not None:
             self._nviol_host += self.model.nviolations
             self._batch_step(grads)
+
+
+_DEF_GAMMA = 6.0
+_DEF_ALPHA = 1.0
+
+
+class SelfAdversarialTrainer(StochasticTrainer):
+    """Self-adversarial negative-sampling loss for the distance models (TransE,
+    RotatE): per positive j with the K = n * len(modes)
+    negatives its sampler draws,
+
+        L_j = -log sigmoid(gamma + phi_pos) - sum_k w_k log sigmoid(-(gamma + phi_k))
+        w_k = softmax_k(alpha * phi_k), a constant in the gradient
+
+    Every one of the 1 + Kv triples of a positive is an occurrence of its
+    three rows; a row's gradient is the library's mean over its occurrences
+    (not the (pos + neg) / 2 batch mean of other code bases), then the updater
+    and the table's projection.  ``loss`` is the epoch's sum over positives.
+
+    kwargs: ``gamma``, ``alpha`` (stored on the model, as ``margin`` is),
+    ``samplef`` (a Sampler's ``sample``: its ``n`` and ``modes`` fix the slots;
+    required), and StochasticTrainer's.  ``device_loop=True`` runs whole epochs
+    on the device (device.SadvLoopRunner) for RandomModeSampler,
+    CorruptedSampler and LCWASampler over any (n, modes) with K <= 64; any
+    other sampler warns and trains on the per-batch path."""
+
+    def __init__(self, *args, **kwargs):
+        from .device import MAX_SLOTS
+        model = args[0]
+        model._require_sadv()
+        runner = kwargs.pop("device_runner", "auto")
+        if runner != "auto":
+            raise ValueError("SelfAdversarialTrainer on %s: device_runner %r; the loss has one "
+                             "device runner, 'auto' (SadvLoopRunner); the named runners are "
+                             "PairwiseStochasticTrainer's" % (type(model).__name__, runner))
+        gamma = float(kwargs.pop("gamma", _DEF_GAMMA))
+        alpha = float(kwargs.pop("alpha", _DEF_ALPHA))
+        if not (np.isfinite(gamma) and np.isfinite(alpha)) or alpha < 0:
+            raise ValueError("SelfAdversarialTrainer on %s: gamma %r must be finite and alpha %r "
+                             "finite and >= 0" % (type(model).__name__, gamma, alpha))
+        self.device_negatives = True   # the device loop draws any (n, modes): no switch
+        super(SelfAdversarialTrainer, self).__init__(*args, **kwargs)
+        if self.samplef is None:
+            raise ValueError("SelfAdversarialTrainer on %s: samplef is None; the loss weighs the "
+                             "negatives a sampler draws per positive (labelled negatives train "
+                             "with PairwiseStochasticTrainer); pass samplef="
+                             "RandomModeSampler(n, modes, xs, sz).sample" % type(model).__name__)
+        smp = getattr(self.samplef, "__self__", None)
+        try:
+            self._n, self._modes = int(smp.n), [int(m) for m in smp.modes]
+        except (AttributeError, TypeError, ValueError):
+            raise ValueError("SelfAdversarialTrainer on %s: samplef must be the sample method of "
+                             "a sampler with n and modes (they fix a positive's slots)"
+                             % type(model).__name__)
+        K = self._n * len(self._modes)
+        if K < 1 or K > MAX_SLOTS or not 1 <= len(self._modes) <= 8 or \
+                any(m not in (0, 1, 2) for m in self._modes):
+            raise ValueError("SelfAdversarialTrainer on %s: n = %d over modes %r is K = %d "
+                             "negatives per positive; 1 <= K <= %d over 1 to 8 modes from {0, 1, 2} (more "
+                             "negatives train with PairwiseStochasticTrainer)"
+                             % (type(model).__name__, self._n, self._modes, K, MAX_SLOTS))
+        self.model.add_hyperparam("gamma", gamma)
+        self.model.add_hyperparam("alpha", alpha)
+
+    def fit(self, xs, ys):
+        if ys is not None and not np.all(np.asarray(ys) == 1):
+            raise ValueError("SelfAdversarialTrainer on %s: labelled negatives (y != 1); the loss "
+                             "draws its negatives with samplef (labelled negatives train with "
+                             "PairwiseStochasticTrainer)" % type(self.model).__name__)
+        if self.device_loop:
+            from .device import device_sampler_args, sadv_device_optim
+            args = device_sampler_args(self, xs, ys)
+            use_device, ntries, why = args
+            if use_device:
+                sadv_device_optim(self, xs, ntries=ntries, sampler=args.kind,
+                                  negatives=args.negatives)
+                return
+            warnings.warn("device_loop: %s; training on the per-batch path" % why)
+        self._optim(list(zip(xs, [1] * len(xs) if ys is None else ys)))
+
+    def _slots(self, xy):
+        """The K slots of one positive: each negative samplef([xy]) returns goes
+        into the first free slot of the mode of the position it corrupts, in
+        slot order; the rest hold -1."""
+        K = self._n * len(self._modes)
+        slots = [-1] * K
+        x = tuple(int(v) for v in xy[0])
+        for nx, _ in self.samplef([xy]):
+            diff = [m for m in range(3) if int(nx[m]) != x[m]]
+            if len(diff) > 1:
+                raise ValueError("SelfAdversarialTrainer: negative %r corrupts more than one "
+                                 "position of %r" % (tuple(nx), x))
+            want = diff if diff else self._modes   # (equal to the positive: any free slot)
+            k = next((k for k in range(K) if slots[k] < 0 and
+                      self._modes[k % len(self._modes)] in want), None)
+            if k is None:
+                raise ValueError("SelfAdversarialTrainer: samplef returned more negatives for %r "
+                                 "than Sampler(n=%d, modes=%r) has slots"
+                                 % (x, self._n, self._modes))
+            slots[k] = int(nx[self._modes[k % len(self._modes)]])
+        return slots
+
+    def _process_batch(self, xys):
+        pos = np.asarray([xy[0] for xy in xys], dtype=np.int32).reshape(-1, 3)
+        negK = np.asarray([self._slots(xy) for xy in xys], dtype=np.int32)
+        if len(pos) == 0:
+            return
+        if self.fused and self._fusable:
+            if self._loss_dev is None:
+                self._loss_dev = torch.zeros(1, dtype=torch.float32, device=self.model.device)
+            self.model._sadv_step(pos, negK, self._modes, self._updaters, self._loss_dev)
+            return
+        grads = self.model._sadv_gradients(pos, negK, self._modes)
+        self.loss += self.model.loss
+        self._batch_step(grads)

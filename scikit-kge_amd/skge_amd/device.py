@@ -763,6 +763,54 @@ class LogisticLoopRunner(_Runner):
                      create="skge_triple_runner_create_ex")
 
 
+class SadvLoopRunner(_Runner):
+    """Native hipGraph epoch of the self-adversarial loss for TransE and RotatE
+    (skge_sadv_runner_create, csrc/skge_pairloop.hip): the epoch's permutation
+    and its K = n * len(modes) negatives per positive drawn on the device (the
+    _multi draw of the other loops, so (n, modes) may be anything with K <= 64,
+    (1, [0, 1]) included as K = 2), then per batch one k_sadv_pos launch
+    straight on the records -- scores, softmax weights, coefficients,
+    contributions -- and one apply of both tables.  A device epoch trains like
+    feeding epoch_records_multi's records batch by batch to model._sadv_step.
+    The epoch's loss is added into ``loss_total``; updateCounts are kept as on
+    the per-batch path."""
+
+    counters = True
+    _who = "sadv-loop runner"
+
+    def __init__(self, model, updaters, kg, nbatches, seed=0, ntries=100, stream=None,
+                 loss_total=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
+        model._require_sadv()
+        self._setup(model, kg, nbatches, seed, ntries, stream, sampler, negatives)
+        if self._neg is None:
+            self._neg = negatives_struct(1, [0, 1], model.sz[2])
+        self.loss_total = self._total(loss_total, torch.float32)
+        B = max(batch_sizes(kg.T, nbatches))
+        self.te, self.tr = model._tables("sadv", updaters,
+                                         slots=((2 + self.K) * B, (1 + self.K) * B))
+        self._hold_captured(updaters)
+        self._create("skge_pair_runner", model._kernel_model(), self.te, self.tr, model.d,
+                     *self._epoch_args(), float(model.gamma), float(model.alpha), self.ntries,
+                     L.ptr(self.loss_total), self._smp, self._neg,
+                     create="skge_sadv_runner_create")
+
+
+def sadv_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
+    """SelfAdversarialTrainer.fit with device_loop=True: per epoch _pre_epoch,
+    one graph replay, the runner's error word, then the post_epoch callbacks
+    (which read the epoch's loss through trainer.loss)."""
+    model = trainer.model
+    dev = model.device
+    if trainer._loss_dev is None:
+        trainer._loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+    kg = DeviceKG(xs, dev)
+    runner = SadvLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
+                            ntries=trainer.ntries if ntries is None else ntries,
+                            loss_total=trainer._loss_dev, sampler=sampler, negatives=negatives)
+    trainer.batch_size = kg.T // trainer.nbatches
+    _fit_epochs(trainer, runner)
+
+
 def _fit_epochs(trainer, runner):
     """The device fits' epoch loop: per epoch _pre_epoch, one graph replay, the
     runner's error word (read before the post_epoch callbacks, so no callback
