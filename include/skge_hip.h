@@ -619,6 +619,53 @@ skge_pair_runner_t *skge_sadv_runner_create(void *stream, int model, const skge_
                                             const skge_negatives_t *negs);
 
 /*
+ * KvsAll (1-N) training of SKGE_DISTMULT and SKGE_COMPLEX: B queries (anchor
+ * q_anchor[b], relation q_rel[b], direction q_dir[b]: 0 asks for the tails of
+ * (a, p, ?), 1 for the heads of (?, p, a)), each scored against EVERY entity
+ * row, with binary cross-entropy against its known answers ans_ids[ans_off[b]
+ * .. ans_off[b + 1]) (a device CSR; ids outside [0, N) are ignored):
+ *   q_b  = the query vector of skge_rank / skge_topk (DistMult E_a o R_p;
+ *          ComplEx E_a R_p for tails, conj(R_p) E_a for heads)
+ *   z_be = q_b . E_e
+ *   y'_be = (1 - smoothing) [e answers b] + smoothing / N
+ *   L    = (1 / B) sum_b sum_e -(y' log sigma(z) + (1 - y') log(1 - sigma(z)))
+ * The model's activation plays no part.  The gradient is the plain gradient
+ * of L -- no mean over a row's occurrences: every entity row occurs in every
+ * query, and the anchors' and relations' chain-rule terms are summed.
+ * Launches (csrc/skge_kvsall.hip): the query vectors, the answers' bitmap,
+ * three fp32 MFMA products (Z = Q E^T with the loss epilogue writing G =
+ * (sigma(z) - y') / B; dq = G E over slices of the entities; gE = G^T Q), the
+ * chain rule (float atomics into gE[a] and gR[p]) and the loss's fixed-order
+ * sum.
+ * skge_kvsall_grad: gE [N][d] (every row written), gR [M][d] and r_touched
+ *   [M] (zeroed first; a relation row no query names stays exactly 0 and
+ *   unmarked, a named one is marked 1), *loss += L; scores (optional, tests)
+ *   receives z [B][N].  No regulariser.
+ * skge_kvsall_step: the same, then the tables' updater and projection (opt,
+ *   lr, state, post, upd_count) with g + (rin + rout) * param on EVERY entity
+ *   row and on the marked relation rows; an unmarked relation row keeps its
+ *   bits, state included.  The accumulator fields, fixed_div and gate are not
+ *   used.  No device-to-host copy and no synchronisation.
+ * A query naming a row outside its table scores as the zero vector and has no
+ * chain-rule term.  workspace: skge_kvsall_workspace_bytes (0 for arguments
+ * the entry points refuse), 16-byte aligned; B * N is indexed in size_t.
+ * Refused, the text naming what was asked: a model code other than 5 / 6
+ * (0..3 and 7: SKGE_ENOTSUP, by name; 4 and anything else: SKGE_EINVAL),
+ * B > 4096 or d > 1024 (SKGE_ENOTSUP), sizes < 1, odd d for ComplEx,
+ * smoothing outside [0, 1), NULL arguments, a short workspace (SKGE_EINVAL).
+ */
+size_t skge_kvsall_workspace_bytes(int model, int B, int N, int M, int d);
+int skge_kvsall_grad(void *stream, int model, const float *E, const float *R, int N, int M,
+                     int d, const int *q_anchor, const int *q_rel, const int *q_dir, int B,
+                     const int *ans_off, const int *ans_ids, float smoothing, float *gE,
+                     float *gR, int *r_touched, float *loss, float *scores, void *workspace,
+                     size_t ws_bytes);
+int skge_kvsall_step(void *stream, int model, const skge_table_t *ent, const skge_table_t *rel,
+                     int d, const int *q_anchor, const int *q_rel, const int *q_dir, int B,
+                     const int *ans_off, const int *ans_ids, float smoothing, float *loss,
+                     void *workspace, size_t ws_bytes);
+
+/*
  * Pipelined epoch runner for TransE-L1 with packed accumulators (the
  * throughput path).  Same result, bit for bit, as skge_runner_create's loop
  * with the same tables and arguments: all negatives of an epoch are drawn in

@@ -1,0 +1,540 @@
+// KvsAll (1-N) training of DistMult and ComplEx: every query (anchor a,
+// relation p, direction t) of a batch is scored against EVERY entity row and
+// takes binary cross-entropy against the multi-hot vector of its known answers
+// (include/skge_hip.h, skge_kvsall_grad).  With the query vector
+// q = query_elem(model, t == 0, E_a, R_p) (skge_elem.h) the score of candidate
+// e is the plain dot product z = q . E_e, so one batch is three fp32 GEMMs:
+//   k_kv_query    Q [B][d], one wave per query
+//   k_kv_labels   the answers' CSR into a bitmap [B][ceil(N / 32)]
+//   k_kv_gemm<FWD>  Z = Q E^T in 128 x 128 tiles; the epilogue takes sigma, the
+//                 smoothed label and the loss term on the accumulators and
+//                 writes G = (sigma(z) - y') / B (and z, when asked for)
+//   k_kv_gemm<DQ>   dq = G E, the contraction over the entities cut into
+//                 slices: partial tiles [ns][B][d]
+//   k_kv_gemm<DE>   gE = G^T Q, every row, plain stores
+//   k_kv_chain    one wave per query: dq_b = the slices' partials in slice
+//                 order, then the chain rule into gE[a] and gR[p] (float
+//                 atomics) and the mark of R row p
+//   k_kv_loss     the workgroups' loss partials, in block order, into *loss
+// and skge_kvsall_step follows them with the row updates of skge_update.hip
+// (launch_update_table: E every row, R the marked rows).
+//
+// One tile kernel serves the three products.  An operand is read either in ROW
+// form (the contraction index runs along its rows: Q and E in FWD, G in DQ) and
+// transposed on its way into LDS, as k_nb_select stages its images
+// (skge_neighbours.hip), or in K-MAJOR form (the contraction index is its row
+// index: E in DQ, G and Q in DE) and stored as loaded.  Either way the LDS
+// image is k-major and a lane reads one dword per MFMA operand.
+#include <algorithm>
+#include <type_traits>
+
+#include "skge_elem.h"
+#include "skge_host.h"
+#include "skge_stage.h"
+
+namespace skge {
+
+int launch_update_table(hipStream_t st, const skge_table_t* t, const float* g, const int* mask);
+
+constexpr int KV_T = 128;            // output rows and columns per tile
+constexpr int KV_KC = 32;            // contraction indices per LDS chunk
+constexpr int KV_PAD_ROW = KV_T + 1; // transposed image: scalar stores, lanes along the rows
+constexpr int KV_PAD_KM = KV_T + 4;  // k-major image: 16-byte stores
+constexpr int KV_BMAX = 4096;
+constexpr int KV_DMAX = 1024;
+
+enum { KV_FWD = 0, KV_DQ = 1, KV_DE = 2 };
+
+struct KvGemm {
+  const float* A;        // ROW form [Mr][lda] / K-MAJOR form [K][lda]
+  const float* B;        // ROW form [Nc][ldb] / K-MAJOR form [K][ldb]
+  size_t lda, ldb;
+  int Mr, Nc, K;         // output rows, output columns, contraction length
+  int kslice;            // contraction indices per slice (multiple of KV_KC); DQ only
+  unsigned nbx;          // tiles along the output rows (the grid is flat)
+  float* C;              // DQ: partials [ns][Mr][Nc]; DE: gE [Mr][Nc]
+  // FWD
+  float* G;              // [Mr][ldg]
+  size_t ldg;
+  float* scores;         // optional [Mr][Nc]
+  const unsigned* bits;  // [Mr][wpr] answer bitmap
+  int wpr;
+  float eps, eps_n, inv_b;   // smoothing, smoothing / N, 1 / B
+  float* lpart;          // [grid] loss partials
+};
+
+// ---- query vectors: one wave per query ----
+// A query naming a row outside its table scores as the zero vector and takes
+// no part in the chain rule (k_kv_chain): nothing is read or written out of
+// bounds for it.
+__device__ __forceinline__ bool kv_query_ok(int a, int p, int t, int N, int M) {
+  return a >= 0 && a < N && p >= 0 && p < M && (t == 0 || t == 1);
+}
+
+__global__ __launch_bounds__(256) void k_kv_query(int model, const float* __restrict__ E,
+                                                  const float* __restrict__ R, int N, int M, int d,
+                                                  const int* __restrict__ qa,
+                                                  const int* __restrict__ qp,
+                                                  const int* __restrict__ qt, int B,
+                                                  float* __restrict__ Q) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (b >= B) return;
+  const int a = qa[b], p = qp[b], t = qt[b];
+  const bool ok = kv_query_ok(a, p, t, N, M);
+  const float* ea = E + (size_t)(ok ? a : 0) * d;
+  const float* rp = R + (size_t)(ok ? p : 0) * d;
+  for (int k = l; k < d; k += 64)
+    Q[(size_t)b * d + k] = ok ? query_elem(model, t == 0, ea, rp, nullptr, d, k) : 0.0f;
+}
+
+// ---- labels: bit e of row b is set when e answers query b ----
+__global__ __launch_bounds__(256) void k_kv_labels(const int* __restrict__ off,
+                                                   const int* __restrict__ ids, int B, int N,
+                                                   int wpr, unsigned* __restrict__ bits) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (b >= B) return;
+  const int beg = off[b], end = off[b + 1];
+  for (int i = beg + l; i < end; i += 64) {
+    const int e = ids[i];
+    if (e >= 0 && e < N) atomicOr(bits + (size_t)b * wpr + (e >> 5), 1u << (e & 31));
+  }
+}
+
+// ---- the tile kernel ----
+// The four waves tile the 128 x 128 block 2 x 2, each wave 2 x 2 MFMA tiles of
+// 32 x 32: lane l feeds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]
+// and holds D[i = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][j = l & 31].  A 32 x 32
+// tile that lies wholly past the output's edge is not computed (wave-uniform).
+// Staging: ROW form, thread = 16 bytes of a row's 128-byte chunk, 8 lanes a
+// row, four rows 32 apart; K-MAJOR form, thread = 16 bytes of one contraction
+// index's 512-byte run, four pieces 32 columns apart.  LDS: 2 x 32 x 132
+// dwords at most = 33 KB.
+template <bool AKM, bool BKM, int EPI>
+__global__ __launch_bounds__(256, 2) void k_kv_gemm(KvGemm a) {
+  constexpr int PADA = AKM ? KV_PAD_KM : KV_PAD_ROW, PADB = BKM ? KV_PAD_KM : KV_PAD_ROW;
+  __shared__ __attribute__((aligned(16))) float sA[KV_KC * PADA];
+  __shared__ __attribute__((aligned(16))) float sB[KV_KC * PADB];
+  __shared__ float s_loss[4];
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, h = l >> 5;
+  const int wq = w >> 1, wt = w & 1;
+  const unsigned bx = blockIdx.x % a.nbx, by = blockIdx.x / a.nbx;
+  int m0, n0, kbeg, kend, slice = 0;
+  if (EPI == KV_DQ) {   // by = column tile + column tiles * slice
+    const unsigned nty = (unsigned)((a.Nc + KV_T - 1) / KV_T);
+    slice = (int)(by / nty);
+    m0 = (int)bx * KV_T;
+    n0 = (int)(by % nty) * KV_T;
+    kbeg = slice * a.kslice;
+    kend = a.K - kbeg < a.kslice ? a.K : kbeg + a.kslice;
+  } else {
+    m0 = (int)bx * KV_T;
+    n0 = (int)by * KV_T;
+    kbeg = 0;
+    kend = a.K;
+  }
+  const int st_r = tid >> 3, st_c = (tid & 7) * 4;
+  // ROW form needs 16-byte rows for the one-load path; K-MAJOR form too
+  const bool veca = (a.lda & 3) == 0, vecb = (a.ldb & 3) == 0;
+  // this wave's 32 x 32 tiles that hold any output
+  bool am[2], bn[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    am[i] = m0 + wq * 64 + 32 * i < a.Mr;
+    bn[i] = n0 + wt * 64 + 32 * i < a.Nc;
+  }
+  const int ai0 = wq * 64 + (l & 31), bj0 = wt * 64 + (l & 31);
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][nj][r] = 0.0f;
+  for (int k0 = kbeg; k0 < kend; k0 += KV_KC) {
+    float4 ra[4], rb[4];
+    auto load = [&](auto va, auto vb) {
+      constexpr bool VA = decltype(va)::value, VB = decltype(vb)::value;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (AKM) {   // contraction index k0 + st_r, output rows m0 + st_c + 32 u ..
+          const int k = k0 + st_r;
+          ra[u] = stage_load4<VA>(a.A + (size_t)(k < kend ? k : kbeg) * a.lda, k < kend,
+                                  m0 + st_c + 32 * u, a.Mr);
+        } else {     // output row m0 + st_r + 32 u, contraction indices k0 + st_c ..
+          const int m = m0 + st_r + 32 * u;
+          ra[u] = stage_load4<VA>(a.A + (size_t)(m < a.Mr ? m : 0) * a.lda, m < a.Mr, k0 + st_c,
+                                  kend);
+        }
+        if (BKM) {
+          const int k = k0 + st_r;
+          rb[u] = stage_load4<VB>(a.B + (size_t)(k < kend ? k : kbeg) * a.ldb, k < kend,
+                                  n0 + st_c + 32 * u, a.Nc);
+        } else {
+          const int n = n0 + st_r + 32 * u;
+          rb[u] = stage_load4<VB>(a.B + (size_t)(n < a.Nc ? n : 0) * a.ldb, n < a.Nc, k0 + st_c,
+                                  kend);
+        }
+      }
+    };
+    if (veca && vecb)
+      load(std::true_type(), std::true_type());
+    else if (veca)
+      load(std::true_type(), std::false_type());
+    else if (vecb)
+      load(std::false_type(), std::true_type());
+    else
+      load(std::false_type(), std::false_type());
+    __syncthreads();   // the previous chunk's reads are done
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (AKM) {
+        *reinterpret_cast<float4*>(sA + st_r * PADA + st_c + 32 * u) = ra[u];
+      } else {
+        float* p = sA + st_c * PADA + st_r + 32 * u;
+        p[0] = ra[u].x;
+        p[PADA] = ra[u].y;
+        p[2 * PADA] = ra[u].z;
+        p[3 * PADA] = ra[u].w;
+      }
+      if (BKM) {
+        *reinterpret_cast<float4*>(sB + st_r * PADB + st_c + 32 * u) = rb[u];
+      } else {
+        float* p = sB + st_c * PADB + st_r + 32 * u;
+        p[0] = rb[u].x;
+        p[PADB] = rb[u].y;
+        p[2 * PADB] = rb[u].z;
+        p[3 * PADB] = rb[u].w;
+      }
+    }
+    __syncthreads();
+    // two contraction indices per MFMA; an odd tail's second is zero padding
+    const int steps = (min(KV_KC, kend - k0) + 1) >> 1;
+    float av[2], bv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      av[i] = sA[h * PADA + ai0 + 32 * i];
+      bv[i] = sB[h * PADB + bj0 + 32 * i];
+    }
+    for (int s = 0; s < steps; ++s) {
+      // the next step's operands are read while this step's MFMAs run
+      const int kn = 2 * min(s + 1, steps - 1) + h;
+      float an[2], bnx[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        an[i] = sA[kn * PADA + ai0 + 32 * i];
+        bnx[i] = sB[kn * PADB + bj0 + 32 * i];
+      }
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int nj = 0; nj < 2; ++nj)
+          if (am[mi] && bn[nj])
+            acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi], bv[nj], acc[mi][nj], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        av[i] = an[i];
+        bv[i] = bnx[i];
+      }
+    }
+  }
+  // ---- epilogue ----
+  float lsum = 0.0f;
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj) {
+      if (!(am[mi] && bn[nj])) continue;
+      const int j = n0 + bj0 + 32 * nj;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = m0 + wq * 64 + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (i >= a.Mr || j >= a.Nc) continue;
+        const float z = acc[mi][nj][r];
+        if (EPI == KV_FWD) {
+          // j - (l & 31) is a multiple of 32: one bitmap word per row and tile
+          const unsigned word = a.bits[(size_t)i * a.wpr + (j >> 5)];
+          const float y = (word >> (j & 31)) & 1u ? (1.0f - a.eps) + a.eps_n : a.eps_n;
+          // softplus(z) - y z = -(y log sigma(z) + (1 - y) log(1 - sigma(z)))
+          const float e = expf(-fabsf(z));
+          const float sig = z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+          lsum += (fmaxf(z, 0.0f) + log1pf(e)) - y * z;
+          a.G[(size_t)i * a.ldg + j] = (sig - y) * a.inv_b;
+          if (a.scores) a.scores[(size_t)i * a.Nc + j] = z;
+        } else if (EPI == KV_DQ) {
+          a.C[((size_t)slice * a.Mr + i) * a.Nc + j] = z;
+        } else {
+          a.C[(size_t)i * a.Nc + j] = z;
+        }
+      }
+    }
+  if (EPI == KV_FWD) {   // the workgroup's loss partial: lanes, then waves 0..3
+    lsum = wave_sum(lsum);
+    if (l == 0) s_loss[w] = lsum;
+    __syncthreads();
+    if (tid == 0) a.lpart[blockIdx.x] = ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3];
+  }
+}
+
+// ---- chain rule: one wave per query ----
+// dq_b = sum over the slices, in slice order, of the DQ partials; then
+//   DistMult        gE[a] += dq o R_p           gR[p] += dq o E_a
+//   ComplEx tails   gE[a] += dq conj(R_p)       gR[p] += dq conj(E_a)
+//   ComplEx heads   gE[a] += dq R_p             gR[p] += conj(dq) E_a
+// (o elementwise, the rest complex products over (x[2j], x[2j + 1])).
+__global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __restrict__ E,
+                                                  const float* __restrict__ R, int N, int M, int d,
+                                                  const int* __restrict__ qa,
+                                                  const int* __restrict__ qp,
+                                                  const int* __restrict__ qt, int B,
+                                                  const float* __restrict__ part, int ns,
+                                                  float* __restrict__ gE, float* __restrict__ gR,
+                                                  int* __restrict__ r_touched) {
+  __shared__ float s_dq[4][KV_DMAX];
+  const int w = threadIdx.x >> 6, l = lane_id();
+  const int b = blockIdx.x * 4 + w;
+  const bool live = b < B;
+  const int a = live ? qa[b] : -1, p = live ? qp[b] : -1, t = live ? qt[b] : 0;
+  const bool ok = live && kv_query_ok(a, p, t, N, M);
+  if (ok) {
+    for (int k = l; k < d; k += 64) {
+      float s = 0.0f;
+      for (int sl = 0; sl < ns; ++sl) s += part[((size_t)sl * B + b) * d + k];
+      s_dq[w][k] = s;
+    }
+  }
+  __syncthreads();
+  if (!ok) return;
+  const float* ea = E + (size_t)a * d;
+  const float* rp = R + (size_t)p * d;
+  float* ge = gE + (size_t)a * d;
+  float* gr = gR + (size_t)p * d;
+  const float* dq = s_dq[w];
+  for (int k = l; k < d; k += 64) {
+    float va, vr;
+    if (model == SKGE_DISTMULT) {
+      va = dq[k] * rp[k];
+      vr = dq[k] * ea[k];
+    } else {
+      const int kp = k ^ 1;
+      const bool im = k & 1, tail = t == 0;
+      if (tail) {   // dq conj(x): re dq.re x.re + dq.im x.im, im dq.im x.re - dq.re x.im
+        va = im ? fmaf(dq[k], rp[kp], -(dq[kp] * rp[k])) : fmaf(dq[k], rp[k], dq[kp] * rp[kp]);
+        vr = im ? fmaf(dq[k], ea[kp], -(dq[kp] * ea[k])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
+      } else {      // dq r: re dq.re r.re - dq.im r.im, im dq.re r.im + dq.im r.re
+        va = im ? fmaf(dq[kp], rp[k], dq[k] * rp[kp]) : fmaf(dq[k], rp[k], -(dq[kp] * rp[kp]));
+        // conj(dq) a: re dq.re a.re + dq.im a.im, im dq.re a.im - dq.im a.re
+        vr = im ? fmaf(dq[kp], ea[k], -(dq[k] * ea[kp])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
+      }
+    }
+    atomicAdd(ge + k, va);
+    atomicAdd(gr + k, vr);
+  }
+  if (l == 0) r_touched[p] = 1;
+}
+
+// ---- the loss: the partials in block order, one workgroup ----
+__global__ __launch_bounds__(256) void k_kv_loss(const float* __restrict__ lpart, unsigned n,
+                                                 float inv_b, float* __restrict__ loss) {
+  __shared__ double s[256];
+  double v = 0.0;
+  for (unsigned i = threadIdx.x; i < n; i += 256) v += (double)lpart[i];
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss += (float)(s[0] * (double)inv_b);
+}
+
+// ---- plan and workspace ----
+struct KvPlan {
+  size_t ldg;            // G's row pitch: N rounded up to 4 (16-byte rows)
+  int wpr;               // bitmap words per query
+  unsigned nbx, nby;     // FWD tiles
+  int kslice, ns;        // DQ slices of the entities
+  size_t o_q, o_bits, o_g, o_part, o_lpart, o_ge, o_gr, o_touched, total;
+};
+
+static KvPlan kv_plan(int B, int N, int M, int d) {
+  KvPlan p;
+  p.ldg = ((size_t)N + 3) & ~(size_t)3;
+  p.wpr = (int)(((long long)N + 31) / 32);
+  p.nbx = (unsigned)((B + KV_T - 1) / KV_T);
+  p.nby = (unsigned)(((long long)N + KV_T - 1) / KV_T);
+  // DQ: about 512 workgroups, the partials at most 16 MB
+  const long long tiles = (long long)p.nbx * ((d + KV_T - 1) / KV_T);
+  const long long chunks = ((long long)N + KV_KC - 1) / KV_KC;
+  const long long cap = std::max<long long>(1, (16ll << 20) / ((long long)B * d * 4));
+  const long long want = std::max<long long>(1, std::min({chunks, (512 + tiles - 1) / tiles, cap}));
+  const long long per = (chunks + want - 1) / want;
+  p.kslice = (int)std::min<long long>(per * KV_KC, 1ll << 30);
+  p.ns = (int)((chunks + per - 1) / per);
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  p.o_q = take((size_t)B * d * sizeof(float));
+  p.o_bits = take((size_t)B * p.wpr * sizeof(unsigned));
+  p.o_g = take((size_t)B * p.ldg * sizeof(float));
+  p.o_part = take((size_t)p.ns * B * d * sizeof(float));
+  p.o_lpart = take((size_t)p.nbx * (size_t)p.nby * sizeof(float));
+  p.o_ge = take((size_t)N * d * sizeof(float));
+  p.o_gr = take((size_t)M * d * sizeof(float));
+  p.o_touched = take((size_t)M * sizeof(int));
+  p.total = o;
+  return p;
+}
+
+static const char* kv_model_name(int model) {
+  switch (model) {
+    case SKGE_TRANSE_L1: return "TransE-L1";
+    case SKGE_TRANSE_L2: return "TransE-L2";
+    case SKGE_HOLE: return "HolE";
+    case SKGE_RESCAL: return "RESCAL";
+    case SKGE_ROTATE: return "RotatE";
+    default: return "?";
+  }
+}
+
+// what both entry points refuse before any launch
+static int kv_check(const char* who, int model, int N, int M, int d, int B, float smoothing) {
+  SKGE_CHECK_ARG(model_known(model), "%s: unknown model %d", who, model);
+  if (!model_diag(model)) {
+    set_error("%s: model %d (%s) is not served: KvsAll scores a query against every entity with "
+              "one dot product, which DistMult and ComplEx allow", who, model,
+              kv_model_name(model));
+    return SKGE_ENOTSUP;
+  }
+  SKGE_CHECK_ARG(N >= 1 && M >= 1 && d >= 1 && B >= 1, "%s: bad sizes (N = %d, M = %d, d = %d, "
+                 "B = %d)", who, N, M, d, B);
+  if (B > KV_BMAX || d > KV_DMAX) {
+    set_error("%s: B = %d, d = %d outside B <= %d, d <= %d", who, B, d, KV_BMAX, KV_DMAX);
+    return SKGE_ENOTSUP;
+  }
+  SKGE_CHECK_ARG(model != SKGE_COMPLEX || d % 2 == 0, "%s: ComplEx needs an even d (%d)", who, d);
+  SKGE_CHECK_ARG(smoothing >= 0.0f && smoothing < 1.0f, "%s: label smoothing %g outside [0, 1)",
+                 who, (double)smoothing);
+  return SKGE_OK;
+}
+
+}  // namespace skge
+
+using namespace skge;
+
+extern "C" size_t skge_kvsall_workspace_bytes(int model, int B, int N, int M, int d) {
+  if (kv_check("skge_kvsall_workspace_bytes", model, N, M, d, B, 0.0f) != SKGE_OK) return 0;
+  return kv_plan(B, N, M, d).total;
+}
+
+extern "C" int skge_kvsall_grad(void* stream, int model, const float* E, const float* R, int N,
+                                int M, int d, const int* q_anchor, const int* q_rel,
+                                const int* q_dir, int B, const int* ans_off, const int* ans_ids,
+                                float smoothing, float* gE, float* gR, int* r_touched, float* loss,
+                                float* scores, void* workspace, size_t ws_bytes) {
+  int rc = kv_check("skge_kvsall_grad", model, N, M, d, B, smoothing);
+  if (rc) return rc;
+  SKGE_CHECK_ARG(E && R && q_anchor && q_rel && q_dir && ans_off && ans_ids && gE && gR &&
+                     r_touched && loss, "skge_kvsall_grad: NULL argument");
+  const KvPlan p = kv_plan(B, N, M, d);
+  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_kvsall_grad: workspace needs %zu bytes "
+                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, N, M, d);
+  SKGE_CHECK_ARG(((uintptr_t)workspace & 15) == 0 &&
+                     (d % 4 != 0 || (((uintptr_t)E | (uintptr_t)R) & 15) == 0),
+                 "skge_kvsall_grad: the workspace and, at d %% 4 == 0, E and R must be 16-byte "
+                 "aligned");
+  hipStream_t st = as_stream(stream);
+  char* ws = (char*)workspace;
+  float* Q = (float*)(ws + p.o_q);
+  unsigned* bits = (unsigned*)(ws + p.o_bits);
+  float* G = (float*)(ws + p.o_g);
+  float* part = (float*)(ws + p.o_part);
+  float* lpart = (float*)(ws + p.o_lpart);
+  SKGE_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)B * p.wpr * sizeof(unsigned), st));
+  SKGE_CHECK_HIP(hipMemsetAsync(gR, 0, (size_t)M * d * sizeof(float), st));
+  SKGE_CHECK_HIP(hipMemsetAsync(r_touched, 0, (size_t)M * sizeof(int), st));
+  const int qblocks = (B + 3) / 4;
+  hipLaunchKernelGGL(k_kv_query, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
+                     q_rel, q_dir, B, Q);
+  hipLaunchKernelGGL(k_kv_labels, dim3(qblocks), dim3(256), 0, st, ans_off, ans_ids, B, N, p.wpr,
+                     bits);
+  KvGemm f = {};
+  f.A = Q;
+  f.lda = d;
+  f.B = E;
+  f.ldb = d;
+  f.Mr = B;
+  f.Nc = N;
+  f.K = d;
+  f.nbx = p.nbx;
+  f.G = G;
+  f.ldg = p.ldg;
+  f.scores = scores;
+  f.bits = bits;
+  f.wpr = p.wpr;
+  f.eps = smoothing;
+  f.eps_n = smoothing / (float)N;
+  f.inv_b = 1.0f / (float)B;
+  f.lpart = lpart;
+  const unsigned nfwd = p.nbx * p.nby;
+  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_FWD>), dim3(nfwd), dim3(256), 0, st, f);
+  KvGemm q = {};   // dq = G E: rows the queries, columns the dims, over the entities
+  q.A = G;
+  q.lda = p.ldg;
+  q.B = E;
+  q.ldb = d;
+  q.Mr = B;
+  q.Nc = d;
+  q.K = N;
+  q.kslice = p.kslice;
+  q.nbx = p.nbx;
+  q.C = part;
+  const unsigned ntd = (unsigned)((d + KV_T - 1) / KV_T);
+  hipLaunchKernelGGL((k_kv_gemm<false, true, KV_DQ>), dim3(p.nbx * ntd * (unsigned)p.ns),
+                     dim3(256), 0, st, q);
+  KvGemm e = {};   // gE = G^T Q: rows the entities, columns the dims, over the queries
+  e.A = G;
+  e.lda = p.ldg;
+  e.B = Q;
+  e.ldb = d;
+  e.Mr = N;
+  e.Nc = d;
+  e.K = B;
+  e.nbx = p.nby;
+  e.C = gE;
+  hipLaunchKernelGGL((k_kv_gemm<true, true, KV_DE>), dim3(p.nby * ntd), dim3(256), 0, st, e);
+  hipLaunchKernelGGL(k_kv_chain, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
+                     q_rel, q_dir, B, part, p.ns, gE, gR, r_touched);
+  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, st, lpart, nfwd, f.inv_b, loss);
+  SKGE_CHECK_LAUNCH("kvsall grad");
+  return SKGE_OK;
+}
+
+extern "C" int skge_kvsall_step(void* stream, int model, const skge_table_t* ent,
+                                const skge_table_t* rel, int d, const int* q_anchor,
+                                const int* q_rel, const int* q_dir, int B, const int* ans_off,
+                                const int* ans_ids, float smoothing, float* loss, void* workspace,
+                                size_t ws_bytes) {
+  int rc = kv_check("skge_kvsall_step", model, ent ? ent->rows : 1, rel ? rel->rows : 1, d, B,
+                    smoothing);
+  if (rc) return rc;
+  if ((rc = check_table(ent, "ent", false)) || (rc = check_table(rel, "rel", false))) return rc;
+  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "skge_kvsall_step: table widths %d / %d, "
+                 "d = %d", ent->width, rel->width, d);
+  const KvPlan p = kv_plan(B, ent->rows, rel->rows, d);
+  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_kvsall_step: workspace needs %zu bytes "
+                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, ent->rows, rel->rows, d);
+  char* ws = (char*)workspace;
+  float* gE = (float*)(ws + p.o_ge);
+  float* gR = (float*)(ws + p.o_gr);
+  int* touched = (int*)(ws + p.o_touched);
+  rc = skge_kvsall_grad(stream, model, ent->param, rel->param, ent->rows, rel->rows, d, q_anchor,
+                        q_rel, q_dir, B, ans_off, ans_ids, smoothing, gE, gR, touched, loss,
+                        nullptr, workspace, ws_bytes);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row
+  return launch_update_table(st, rel, gR, touched);                   // the rows a query names
+}

@@ -569,6 +569,29 @@ __global__ __launch_bounds__(256) void k_update_rows(TableDev t, const float* __
   }
 }
 
+// whole-table updater call (KvsAll, skge_kvsall.hip): row i with the gradient
+// g[i] + rin * P[i] + rout * P[i] (a sum over the batch: no occurrence mean),
+// every row, or the rows whose mask word is non-zero -- a masked-out row is
+// neither read nor written, parameter and state
+template <int KM>
+__global__ __launch_bounds__(256) void k_update_table(TableDev t, const float* __restrict__ g,
+                                                      const int* __restrict__ mask) {
+  const int wpb = blockDim.x >> 6;
+  const int l = lane_id();
+  for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < t.rows; row += gridDim.x * wpb) {
+    if (mask && __builtin_amdgcn_readfirstlane(mask[row]) == 0) continue;
+    float gv[KM];
+#pragma unroll
+    for (int k = 0; k < KM; ++k) {
+      const int e = l + 64 * k;
+      const size_t o = (size_t)row * t.width + (e < t.width ? e : t.width - 1);
+      const float x = g[o], p = t.P[o];
+      gv[k] = e < t.width ? (x + t.rin * p) + t.rout * p : 0.0f;
+    }
+    update_row<KM>(t, row, gv);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_update_rows_wide(TableDev t, const float* __restrict__ g,
                                                           const int* __restrict__ idx, int U) {
   const long long w = t.width;
@@ -861,6 +884,35 @@ int apply_with_wstep(hipStream_t st, const skge_table_t* ent, int nslots, const 
     default: set_error("entity width %d unsupported", ent->width); return SKGE_ENOTSUP;
   }
   SKGE_CHECK_LAUNCH("apply + W step");
+  return SKGE_OK;
+}
+
+// The updater and projection of t on every row (mask NULL) or on the rows
+// mask [rows] marks, from a whole-table gradient g [rows][width]
+// (k_update_table); skge_update_rows' checks and arithmetic (update_row).
+int launch_update_table(hipStream_t st, const skge_table_t* t, const float* g, const int* mask) {
+  int rc = check_table(t, "table", false);
+  if (rc) return rc;
+  SKGE_CHECK_ARG(t->opt == SKGE_SGD || t->opt == SKGE_ADAGRAD, "unknown updater %d", t->opt);
+  SKGE_CHECK_ARG(t->opt == SKGE_SGD || t->state, "AdaGrad needs state");
+  SKGE_CHECK_ARG(t->post >= 0 && t->post <= 3, "unknown post %d", t->post);
+  if ((rc = check_unitmod(t))) return rc;
+  SKGE_CHECK_ARG(g, "g NULL");
+  const TableDev td = table_dev(t);
+  const int grid = grid_for_waves(t->rows);
+#define SKGE_UT(K) \
+  case K: hipLaunchKernelGGL((k_update_table<K>), dim3(grid), dim3(256), 0, st, td, g, mask); break;
+  switch (km_for(t->width)) {
+    SKGE_UT(1)
+    SKGE_UT(2)
+    SKGE_UT(3)
+    SKGE_UT(4)
+    SKGE_UT(8)
+    SKGE_UT(16)
+    default: set_error("table width %d unsupported (1..1024)", t->width); return SKGE_ENOTSUP;
+  }
+#undef SKGE_UT
+  SKGE_CHECK_LAUNCH("update table");
   return SKGE_OK;
 }
 

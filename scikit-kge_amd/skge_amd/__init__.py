@@ -6,6 +6,7 @@ RandomModeSampler, CorruptedSampler, LCWASampler.  Every numeric step runs in li
 from .version import __version__
 from .base import (Model, StochasticTrainer, PairwiseStochasticTrainer, SelfAdversarialTrainer,
                    set_deterministic, deterministic)
+from .kvsall import KvsAllTrainer, KvsAllQueries
 from .transe import TransE
 from .hole import HolE
 from .rescal import RESCAL

@@ -150,6 +150,11 @@ SIGNATURES = {
     "skge_sadv_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_i, N_P, c_f, c_f, c_p]),
     "skge_sadv_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
                                       c_p, c_f, c_f, c_i, c_p, S_P, N_P]),
+    "skge_kvsall_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "skge_kvsall_grad": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p,
+                               c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz]),
+    "skge_kvsall_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p,
+                               c_p, c_sz]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,

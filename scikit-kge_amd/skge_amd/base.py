@@ -363,9 +363,78 @@ class Model(object):
                                        L.ptr(pos), L.ptr(negK), P, negs, float(self.gamma),
                                        float(self.alpha), L.ptr(loss)), "sadv_step")
 
+    # ---- KvsAll / 1-N scoring with binary cross-entropy (DistMult, ComplEx) ----
+    def _require_kvsall(self):
+        if self._kernel_model() not in KVSALL_MODELS:
+            raise ValueError("%s has no KvsAll training: scoring a query against every entity "
+                             "with one dot product is served for DistMult and ComplEx; train %s "
+                             "with StochasticTrainer or PairwiseStochasticTrainer"
+                             % (type(self).__name__, type(self).__name__))
+
+    def _kvsall_args(self, batch):
+        """A KvsAllQueries batch on the model's device, checked, and the
+        workspace of its shape."""
+        self._require_kvsall()
+        B = len(batch)
+        if B < 1 or B > 4096:
+            raise ValueError("KvsAll batch of %d queries; a batch holds 1 to 4096 (raise the "
+                             "trainer's nbatches)" % B)
+        if batch.device != self.device:
+            batch = batch.to(self.device)
+        N, M = self.params["E"].rows, self.params["R"].rows
+        nbytes = L.lib().skge_kvsall_workspace_bytes(self._kernel_model(), B, N, M, self.d)
+        if nbytes == 0:
+            raise L.SkgeError("kvsall: %s" % L.lib().skge_last_error().decode())
+        return batch, B, N, M, self._workspace(nbytes), nbytes
+
+    def _kvsall_gradients(self, batch, scores=False):
+        """KvsAll gradients of a batch of queries (kvsall.KvsAllQueries):
+        {"E": (gE [N, d], arange(N)), "R": (rows [U, d], the sorted ids of the
+        relations the batch names)} -- the plain gradient of the batch's
+        L plus the logistic regulariser rparam * param, no mean over
+        occurrences -- and sets self.loss = L.  scores=True
+        keeps the raw z [B, N] in _score."""
+        batch, B, N, M, ws, nbytes = self._kvsall_args(batch)
+        dev, d = self.device, self.d
+        gE = torch.empty((N, d), dtype=torch.float32, device=dev)
+        gR = torch.empty((M, d), dtype=torch.float32, device=dev)
+        touched = torch.empty(M, dtype=torch.int32, device=dev)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._score = torch.empty((B, N), dtype=torch.float32, device=dev) if scores else None
+        L.check(L.lib().skge_kvsall_grad(
+            L.stream_ptr(), self._kernel_model(), L.ptr(self.params["E"].data),
+            L.ptr(self.params["R"].data), N, M, d, L.ptr(batch.anchor), L.ptr(batch.rel),
+            L.ptr(batch.dir), B, L.ptr(batch.off), L.ptr(batch.ans),
+            float(getattr(self, "label_smoothing", 0.0)), L.ptr(gE), L.ptr(gR), L.ptr(touched),
+            L.ptr(loss), L.ptr(self._score), L.ptr(ws), nbytes), "kvsall_grad")
+        self.loss = float(loss.item())
+        ids = torch.nonzero(touched).reshape(-1)
+        rows = gR[ids]
+        reg = self._reg("logistic")
+        for pid, g, idx in (("E", gE, None), ("R", rows, ids)):
+            rin, rout, _ = reg[pid]
+            if rin + rout != 0.0:   # g += rparam * param, as skge_kvsall_step's update does
+                p = self.params[pid].data
+                g.add_(p if idx is None else p[idx], alpha=float(rin + rout))
+        return {"E": (gE, torch.arange(N, device=dev)), "R": (rows, ids)}
+
+    def _kvsall_step(self, batch, updaters, loss):
+        """scores + loss + gradients + update of a batch of queries in one
+        skge_kvsall_step; the batch's L is added into the device word `loss`."""
+        batch, B, N, M, ws, nbytes = self._kvsall_args(batch)
+        reg = self._reg("logistic")
+        te, tr = [updaters[pid].table(None, rin=reg[pid][0], rout=reg[pid][1]) for pid in ("E", "R")]
+        L.check(L.lib().skge_kvsall_step(
+            L.stream_ptr(), self._kernel_model(), te, tr, self.d, L.ptr(batch.anchor),
+            L.ptr(batch.rel), L.ptr(batch.dir), B, L.ptr(batch.off), L.ptr(batch.ans),
+            float(getattr(self, "label_smoothing", 0.0)), L.ptr(loss), L.ptr(ws), nbytes),
+            "kvsall_step")
+
 
 # the distance models (scores <= 0) the self-adversarial loss is defined for
 SADV_MODELS = (L.SKGE_TRANSE_L1, L.SKGE_TRANSE_L2, L.SKGE_ROTATE)
+# the models whose score is one dot product of a query vector with the candidate row
+KVSALL_MODELS = (L.SKGE_DISTMULT, L.SKGE_COMPLEX)
 
 
 class StochasticTrainer(object):
