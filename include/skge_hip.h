@@ -666,6 +666,61 @@ int skge_kvsall_step(void *stream, int model, const skge_table_t *ent, const skg
                      void *workspace, size_t ws_bytes);
 
 /*
+ * 1vsAll training of SKGE_DISTMULT and SKGE_COMPLEX (Lacroix et al. 2018):
+ * softmax cross-entropy of every query against its ONE target, with the
+ * nuclear 3-norm regulariser N3.  A query is (anchor q_anchor[b], relation
+ * q_rel[b], direction q_dir[b], target q_target[b]): direction 0 is (a, p, ?)
+ * with the triple's object for target, 1 is (?, p, a) with its subject; one
+ * query per training triple and direction, never deduplicated.  With q_b the
+ * query vector of skge_kvsall_grad, z_be = q_b . E_e, eps = smoothing:
+ *   y'_be = (1 - eps) [e == g_b] + eps / N
+ *   lse_b = log sum_e exp(z_be)                       (max-subtracted)
+ *   L_ce  = (1 / B) sum_b ( lse_b - sum_e y'_be z_be )
+ *   G_be  = ( exp(z_be - lse_b) - y'_be ) / B
+ *   gE[e] = sum_b G_be q_b        dq_b = sum_e G_be E_e
+ *   L_n3  = (n3 / B) sum_b ( |E_a|_3^3 + |R_p|_3^3 + |E_g|_3^3 )
+ * dq_b goes through q's Jacobian into gE[a_b] and gR[p_b] as in
+ * skge_kvsall_grad.  |x|_3^3 sums |x_k|^3 (DistMult) or (re^2 + im^2)^(3/2)
+ * over the d / 2 interleaved complex components (ComplEx); its gradient,
+ * 3 |x_k| x_k or 3 |c_j| (re, im) times n3 / B, is added once per occurrence
+ * to gE[a], gR[p] and gE[g]; it is 0, never NaN, at a zero component.
+ * *loss += L_ce + L_n3.  The gradient is the plain gradient of that sum, no
+ * mean over occurrences; the model's activation plays no part.
+ * Launches (csrc/skge_kvsall.hip): the query vectors; Z = Q E^T, whose
+ * epilogue leaves raw z in G and, per row and 128-column tile, max z, sum
+ * exp(z - max) and sum z; the combine (lse_b, the query's loss partial, G
+ * rewritten in place to (softmax - y') / B); dq = G E; gE = G^T Q; at n3 > 0
+ * the N3 gradient, one plain add per element of every row a query names (its
+ * occurrence count times the row's term); the chain rule (float atomics); the
+ * loss's fixed-order sum.
+ * skge_onevsall_grad: gE [N][d] (every row written), gR [M][d] and r_touched
+ *   [M] as skge_kvsall_grad leaves them; scores (optional) receives z [B][N],
+ *   lse (optional) lse_b [B].  No rparam regulariser.
+ * skge_onevsall_step: the same, then skge_kvsall_step's updates: every entity
+ *   row, the marked relation rows, g + (rin + rout) * param.
+ * A query is invalid when its anchor, relation, direction or target lies
+ * outside its table: its G row is zero, it adds no loss, no chain-rule term, no
+ * N3 term and no mark, B still counts it, and nothing is read or written out
+ * of bounds for it.  workspace: skge_onevsall_workspace_bytes (0 for arguments
+ * the entry points refuse), 16-byte aligned: Q, G, the dq partials, 3 nby B row
+ * partials (nby = ceil(N / 128)), lse, one loss partial per query, N + M
+ * occurrence counts, and the step's gE, gR and marks; no answer bitmap.
+ * Refused as skge_kvsall_* refuse (models other than 5 / 6 by name, B > 4096,
+ * d > 1024, sizes < 1, odd d for ComplEx, smoothing outside [0, 1), NULL
+ * arguments, a short workspace), and n3 < 0 or not finite (SKGE_EINVAL).
+ */
+size_t skge_onevsall_workspace_bytes(int model, int B, int N, int M, int d);
+int skge_onevsall_grad(void *stream, int model, const float *E, const float *R, int N, int M,
+                       int d, const int *q_anchor, const int *q_rel, const int *q_dir,
+                       const int *q_target, int B, float smoothing, float n3, float *gE,
+                       float *gR, int *r_touched, float *loss, float *scores, float *lse,
+                       void *workspace, size_t ws_bytes);
+int skge_onevsall_step(void *stream, int model, const skge_table_t *ent, const skge_table_t *rel,
+                       int d, const int *q_anchor, const int *q_rel, const int *q_dir,
+                       const int *q_target, int B, float smoothing, float n3, float *loss,
+                       void *workspace, size_t ws_bytes);
+
+/*
  * Pipelined epoch runner for TransE-L1 with packed accumulators (the
  * throughput path).  Same result, bit for bit, as skge_runner_create's loop
  * with the same tables and arguments: all negatives of an epoch are drawn in

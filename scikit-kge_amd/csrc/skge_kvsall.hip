@@ -25,7 +25,14 @@
 // (skge_neighbours.hip), or in K-MAJOR form (the contraction index is its row
 // index: E in DQ, G and Q in DE) and stored as loaded.  Either way the LDS
 // image is k-major and a lane reads one dword per MFMA operand.
+//
+// 1vsAll (skge_onevsall_grad) shares the query vectors, the
+// tile kernel and the loss sum: softmax cross-entropy against one target per
+// query needs a reduction across a score row, which k_kv_gemm<OVA> starts on
+// the accumulators (per row and column tile) and k_ova_combine finishes; see
+// "1vsAll" below.
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "skge_elem.h"
@@ -43,7 +50,8 @@ constexpr int KV_PAD_KM = KV_T + 4;  // k-major image: 16-byte stores
 constexpr int KV_BMAX = 4096;
 constexpr int KV_DMAX = 1024;
 
-enum { KV_FWD = 0, KV_DQ = 1, KV_DE = 2 };
+// KV_OVA: the 1vsAll forward (raw z and each row's softmax partials per tile)
+enum { KV_FWD = 0, KV_DQ = 1, KV_DE = 2, KV_OVA = 3 };
 
 struct KvGemm {
   const float* A;        // ROW form [Mr][lda] / K-MAJOR form [K][lda]
@@ -61,7 +69,37 @@ struct KvGemm {
   int wpr;
   float eps, eps_n, inv_b;   // smoothing, smoothing / N, 1 / B
   float* lpart;          // [grid] loss partials
+  // OVA: per output row and column tile, over the tile's live columns
+  float *pm, *ps, *pt;   // [nby][Mr] max z, sum exp(z - max), sum z
 };
+
+// ---- softmax partials (1vsAll) ----
+// (m, s): s = sum exp(z - m) over some columns, the identity (-inf, 0) over none
+__device__ __forceinline__ void kv_ms_merge(float& m, float& s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  s = (m == mx ? s : (s == 0.0f ? 0.0f : s * expf(m - mx))) +
+      (m2 == mx ? s2 : (s2 == 0.0f ? 0.0f : s2 * expf(m2 - mx)));
+  m = mx;
+}
+
+// max / sum over the 32 lanes of a lane's half-wave, wave_sum's DPP steps: the
+// 16-lane rows' values, then the half's two rows
+__device__ __forceinline__ float half_max(float v, int h) {
+  v = fmaxf(v, dpp_f<0xb1>(v));
+  v = fmaxf(v, dpp_f<0x4e>(v));
+  v = fmaxf(v, dpp_f<0x141>(v));
+  v = fmaxf(v, dpp_f<0x140>(v));
+  const float lo = fmaxf(lane_f(v, 0), lane_f(v, 16)), hi = fmaxf(lane_f(v, 32), lane_f(v, 48));
+  return h ? hi : lo;
+}
+__device__ __forceinline__ float half_sum(float v, int h) {
+  v += dpp_f<0xb1>(v);
+  v += dpp_f<0x4e>(v);
+  v += dpp_f<0x141>(v);
+  v += dpp_f<0x140>(v);
+  const float lo = lane_f(v, 0) + lane_f(v, 16), hi = lane_f(v, 32) + lane_f(v, 48);
+  return h ? hi : lo;
+}
 
 // ---- query vectors: one wave per query ----
 // A query naming a row outside its table scores as the zero vector and takes
@@ -238,6 +276,66 @@ __global__ __launch_bounds__(256, 2) void k_kv_gemm(KvGemm a) {
     }
   }
   // ---- epilogue ----
+  if constexpr (EPI == KV_OVA) {
+    // Raw z, and per output row the tile's (max z, sum exp(z - max), sum z)
+    // over its live columns: the 32 lanes of the row's half-wave, then the two
+    // nj tiles, then the two wt waves through LDS (wt = 0 first).  A skipped
+    // 32 x 32 tile is the identity (-inf, 0, 0).  Lane rho of a half keeps row
+    // rho = 16 mi + r, so the partials leave in one store per lane.
+    // The three half_* reductions of one (r, nj) read lanes with v_readlane,
+    // so all 64 lanes must be active in them: they sit under the wave-uniform
+    // am / bn tests only, never under a per-lane one, and run for rows at or
+    // past Mr as well (acc = 0 there; the result is not stored).
+    float km = -INFINITY, ks = 0.0f, kt = 0.0f;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+      if (!am[mi]) continue;   // wave-uniform
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = m0 + wq * 64 + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+        float rm = -INFINITY, rs = 0.0f, rt = 0.0f;
+#pragma unroll
+        for (int nj = 0; nj < 2; ++nj) {
+          if (!bn[nj]) continue;   // wave-uniform
+          const int j = n0 + bj0 + 32 * nj;
+          const bool live = j < a.Nc;
+          const float z = acc[mi][nj][r];
+          if (live && i < a.Mr) {
+            a.G[(size_t)i * a.ldg + j] = z;
+            if (a.scores) a.scores[(size_t)i * a.Nc + j] = z;
+          }
+          const float m = half_max(live ? z : -INFINITY, h);   // finite: column n0 + .. + 32 nj lives
+          const float s = half_sum(live ? expf(z - m) : 0.0f, h);
+          const float t = half_sum(live ? z : 0.0f, h);
+          kv_ms_merge(rm, rs, m, s);
+          rt += t;
+        }
+        if ((l & 31) == 16 * mi + r) {
+          km = rm;
+          ks = rs;
+          kt = rt;
+        }
+      }
+    }
+    const int rho = l & 31;
+    const int row = wq * 64 + 32 * (rho >> 4) + (rho & 3) + 8 * ((rho & 15) >> 2) + 4 * h;
+    __syncthreads();   // the last chunk's operand reads are done: sA is free
+    if (wt == 1) {
+      sA[3 * row] = km;
+      sA[3 * row + 1] = ks;
+      sA[3 * row + 2] = kt;
+    }
+    __syncthreads();
+    if (wt == 0 && m0 + row < a.Mr) {
+      kv_ms_merge(km, ks, sA[3 * row], sA[3 * row + 1]);
+      kt += sA[3 * row + 2];
+      const size_t at = (size_t)by * a.Mr + (m0 + row);
+      a.pm[at] = km;
+      a.ps[at] = ks;
+      a.pt[at] = kt;
+    }
+    return;
+  }
   float lsum = 0.0f;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
@@ -281,6 +379,35 @@ __global__ __launch_bounds__(256, 2) void k_kv_gemm(KvGemm a) {
 //   ComplEx tails   gE[a] += dq conj(R_p)       gR[p] += dq conj(E_a)
 //   ComplEx heads   gE[a] += dq R_p             gR[p] += conj(dq) E_a
 // (o elementwise, the rest complex products over (x[2j], x[2j + 1])).
+__device__ __forceinline__ void kv_dq_sum(const float* __restrict__ part, int ns, int B, int b,
+                                          int d, int l, float* dq) {
+  for (int k = l; k < d; k += 64) {
+    float s = 0.0f;
+    for (int sl = 0; sl < ns; ++sl) s += part[((size_t)sl * B + b) * d + k];
+    dq[k] = s;
+  }
+}
+
+// component k of the two chain-rule rows: va into gE[a], vr into gR[p]
+__device__ __forceinline__ void kv_chain_elem(int model, int t, const float* dq, const float* ea,
+                                              const float* rp, int k, float& va, float& vr) {
+  if (model == SKGE_DISTMULT) {
+    va = dq[k] * rp[k];
+    vr = dq[k] * ea[k];
+  } else {
+    const int kp = k ^ 1;
+    const bool im = k & 1, tail = t == 0;
+    if (tail) {   // dq conj(x): re dq.re x.re + dq.im x.im, im dq.im x.re - dq.re x.im
+      va = im ? fmaf(dq[k], rp[kp], -(dq[kp] * rp[k])) : fmaf(dq[k], rp[k], dq[kp] * rp[kp]);
+      vr = im ? fmaf(dq[k], ea[kp], -(dq[kp] * ea[k])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
+    } else {      // dq r: re dq.re r.re - dq.im r.im, im dq.re r.im + dq.im r.re
+      va = im ? fmaf(dq[kp], rp[k], dq[k] * rp[kp]) : fmaf(dq[k], rp[k], -(dq[kp] * rp[kp]));
+      // conj(dq) a: re dq.re a.re + dq.im a.im, im dq.re a.im - dq.im a.re
+      vr = im ? fmaf(dq[kp], ea[k], -(dq[k] * ea[kp])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __restrict__ E,
                                                   const float* __restrict__ R, int N, int M, int d,
                                                   const int* __restrict__ qa,
@@ -295,13 +422,7 @@ __global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __rest
   const bool live = b < B;
   const int a = live ? qa[b] : -1, p = live ? qp[b] : -1, t = live ? qt[b] : 0;
   const bool ok = live && kv_query_ok(a, p, t, N, M);
-  if (ok) {
-    for (int k = l; k < d; k += 64) {
-      float s = 0.0f;
-      for (int sl = 0; sl < ns; ++sl) s += part[((size_t)sl * B + b) * d + k];
-      s_dq[w][k] = s;
-    }
-  }
+  if (ok) kv_dq_sum(part, ns, B, b, d, l, s_dq[w]);
   __syncthreads();
   if (!ok) return;
   const float* ea = E + (size_t)a * d;
@@ -311,21 +432,7 @@ __global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __rest
   const float* dq = s_dq[w];
   for (int k = l; k < d; k += 64) {
     float va, vr;
-    if (model == SKGE_DISTMULT) {
-      va = dq[k] * rp[k];
-      vr = dq[k] * ea[k];
-    } else {
-      const int kp = k ^ 1;
-      const bool im = k & 1, tail = t == 0;
-      if (tail) {   // dq conj(x): re dq.re x.re + dq.im x.im, im dq.im x.re - dq.re x.im
-        va = im ? fmaf(dq[k], rp[kp], -(dq[kp] * rp[k])) : fmaf(dq[k], rp[k], dq[kp] * rp[kp]);
-        vr = im ? fmaf(dq[k], ea[kp], -(dq[kp] * ea[k])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
-      } else {      // dq r: re dq.re r.re - dq.im r.im, im dq.re r.im + dq.im r.re
-        va = im ? fmaf(dq[kp], rp[k], dq[k] * rp[kp]) : fmaf(dq[k], rp[k], -(dq[kp] * rp[kp]));
-        // conj(dq) a: re dq.re a.re + dq.im a.im, im dq.re a.im - dq.im a.re
-        vr = im ? fmaf(dq[kp], ea[k], -(dq[k] * ea[kp])) : fmaf(dq[k], ea[k], dq[kp] * ea[kp]);
-      }
-    }
+    kv_chain_elem(model, t, dq, ea, rp, k, va, vr);
     atomicAdd(ge + k, va);
     atomicAdd(gr + k, vr);
   }
@@ -345,6 +452,198 @@ __global__ __launch_bounds__(256) void k_kv_loss(const float* __restrict__ lpart
     __syncthreads();
   }
   if (threadIdx.x == 0) *loss += (float)(s[0] * (double)inv_b);
+}
+
+// ==== 1vsAll: softmax cross-entropy against one target, with N3 ====
+// (include/skge_hip.h, skge_onevsall_grad).  A query carries a
+// target g; the forward is k_kv_gemm<OVA>, which leaves raw z in G and each
+// row's (max, sum exp, sum z) per column tile; k_ova_combine turns them into
+// lse_b and the loss term and rewrites G to (softmax - y') / B; the DQ and DE
+// products, k_kv_loss and the updates are KvsAll's.
+__device__ __forceinline__ bool ova_query_ok(int a, int p, int t, int g, int N, int M) {
+  return kv_query_ok(a, p, t, N, M) && g >= 0 && g < N;
+}
+
+// block-wide reductions in a fixed order (the tree of k_kv_loss); all 256 threads
+__device__ __forceinline__ double block_sum256(double v, double* s) {
+  __syncthreads();   // s may still be read from the call before
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+    __syncthreads();
+  }
+  return s[0];
+}
+__device__ __forceinline__ double block_max256(double v, double* s) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
+    __syncthreads();
+  }
+  return s[0];
+}
+
+// Workgroup (b, c) of nsplit per query: every one combines query b's nby
+// partials -- the row's maximum mx (exact in any order), then S = sum_tile
+// s_tile exp(m_tile - mx) and T = sum_tile t_tile in fp64, thread i over tiles
+// i, i + 256, .., then the fixed tree -- and rewrites columns [c chunk, (c + 1)
+// chunk) of G's row in place:
+//   G_be = (exp((z_be - mx) - log S) - y'_be) / B,   0 for an invalid query.
+// The workgroup whose columns hold the target (workgroup 0 of an invalid query)
+// reads z_g before it rewrites and leaves lse_b = mx + log S and the query's
+// loss partial (mx - z_g) + log S + eps (z_g - T / N); at n3 > 0 it also counts
+// the query's anchor, target and relation rows in occ [N + M] (integer adds:
+// the counts do not depend on the order).  chunk is a multiple of
+// 4: whole 16-byte groups below N move as float4, the last group by element;
+// the pad columns past N are neither read nor written.
+__global__ __launch_bounds__(256) void k_ova_combine(
+    float* __restrict__ G, size_t ldg, int N, int M, int B, int nby, int nsplit, int chunk,
+    const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ pt,
+    const int* __restrict__ qa, const int* __restrict__ qp, const int* __restrict__ qt,
+    const int* __restrict__ qg, float eps, float* __restrict__ lse_ws,
+    float* __restrict__ lse_out, float* __restrict__ lpart, int* __restrict__ occ) {
+  __shared__ double s_red[256];
+  const int b = blockIdx.x / nsplit, c = blockIdx.x % nsplit, tid = threadIdx.x;
+  const int g = qg[b];
+  const bool ok = ova_query_ok(qa[b], qp[b], qt[b], g, N, M);
+  double mloc = -INFINITY;
+  for (int i = tid; i < nby; i += 256) mloc = fmax(mloc, (double)pm[(size_t)i * B + b]);
+  const double mx = block_max256(mloc, s_red);   // finite: tile 0 holds column 0
+  double sl = 0.0, tl = 0.0;
+  for (int i = tid; i < nby; i += 256) {
+    const size_t at = (size_t)i * B + b;
+    sl += (double)ps[at] * exp((double)pm[at] - mx);
+    tl += (double)pt[at];
+  }
+  const double S = block_sum256(sl, s_red);
+  const double T = block_sum256(tl, s_red);
+  const double logS = log(S);
+  float* row = G + (size_t)b * ldg;
+  const int c0 = c * chunk, c1 = min(N, c0 + chunk);
+  const bool owner = ok ? (g >= c0 && g < c1) : c == 0;
+  if (owner && tid == 0) {
+    const float lse = (float)(mx + logS);
+    lse_ws[b] = lse;
+    if (lse_out) lse_out[b] = lse;
+    float term = 0.0f;
+    if (ok) {
+      const double zg = (double)row[g];
+      term = (float)((mx - zg) + logS + (double)eps * (zg - T / (double)N));
+    }
+    lpart[b] = term;
+    if (ok && occ) {   // N3: the rows this query names, counted (k_ova_n3)
+      atomicAdd(occ + qa[b], 1);
+      atomicAdd(occ + g, 1);
+      atomicAdd(occ + N + qp[b], 1);
+    }
+  }
+  __syncthreads();   // z_g is read before any thread rewrites it
+  const float fm = (float)mx, fl = (float)logS, inv_b = 1.0f / (float)B;
+  const float yn = eps / (float)N, yg = (1.0f - eps) + yn;
+  for (int j = c0 + 4 * tid; j < c1; j += 1024) {
+    if (j + 4 <= N) {
+      float4 v = *reinterpret_cast<const float4*>(row + j);
+      float o[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        o[u] = ok ? (expf((o[u] - fm) - fl) - (j + u == g ? yg : yn)) * inv_b : 0.0f;
+      *reinterpret_cast<float4*>(row + j) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+      for (int u = 0; j + u < N; ++u)
+        row[j + u] = ok ? (expf((row[j + u] - fm) - fl) - (j + u == g ? yg : yn)) * inv_b : 0.0f;
+    }
+  }
+}
+
+// |x|_3^3 terms of row x at component k, weight c = n3 / B: the gradient
+// 3 |x_k| x_k (DistMult) or 3 |c_j| (re, im) (ComplEx) -- 0, never NaN, at a
+// zero component -- and the component's share of the norm (ComplEx: the even
+// lane of a pair carries |c_j|^3)
+__device__ __forceinline__ float n3_elem(int model, const float* x, int k, float& norm) {
+  if (model == SKGE_DISTMULT) {
+    const float ax = fabsf(x[k]);
+    norm += ax * ax * ax;
+    return 3.0f * ax * x[k];
+  }
+  const float re = x[k & ~1], im = x[k | 1];
+  const float mod = sqrtf(fmaf(re, re, im * im));
+  if (!(k & 1)) norm += mod * mod * mod;
+  return 3.0f * mod * x[k];
+}
+
+// The N3 gradient, one wave per table row (E rows, then R rows).  Every
+// occurrence of a row adds the same term, c 3 |x_k| x_k with c = n3 / B, so the
+// sum over a batch is occ[row] times it: one product per element in place of
+// one float atomic per occurrence, and the same bits whatever order the queries
+// ran in.  It runs after the DE product's stores and gR's memset and before
+// the chain rule's atomics; a row no valid query names is not touched.
+__global__ __launch_bounds__(256) void k_ova_n3(int model, const float* __restrict__ E,
+                                                const float* __restrict__ R, int N, int M, int d,
+                                                const int* __restrict__ occ, float c,
+                                                float* __restrict__ gE, float* __restrict__ gR) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (row >= N + M) return;
+  const int n = occ[row];
+  if (n == 0) return;
+  const bool ent = row < N;
+  const float* x = ent ? E + (size_t)row * d : R + (size_t)(row - N) * d;
+  float* g = ent ? gE + (size_t)row * d : gR + (size_t)(row - N) * d;
+  const float w = c * (float)n;
+  float norm = 0.0f;
+  for (int k = l; k < d; k += 64) g[k] = fmaf(w, n3_elem(model, x, k, norm), g[k]);
+}
+
+// k_kv_chain with a target: the same chain rule, and at n3 > 0 the query's
+// n3 (|E_a|_3^3 + |R_p|_3^3 + |E_g|_3^3) into its loss partial (the N3 gradient
+// is k_ova_n3's).  An invalid query (target included) adds nothing and marks
+// nothing.
+__global__ __launch_bounds__(256) void k_ova_chain(int model, const float* __restrict__ E,
+                                                   const float* __restrict__ R, int N, int M, int d,
+                                                   const int* __restrict__ qa,
+                                                   const int* __restrict__ qp,
+                                                   const int* __restrict__ qt,
+                                                   const int* __restrict__ qg, int B,
+                                                   const float* __restrict__ part, int ns,
+                                                   float n3, float* __restrict__ gE,
+                                                   float* __restrict__ gR,
+                                                   int* __restrict__ r_touched,
+                                                   float* __restrict__ lpart) {
+  __shared__ float s_dq[4][KV_DMAX];
+  const int w = threadIdx.x >> 6, l = lane_id();
+  const int b = blockIdx.x * 4 + w;
+  const bool live = b < B;
+  const int a = live ? qa[b] : -1, p = live ? qp[b] : -1, t = live ? qt[b] : 0;
+  const int g = live ? qg[b] : -1;
+  const bool ok = live && ova_query_ok(a, p, t, g, N, M);
+  if (ok) kv_dq_sum(part, ns, B, b, d, l, s_dq[w]);
+  __syncthreads();
+  if (!ok) return;
+  const float* ea = E + (size_t)a * d;
+  const float* rp = R + (size_t)p * d;
+  const float* eg = E + (size_t)g * d;
+  float* ge = gE + (size_t)a * d;
+  float* gr = gR + (size_t)p * d;
+  const float* dq = s_dq[w];
+  float norm = 0.0f;
+  for (int k = l; k < d; k += 64) {
+    float va, vr;
+    kv_chain_elem(model, t, dq, ea, rp, k, va, vr);
+    if (n3 > 0.0f) {
+      n3_elem(model, ea, k, norm);
+      n3_elem(model, rp, k, norm);
+      n3_elem(model, eg, k, norm);
+    }
+    atomicAdd(ge + k, va);
+    atomicAdd(gr + k, vr);
+  }
+  if (n3 > 0.0f) {   // wave-uniform
+    norm = wave_sum(norm);
+    if (l == 0) lpart[b] += n3 * norm;
+  }
+  if (l == 0) r_touched[p] = 1;
 }
 
 // ---- plan and workspace ----
@@ -417,6 +716,58 @@ static int kv_check(const char* who, int model, int N, int M, int d, int B, floa
   SKGE_CHECK_ARG(model != SKGE_COMPLEX || d % 2 == 0, "%s: ComplEx needs an even d (%d)", who, d);
   SKGE_CHECK_ARG(smoothing >= 0.0f && smoothing < 1.0f, "%s: label smoothing %g outside [0, 1)",
                  who, (double)smoothing);
+  return SKGE_OK;
+}
+
+// ---- 1vsAll: plan and checks ----
+struct OvaPlan {
+  KvPlan kv;             // ldg, the FWD tiles and the DQ slices are KvsAll's
+  int nsplit, chunk;     // k_ova_combine: workgroups per query, columns per workgroup
+  size_t o_q, o_g, o_part, o_rowp, o_lse, o_lpart, o_occ, o_ge, o_gr, o_touched, total;
+};
+
+static OvaPlan ova_plan(int B, int N, int M, int d) {
+  OvaPlan p;
+  p.kv = kv_plan(B, N, M, d);
+  // about 1024 workgroups, none with fewer than 1024 columns (but one per query)
+  const long long want = std::max<long long>(1, std::min<long long>((1024 + B - 1) / B,
+                                                                    ((long long)N + 1023) / 1024));
+  const long long per = (((long long)N + want - 1) / want + 3) & ~3ll;
+  p.chunk = (int)std::min<long long>(per, (1ll << 31) - 4);
+  p.nsplit = (int)(((long long)N + p.chunk - 1) / p.chunk);
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align256(bytes);
+    return at;
+  };
+  p.o_q = take((size_t)B * d * sizeof(float));
+  p.o_g = take((size_t)B * p.kv.ldg * sizeof(float));
+  p.o_part = take((size_t)p.kv.ns * B * d * sizeof(float));
+  p.o_rowp = take((size_t)3 * p.kv.nby * B * sizeof(float));
+  p.o_lse = take((size_t)B * sizeof(float));
+  p.o_lpart = take((size_t)B * sizeof(float));
+  p.o_occ = take(((size_t)N + M) * sizeof(int));
+  p.o_ge = take((size_t)N * d * sizeof(float));
+  p.o_gr = take((size_t)M * d * sizeof(float));
+  p.o_touched = take((size_t)M * sizeof(int));
+  p.total = o;
+  return p;
+}
+
+static int ova_check(const char* who, int model, int N, int M, int d, int B, float smoothing,
+                     float n3) {
+  SKGE_CHECK_ARG(model_known(model), "%s: unknown model %d", who, model);
+  if (!model_diag(model)) {
+    set_error("%s: model %d (%s) is not served: 1vsAll scores a query against every entity with "
+              "one dot product, which DistMult and ComplEx allow", who, model,
+              kv_model_name(model));
+    return SKGE_ENOTSUP;
+  }
+  int rc = kv_check(who, model, N, M, d, B, smoothing);
+  if (rc) return rc;
+  SKGE_CHECK_ARG(n3 >= 0.0f && std::isfinite(n3), "%s: N3 weight %g is negative or not finite", who,
+                 (double)n3);
   return SKGE_OK;
 }
 
@@ -533,6 +884,128 @@ extern "C" int skge_kvsall_step(void* stream, int model, const skge_table_t* ent
   rc = skge_kvsall_grad(stream, model, ent->param, rel->param, ent->rows, rel->rows, d, q_anchor,
                         q_rel, q_dir, B, ans_off, ans_ids, smoothing, gE, gR, touched, loss,
                         nullptr, workspace, ws_bytes);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row
+  return launch_update_table(st, rel, gR, touched);                   // the rows a query names
+}
+
+// ---- 1vsAll entry points ----
+extern "C" size_t skge_onevsall_workspace_bytes(int model, int B, int N, int M, int d) {
+  if (ova_check("skge_onevsall_workspace_bytes", model, N, M, d, B, 0.0f, 0.0f) != SKGE_OK)
+    return 0;
+  return ova_plan(B, N, M, d).total;
+}
+
+extern "C" int skge_onevsall_grad(void* stream, int model, const float* E, const float* R, int N,
+                                  int M, int d, const int* q_anchor, const int* q_rel,
+                                  const int* q_dir, const int* q_target, int B, float smoothing,
+                                  float n3, float* gE, float* gR, int* r_touched, float* loss,
+                                  float* scores, float* lse, void* workspace, size_t ws_bytes) {
+  int rc = ova_check("skge_onevsall_grad", model, N, M, d, B, smoothing, n3);
+  if (rc) return rc;
+  SKGE_CHECK_ARG(E && R && q_anchor && q_rel && q_dir && q_target && gE && gR && r_touched && loss,
+                 "skge_onevsall_grad: NULL argument");
+  const OvaPlan p = ova_plan(B, N, M, d);
+  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_onevsall_grad: workspace needs %zu bytes "
+                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, N, M, d);
+  SKGE_CHECK_ARG(((uintptr_t)workspace & 15) == 0 &&
+                     (d % 4 != 0 || (((uintptr_t)E | (uintptr_t)R) & 15) == 0),
+                 "skge_onevsall_grad: the workspace and, at d %% 4 == 0, E and R must be 16-byte "
+                 "aligned");
+  hipStream_t st = as_stream(stream);
+  char* ws = (char*)workspace;
+  float* Q = (float*)(ws + p.o_q);
+  float* G = (float*)(ws + p.o_g);
+  float* part = (float*)(ws + p.o_part);
+  float* rowp = (float*)(ws + p.o_rowp);
+  float* lse_ws = (float*)(ws + p.o_lse);
+  float* lpart = (float*)(ws + p.o_lpart);
+  const size_t nrow = (size_t)p.kv.nby * B;
+  int* occ = n3 > 0.0f ? (int*)(ws + p.o_occ) : nullptr;
+  if (occ) SKGE_CHECK_HIP(hipMemsetAsync(occ, 0, ((size_t)N + M) * sizeof(int), st));
+  SKGE_CHECK_HIP(hipMemsetAsync(gR, 0, (size_t)M * d * sizeof(float), st));
+  SKGE_CHECK_HIP(hipMemsetAsync(r_touched, 0, (size_t)M * sizeof(int), st));
+  const int qblocks = (B + 3) / 4;
+  hipLaunchKernelGGL(k_kv_query, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
+                     q_rel, q_dir, B, Q);
+  KvGemm f = {};
+  f.A = Q;
+  f.lda = d;
+  f.B = E;
+  f.ldb = d;
+  f.Mr = B;
+  f.Nc = N;
+  f.K = d;
+  f.nbx = p.kv.nbx;
+  f.G = G;
+  f.ldg = p.kv.ldg;
+  f.scores = scores;
+  f.pm = rowp;
+  f.ps = rowp + nrow;
+  f.pt = rowp + 2 * nrow;
+  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_OVA>), dim3(p.kv.nbx * p.kv.nby), dim3(256), 0,
+                     st, f);
+  hipLaunchKernelGGL(k_ova_combine, dim3((unsigned)B * (unsigned)p.nsplit), dim3(256), 0, st, G,
+                     p.kv.ldg, N, M, B, (int)p.kv.nby, p.nsplit, p.chunk, f.pm, f.ps, f.pt,
+                     q_anchor, q_rel, q_dir, q_target, smoothing, lse_ws, lse, lpart, occ);
+  KvGemm q = {};   // dq = G E, as skge_kvsall_grad
+  q.A = G;
+  q.lda = p.kv.ldg;
+  q.B = E;
+  q.ldb = d;
+  q.Mr = B;
+  q.Nc = d;
+  q.K = N;
+  q.kslice = p.kv.kslice;
+  q.nbx = p.kv.nbx;
+  q.C = part;
+  const unsigned ntd = (unsigned)((d + KV_T - 1) / KV_T);
+  hipLaunchKernelGGL((k_kv_gemm<false, true, KV_DQ>), dim3(p.kv.nbx * ntd * (unsigned)p.kv.ns),
+                     dim3(256), 0, st, q);
+  KvGemm e = {};   // gE = G^T Q
+  e.A = G;
+  e.lda = p.kv.ldg;
+  e.B = Q;
+  e.ldb = d;
+  e.Mr = N;
+  e.Nc = d;
+  e.K = B;
+  e.nbx = p.kv.nby;
+  e.C = gE;
+  hipLaunchKernelGGL((k_kv_gemm<true, true, KV_DE>), dim3(p.kv.nby * ntd), dim3(256), 0, st, e);
+  if (occ)
+    hipLaunchKernelGGL(k_ova_n3, dim3((unsigned)(((size_t)N + M + 3) / 4)), dim3(256), 0, st, model,
+                       E, R, N, M, d, occ, n3 / (float)B, gE, gR);
+  hipLaunchKernelGGL(k_ova_chain, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
+                     q_rel, q_dir, q_target, B, part, p.kv.ns, n3, gE, gR, r_touched, lpart);
+  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, st, lpart, (unsigned)B, 1.0f / (float)B,
+                     loss);
+  SKGE_CHECK_LAUNCH("onevsall grad");
+  return SKGE_OK;
+}
+
+extern "C" int skge_onevsall_step(void* stream, int model, const skge_table_t* ent,
+                                  const skge_table_t* rel, int d, const int* q_anchor,
+                                  const int* q_rel, const int* q_dir, const int* q_target, int B,
+                                  float smoothing, float n3, float* loss, void* workspace,
+                                  size_t ws_bytes) {
+  int rc = ova_check("skge_onevsall_step", model, ent ? ent->rows : 1, rel ? rel->rows : 1, d, B,
+                     smoothing, n3);
+  if (rc) return rc;
+  if ((rc = check_table(ent, "ent", false)) || (rc = check_table(rel, "rel", false))) return rc;
+  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "skge_onevsall_step: table widths %d / %d, "
+                 "d = %d", ent->width, rel->width, d);
+  const OvaPlan p = ova_plan(B, ent->rows, rel->rows, d);
+  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_onevsall_step: workspace needs %zu bytes "
+                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, ent->rows, rel->rows, d);
+  char* ws = (char*)workspace;
+  float* gE = (float*)(ws + p.o_ge);
+  float* gR = (float*)(ws + p.o_gr);
+  int* touched = (int*)(ws + p.o_touched);
+  rc = skge_onevsall_grad(stream, model, ent->param, rel->param, ent->rows, rel->rows, d, q_anchor,
+                          q_rel, q_dir, q_target, B, smoothing, n3, gE, gR, touched, loss, nullptr,
+                          nullptr, workspace, ws_bytes);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row

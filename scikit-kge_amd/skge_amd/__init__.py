@@ -7,6 +7,7 @@ from .version import __version__
 from .base import (Model, StochasticTrainer, PairwiseStochasticTrainer, SelfAdversarialTrainer,
                    set_deterministic, deterministic)
 from .kvsall import KvsAllTrainer, KvsAllQueries
+from .onevsall import OneVsAllTrainer, OneVsAllQueries
 from .transe import TransE
 from .hole import HolE
 from .rescal import RESCAL

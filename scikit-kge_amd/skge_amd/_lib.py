@@ -155,6 +155,11 @@ SIGNATURES = {
                                c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz]),
     "skge_kvsall_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_f, c_p,
                                c_p, c_sz]),
+    "skge_onevsall_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "skge_onevsall_grad": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_f,
+                                 c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz]),
+    "skge_onevsall_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p,
+                                 c_p, c_sz]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,

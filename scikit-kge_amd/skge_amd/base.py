@@ -364,12 +364,12 @@ class Model(object):
                                        float(self.alpha), L.ptr(loss)), "sadv_step")
 
     # ---- KvsAll / 1-N scoring with binary cross-entropy (DistMult, ComplEx) ----
-    def _require_kvsall(self):
+    def _require_kvsall(self, regime="KvsAll"):
         if self._kernel_model() not in KVSALL_MODELS:
-            raise ValueError("%s has no KvsAll training: scoring a query against every entity "
+            raise ValueError("%s has no %s training: scoring a query against every entity "
                              "with one dot product is served for DistMult and ComplEx; train %s "
                              "with StochasticTrainer or PairwiseStochasticTrainer"
-                             % (type(self).__name__, type(self).__name__))
+                             % (type(self).__name__, regime, type(self).__name__))
 
     def _kvsall_args(self, batch):
         """A KvsAllQueries batch on the model's device, checked, and the
@@ -429,6 +429,69 @@ class Model(object):
             L.ptr(batch.rel), L.ptr(batch.dir), B, L.ptr(batch.off), L.ptr(batch.ans),
             float(getattr(self, "label_smoothing", 0.0)), L.ptr(loss), L.ptr(ws), nbytes),
             "kvsall_step")
+
+    # ---- 1vsAll: softmax cross-entropy against one target, with N3 (DistMult, ComplEx) ----
+    def _onevsall_args(self, batch):
+        """A OneVsAllQueries batch on the model's device, checked, and the
+        workspace of its shape."""
+        self._require_kvsall("1vsAll")
+        B = len(batch)
+        if B < 1 or B > 4096:
+            raise ValueError("1vsAll batch of %d queries; a batch holds 1 to 4096 (raise the "
+                             "trainer's nbatches)" % B)
+        if batch.device != self.device:
+            batch = batch.to(self.device)
+        N, M = self.params["E"].rows, self.params["R"].rows
+        nbytes = L.lib().skge_onevsall_workspace_bytes(self._kernel_model(), B, N, M, self.d)
+        if nbytes == 0:
+            raise L.SkgeError("onevsall: %s" % L.lib().skge_last_error().decode())
+        return batch, B, N, M, self._workspace(nbytes), nbytes
+
+    def _onevsall_gradients(self, batch, scores=False):
+        """1vsAll gradients of a batch of queries (onevsall.OneVsAllQueries), in
+        _kvsall_gradients' form: {"E": (gE [N, d], arange(N)), "R": (rows [U, d],
+        the sorted ids of the relations the batch names)} -- the plain gradient
+        of L = L_ce + L_n3 plus rparam * param -- and sets
+        self.loss = L.  The rows' lse [B] stay in _lse; scores=True keeps the
+        raw z [B, N] in _score."""
+        batch, B, N, M, ws, nbytes = self._onevsall_args(batch)
+        dev, d = self.device, self.d
+        gE = torch.empty((N, d), dtype=torch.float32, device=dev)
+        gR = torch.empty((M, d), dtype=torch.float32, device=dev)
+        touched = torch.empty(M, dtype=torch.int32, device=dev)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._score = torch.empty((B, N), dtype=torch.float32, device=dev) if scores else None
+        self._lse = torch.empty(B, dtype=torch.float32, device=dev)
+        L.check(L.lib().skge_onevsall_grad(
+            L.stream_ptr(), self._kernel_model(), L.ptr(self.params["E"].data),
+            L.ptr(self.params["R"].data), N, M, d, L.ptr(batch.anchor), L.ptr(batch.rel),
+            L.ptr(batch.dir), L.ptr(batch.target), B,
+            float(getattr(self, "label_smoothing", 0.0)), float(getattr(self, "n3", 0.0)),
+            L.ptr(gE), L.ptr(gR), L.ptr(touched), L.ptr(loss), L.ptr(self._score),
+            L.ptr(self._lse), L.ptr(ws), nbytes), "onevsall_grad")
+        self.loss = float(loss.item())
+        ids = torch.nonzero(touched).reshape(-1)
+        rows = gR[ids]
+        reg = self._reg("logistic")
+        for pid, g, idx in (("E", gE, None), ("R", rows, ids)):
+            rin, rout, _ = reg[pid]
+            if rin + rout != 0.0:   # g += rparam * param, as skge_onevsall_step's update does
+                p = self.params[pid].data
+                g.add_(p if idx is None else p[idx], alpha=float(rin + rout))
+        return {"E": (gE, torch.arange(N, device=dev)), "R": (rows, ids)}
+
+    def _onevsall_step(self, batch, updaters, loss):
+        """scores + softmax + loss + gradients + update of a batch of queries in
+        one skge_onevsall_step; the batch's L is added into the device word
+        `loss`."""
+        batch, B, N, M, ws, nbytes = self._onevsall_args(batch)
+        reg = self._reg("logistic")
+        te, tr = [updaters[pid].table(None, rin=reg[pid][0], rout=reg[pid][1]) for pid in ("E", "R")]
+        L.check(L.lib().skge_onevsall_step(
+            L.stream_ptr(), self._kernel_model(), te, tr, self.d, L.ptr(batch.anchor),
+            L.ptr(batch.rel), L.ptr(batch.dir), L.ptr(batch.target), B,
+            float(getattr(self, "label_smoothing", 0.0)), float(getattr(self, "n3", 0.0)),
+            L.ptr(loss), L.ptr(ws), nbytes), "onevsall_step")
 
 
 # the distance models (scores <= 0) the self-adversarial loss is defined for
