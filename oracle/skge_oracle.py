@@ -238,18 +238,44 @@ def hole_pairwise_gradients(E, R, pos, neg, margin, rparam=0.0, af=Sigmoid):
 # ----------------------------------------------------------------------------
 
 
+def _rescal_rows(d):
+    """Rows of a batch whose W[p] are gathered at a time: 32 MB of doubles."""
+    return max(1, (1 << 22) // (d * d))
+
+
+def _rescal_we(E, W, p, o):
+    """W[p_n] E[o_n] per row n.  The rows go through the same einsum a few at a
+    time: all of W[p] at once is n d^2 doubles (433 MB at n = 800, d = 260)."""
+    out = np.empty((len(p), E.shape[1]), dtype=np.result_type(E, W))
+    rows = _rescal_rows(E.shape[1])
+    for i in range(0, len(p), rows):
+        j = slice(i, i + rows)
+        out[j] = np.einsum("nij,nj->ni", W[p[j]], E[o[j]])
+    return out
+
+
+def _rescal_ew(E, W, s, p):
+    """E[s_n] W[p_n] per row n, as _rescal_we."""
+    out = np.empty((len(p), E.shape[1]), dtype=np.result_type(E, W))
+    rows = _rescal_rows(E.shape[1])
+    for i in range(0, len(p), rows):
+        j = slice(i, i + rows)
+        out[j] = np.einsum("ni,nij->nj", E[s[j]], W[p[j]])
+    return out
+
+
 def rescal_scores(E, W, trip):
     """skge/rescal.py:31-35: E[s] . (W[p] E[o])."""
     s, p, o = _split(trip)
-    return np.einsum("nd,nd->n", E[s], np.einsum("nij,nj->ni", W[p], E[o]))
+    return np.einsum("nd,nd->n", E[s], _rescal_we(E, W, p, o))
 
 
 def rescal_gradients(E, W, trip, ys, rparam=0.0):
     """Logistic loss, skge/rescal.py:37-76.  Returns (score, loss, grads)."""
     ss, ps, os_ = _split(trip)
     ys = np.asarray(ys, dtype=np.float64)
-    WE = np.einsum("nij,nj->ni", W[ps], E[os_])
-    EW = np.einsum("ni,nij->nj", E[ss], W[ps])
+    WE = _rescal_we(E, W, ps, os_)
+    EW = _rescal_ew(E, W, ss, ps)
     score = np.sum(E[ss] * WE, axis=1)
     ysc = ys * score
     loss = np.sum(np.logaddexp(0, -ysc))
@@ -270,8 +296,8 @@ def rescal_pairwise_gradients(E, W, pos, neg, margin, rparam=0.0, af=Linear):
     uses ALL pairs; rparam sits inside the entity mean."""
     sp, pp, op = _split(pos)
     sn, pn, on = _split(neg)
-    WEp = np.einsum("nij,nj->ni", W[pp], E[op])
-    WEn = np.einsum("nij,nj->ni", W[pn], E[on])
+    WEp = _rescal_we(E, W, pp, op)
+    WEn = _rescal_we(E, W, pn, on)
     praw = np.sum(E[sp] * WEp, axis=1)
     nraw = np.sum(E[sn] * WEn, axis=1)
     pf, nf = af.f(praw), af.f(nraw)
@@ -290,8 +316,8 @@ def rescal_pairwise_gradients(E, W, pos, neg, margin, rparam=0.0, af=Linear):
         gw[i] += np.dot(E[sn[b]].T, gn[b] * E[on[b]])
         gw[i] += rparam * W[p]
         gw[i] /= 2.0
-    EWp = np.einsum("ni,nij->nj", E[sp[ind]], W[pp[ind]])
-    EWn = np.einsum("ni,nij->nj", E[sn[ind]], W[pn[ind]])
+    EWp = _rescal_ew(E, W, sp[ind], pp[ind])
+    EWn = _rescal_ew(E, W, sn[ind], pn[ind])
     gpi, gni = gp[ind], gn[ind]
     eidx, esum, en = segment_mean(
         np.concatenate([sp[ind], sn[ind], op[ind], on[ind]]),

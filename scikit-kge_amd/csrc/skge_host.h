@@ -72,6 +72,19 @@ inline bool model_known(int model) {
   return (model >= SKGE_TRANSE_L1 && model <= SKGE_RESCAL) || model == SKGE_DISTMULT ||
          model == SKGE_COMPLEX || model == SKGE_ROTATE;
 }
+// a code's name for an error text: the one code-to-name table
+inline const char* model_name(int model) {
+  switch (model) {
+    case SKGE_TRANSE_L1: return "TransE-L1";
+    case SKGE_TRANSE_L2: return "TransE-L2";
+    case SKGE_HOLE: return "HolE";
+    case SKGE_RESCAL: return "RESCAL";
+    case SKGE_DISTMULT: return "DistMult";
+    case SKGE_COMPLEX: return "ComplEx";
+    case SKGE_ROTATE: return "RotatE";
+    default: return "?";
+  }
+}
 // rows of d/2 interleaved complex components: ComplEx and RotatE
 inline bool model_complex_rows(int model) { return model == SKGE_COMPLEX || model == SKGE_ROTATE; }
 // DistMult / ComplEx: HolE's table shapes and slot maps, skge_diag.h's scores

@@ -1,23 +1,31 @@
-// KvsAll (1-N) training of DistMult and ComplEx: every query (anchor a,
-// relation p, direction t) of a batch is scored against EVERY entity row and
-// takes binary cross-entropy against the multi-hot vector of its known answers
-// (include/skge_hip.h, skge_kvsall_grad).  With the query vector
-// q = query_elem(model, t == 0, E_a, R_p) (skge_elem.h) the score of candidate
-// e is the plain dot product z = q . E_e, so one batch is three fp32 GEMMs:
+// 1-N training of DistMult and ComplEx: every query (anchor a, relation p,
+// direction t) of a batch is scored against EVERY entity row.  With the query
+// vector q = query_elem(model, t == 0, E_a, R_p) (skge_elem.h) the score of
+// candidate e is the plain dot product z = q . E_e, so one batch is three fp32
+// GEMMs around G = d L / d z.  The core both regimes run (kv_open, kv_queries,
+// kv_forward, kv_backward, kv_step; one KvPlan lays out the workspace):
 //   k_kv_query    Q [B][d], one wave per query
-//   k_kv_labels   the answers' CSR into a bitmap [B][ceil(N / 32)]
-//   k_kv_gemm<FWD>  Z = Q E^T in 128 x 128 tiles; the epilogue takes sigma, the
-//                 smoothed label and the loss term on the accumulators and
-//                 writes G = (sigma(z) - y') / B (and z, when asked for)
+//   k_kv_gemm     forward: Z = Q E^T in 128 x 128 tiles, the regime's epilogue
+//                 on the accumulators; G [B][ldg] (and z, when asked for)
 //   k_kv_gemm<DQ>   dq = G E, the contraction over the entities cut into
 //                 slices: partial tiles [ns][B][d]
 //   k_kv_gemm<DE>   gE = G^T Q, every row, plain stores
 //   k_kv_chain    one wave per query: dq_b = the slices' partials in slice
 //                 order, then the chain rule into gE[a] and gR[p] (float
 //                 atomics) and the mark of R row p
-//   k_kv_loss     the workgroups' loss partials, in block order, into *loss
-// and skge_kvsall_step follows them with the row updates of skge_update.hip
-// (launch_update_table: E every row, R the marked rows).
+//   k_kv_loss     the loss partials, in order, into *loss
+// and a _step follows them with the row updates of skge_update.hip
+// (launch_update_table: E every row, R the marked rows).  A regime adds:
+//   KvsAll (skge_kvsall_grad), binary cross-entropy against the
+//   multi-hot vector of a query's known answers: k_kv_labels turns the answers'
+//   CSR into a bitmap [B][ceil(N / 32)]; the <FWD> epilogue takes sigma, the
+//   smoothed label and the loss term and writes G = (sigma(z) - y') / B and one
+//   loss partial per workgroup.
+//   1vsAll (skge_onevsall_grad), softmax cross-entropy against
+//   one target per query, with N3: the <OVA> epilogue leaves raw z and starts
+//   the reduction across a score row, k_ova_combine finishes it, rewrites G and
+//   leaves one loss partial per query; k_ova_n3 adds the N3 gradient;
+//   k_kv_chain<true> checks the target too and adds the N3 norms; see "1vsAll".
 //
 // One tile kernel serves the three products.  An operand is read either in ROW
 // form (the contraction index runs along its rows: Q and E in FWD, G in DQ) and
@@ -25,12 +33,6 @@
 // (skge_neighbours.hip), or in K-MAJOR form (the contraction index is its row
 // index: E in DQ, G and Q in DE) and stored as loaded.  Either way the LDS
 // image is k-major and a lane reads one dword per MFMA operand.
-//
-// 1vsAll (skge_onevsall_grad) shares the query vectors, the
-// tile kernel and the loss sum: softmax cross-entropy against one target per
-// query needs a reduction across a score row, which k_kv_gemm<OVA> starts on
-// the accumulators (per row and column tile) and k_ova_combine finishes; see
-// "1vsAll" below.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -373,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void k_kv_gemm(KvGemm a) {
   }
 }
 
-// ---- chain rule: one wave per query ----
+// ---- chain rule: the arithmetic of a query's wave (k_kv_chain, below n3_elem) ----
 // dq_b = sum over the slices, in slice order, of the DQ partials; then
 //   DistMult        gE[a] += dq o R_p           gR[p] += dq o E_a
 //   ComplEx tails   gE[a] += dq conj(R_p)       gR[p] += dq conj(E_a)
@@ -408,37 +410,6 @@ __device__ __forceinline__ void kv_chain_elem(int model, int t, const float* dq,
   }
 }
 
-__global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __restrict__ E,
-                                                  const float* __restrict__ R, int N, int M, int d,
-                                                  const int* __restrict__ qa,
-                                                  const int* __restrict__ qp,
-                                                  const int* __restrict__ qt, int B,
-                                                  const float* __restrict__ part, int ns,
-                                                  float* __restrict__ gE, float* __restrict__ gR,
-                                                  int* __restrict__ r_touched) {
-  __shared__ float s_dq[4][KV_DMAX];
-  const int w = threadIdx.x >> 6, l = lane_id();
-  const int b = blockIdx.x * 4 + w;
-  const bool live = b < B;
-  const int a = live ? qa[b] : -1, p = live ? qp[b] : -1, t = live ? qt[b] : 0;
-  const bool ok = live && kv_query_ok(a, p, t, N, M);
-  if (ok) kv_dq_sum(part, ns, B, b, d, l, s_dq[w]);
-  __syncthreads();
-  if (!ok) return;
-  const float* ea = E + (size_t)a * d;
-  const float* rp = R + (size_t)p * d;
-  float* ge = gE + (size_t)a * d;
-  float* gr = gR + (size_t)p * d;
-  const float* dq = s_dq[w];
-  for (int k = l; k < d; k += 64) {
-    float va, vr;
-    kv_chain_elem(model, t, dq, ea, rp, k, va, vr);
-    atomicAdd(ge + k, va);
-    atomicAdd(gr + k, vr);
-  }
-  if (l == 0) r_touched[p] = 1;
-}
-
 // ---- the loss: the partials in block order, one workgroup ----
 __global__ __launch_bounds__(256) void k_kv_loss(const float* __restrict__ lpart, unsigned n,
                                                  float inv_b, float* __restrict__ loss) {
@@ -459,7 +430,7 @@ __global__ __launch_bounds__(256) void k_kv_loss(const float* __restrict__ lpart
 // target g; the forward is k_kv_gemm<OVA>, which leaves raw z in G and each
 // row's (max, sum exp, sum z) per column tile; k_ova_combine turns them into
 // lse_b and the loss term and rewrites G to (softmax - y') / B; the DQ and DE
-// products, k_kv_loss and the updates are KvsAll's.
+// products, the chain rule, k_kv_loss and the updates are the core's.
 __device__ __forceinline__ bool ova_query_ok(int a, int p, int t, int g, int N, int M) {
   return kv_query_ok(a, p, t, N, M) && g >= 0 && g < N;
 }
@@ -596,28 +567,38 @@ __global__ __launch_bounds__(256) void k_ova_n3(int model, const float* __restri
   for (int k = l; k < d; k += 64) g[k] = fmaf(w, n3_elem(model, x, k, norm), g[k]);
 }
 
-// k_kv_chain with a target: the same chain rule, and at n3 > 0 the query's
-// n3 (|E_a|_3^3 + |R_p|_3^3 + |E_g|_3^3) into its loss partial (the N3 gradient
-// is k_ova_n3's).  An invalid query (target included) adds nothing and marks
-// nothing.
-__global__ __launch_bounds__(256) void k_ova_chain(int model, const float* __restrict__ E,
-                                                   const float* __restrict__ R, int N, int M, int d,
-                                                   const int* __restrict__ qa,
-                                                   const int* __restrict__ qp,
-                                                   const int* __restrict__ qt,
-                                                   const int* __restrict__ qg, int B,
-                                                   const float* __restrict__ part, int ns,
-                                                   float n3, float* __restrict__ gE,
-                                                   float* __restrict__ gR,
-                                                   int* __restrict__ r_touched,
-                                                   float* __restrict__ lpart) {
+// ---- the chain kernel: one wave per query, one template for both regimes ----
+// dq_b into s_dq (kv_dq_sum), then kv_chain_elem's rows into gE[a] and gR[p]
+// with float atomics and the mark of R row p.  An invalid query adds nothing
+// and marks nothing.  TARGET (1vsAll): the query carries a target g, which
+// must be a row of E too, and at n3 > 0 its n3 (|E_a|_3^3 + |R_p|_3^3 +
+// |E_g|_3^3) joins its loss partial (the N3 gradient is k_ova_n3's).  Without
+// TARGET (KvsAll) qg, n3 and lpart are not read and none of that code exists.
+template <bool TARGET>
+__global__ __launch_bounds__(256) void k_kv_chain(int model, const float* __restrict__ E,
+                                                  const float* __restrict__ R, int N, int M, int d,
+                                                  const int* __restrict__ qa,
+                                                  const int* __restrict__ qp,
+                                                  const int* __restrict__ qt,
+                                                  const int* __restrict__ qg, int B,
+                                                  const float* __restrict__ part, int ns,
+                                                  float n3, float* __restrict__ gE,
+                                                  float* __restrict__ gR,
+                                                  int* __restrict__ r_touched,
+                                                  float* __restrict__ lpart) {
   __shared__ float s_dq[4][KV_DMAX];
   const int w = threadIdx.x >> 6, l = lane_id();
   const int b = blockIdx.x * 4 + w;
   const bool live = b < B;
   const int a = live ? qa[b] : -1, p = live ? qp[b] : -1, t = live ? qt[b] : 0;
-  const int g = live ? qg[b] : -1;
-  const bool ok = live && ova_query_ok(a, p, t, g, N, M);
+  int g = 0;
+  bool ok;
+  if constexpr (TARGET) {
+    g = live ? qg[b] : -1;
+    ok = live && ova_query_ok(a, p, t, g, N, M);
+  } else {
+    ok = live && kv_query_ok(a, p, t, N, M);
+  }
   if (ok) kv_dq_sum(part, ns, B, b, d, l, s_dq[w]);
   __syncthreads();
   if (!ok) return;
@@ -631,55 +612,85 @@ __global__ __launch_bounds__(256) void k_ova_chain(int model, const float* __res
   for (int k = l; k < d; k += 64) {
     float va, vr;
     kv_chain_elem(model, t, dq, ea, rp, k, va, vr);
-    if (n3 > 0.0f) {
-      n3_elem(model, ea, k, norm);
-      n3_elem(model, rp, k, norm);
-      n3_elem(model, eg, k, norm);
+    if constexpr (TARGET) {
+      if (n3 > 0.0f) {
+        n3_elem(model, ea, k, norm);
+        n3_elem(model, rp, k, norm);
+        n3_elem(model, eg, k, norm);
+      }
     }
     atomicAdd(ge + k, va);
     atomicAdd(gr + k, vr);
   }
-  if (n3 > 0.0f) {   // wave-uniform
-    norm = wave_sum(norm);
-    if (l == 0) lpart[b] += n3 * norm;
+  if constexpr (TARGET) {
+    if (n3 > 0.0f) {   // wave-uniform
+      norm = wave_sum(norm);
+      if (l == 0) lpart[b] += n3 * norm;
+    }
   }
   if (l == 0) r_touched[p] = 1;
 }
+
+// ==== the host side: one plan, one check, one launch sequence ====
+enum { KV_KVSALL = 0, KV_ONEVSALL = 1 };   // the regime
 
 // ---- plan and workspace ----
 struct KvPlan {
   size_t ldg;            // G's row pitch: N rounded up to 4 (16-byte rows)
   int wpr;               // bitmap words per query
-  unsigned nbx, nby;     // FWD tiles
+  unsigned nbx, nby;     // forward tiles
   int kslice, ns;        // DQ slices of the entities
-  size_t o_q, o_bits, o_g, o_part, o_lpart, o_ge, o_gr, o_touched, total;
+  int nsplit, chunk;     // 1vsAll, k_ova_combine: workgroups per query, columns per workgroup
+  size_t o_q, o_g, o_part, o_lpart, o_ge, o_gr, o_touched;   // both regimes
+  size_t o_bits;                                             // KvsAll
+  size_t o_rowp, o_lse, o_occ;                               // 1vsAll
+  size_t total;
 };
 
-static KvPlan kv_plan(int B, int N, int M, int d) {
-  KvPlan p;
+// A regime's arena holds its own buffers only; lpart is one float per forward
+// workgroup (KvsAll) or per query (1vsAll).  Q, G, the partials and the
+// gradients lie where each regime has always had them.
+static KvPlan kv_plan(int regime, int B, int N, int M, int d) {
+  KvPlan p = {};
   p.ldg = ((size_t)N + 3) & ~(size_t)3;
   p.wpr = (int)(((long long)N + 31) / 32);
   p.nbx = (unsigned)((B + KV_T - 1) / KV_T);
   p.nby = (unsigned)(((long long)N + KV_T - 1) / KV_T);
-  // DQ: about 512 workgroups, the partials at most 16 MB
-  const long long tiles = (long long)p.nbx * ((d + KV_T - 1) / KV_T);
-  const long long chunks = ((long long)N + KV_KC - 1) / KV_KC;
-  const long long cap = std::max<long long>(1, (16ll << 20) / ((long long)B * d * 4));
-  const long long want = std::max<long long>(1, std::min({chunks, (512 + tiles - 1) / tiles, cap}));
-  const long long per = (chunks + want - 1) / want;
-  p.kslice = (int)std::min<long long>(per * KV_KC, 1ll << 30);
-  p.ns = (int)((chunks + per - 1) / per);
+  {   // DQ: about 512 workgroups, the partials at most 16 MB
+    const long long tiles = (long long)p.nbx * ((d + KV_T - 1) / KV_T);
+    const long long chunks = ((long long)N + KV_KC - 1) / KV_KC;
+    const long long cap = std::max<long long>(1, (16ll << 20) / ((long long)B * d * 4));
+    const long long want =
+        std::max<long long>(1, std::min({chunks, (512 + tiles - 1) / tiles, cap}));
+    const long long per = (chunks + want - 1) / want;
+    p.kslice = (int)std::min<long long>(per * KV_KC, 1ll << 30);
+    p.ns = (int)((chunks + per - 1) / per);
+  }
+  if (regime == KV_ONEVSALL) {
+    // about 1024 workgroups, none with fewer than 1024 columns (but one per query)
+    const long long want = std::max<long long>(
+        1, std::min<long long>((1024 + B - 1) / B, ((long long)N + 1023) / 1024));
+    const long long per = (((long long)N + want - 1) / want + 3) & ~3ll;
+    p.chunk = (int)std::min<long long>(per, (1ll << 31) - 4);
+    p.nsplit = (int)(((long long)N + p.chunk - 1) / p.chunk);
+  }
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
     o += align256(bytes);
     return at;
   };
+  const bool ova = regime == KV_ONEVSALL;
   p.o_q = take((size_t)B * d * sizeof(float));
-  p.o_bits = take((size_t)B * p.wpr * sizeof(unsigned));
+  if (!ova) p.o_bits = take((size_t)B * p.wpr * sizeof(unsigned));
   p.o_g = take((size_t)B * p.ldg * sizeof(float));
   p.o_part = take((size_t)p.ns * B * d * sizeof(float));
-  p.o_lpart = take((size_t)p.nbx * (size_t)p.nby * sizeof(float));
+  if (ova) {
+    p.o_rowp = take((size_t)3 * p.nby * B * sizeof(float));
+    p.o_lse = take((size_t)B * sizeof(float));
+    p.o_occ = take(((size_t)N + M) * sizeof(int));
+  }
+  p.o_lpart = take((ova ? (size_t)B : (size_t)p.nbx * p.nby) * sizeof(float));
   p.o_ge = take((size_t)N * d * sizeof(float));
   p.o_gr = take((size_t)M * d * sizeof(float));
   p.o_touched = take((size_t)M * sizeof(int));
@@ -687,24 +698,14 @@ static KvPlan kv_plan(int B, int N, int M, int d) {
   return p;
 }
 
-static const char* kv_model_name(int model) {
-  switch (model) {
-    case SKGE_TRANSE_L1: return "TransE-L1";
-    case SKGE_TRANSE_L2: return "TransE-L2";
-    case SKGE_HOLE: return "HolE";
-    case SKGE_RESCAL: return "RESCAL";
-    case SKGE_ROTATE: return "RotatE";
-    default: return "?";
-  }
-}
-
-// what both entry points refuse before any launch
-static int kv_check(const char* who, int model, int N, int M, int d, int B, float smoothing) {
+// what every entry point refuses before any launch; n3 is 1vsAll's (KvsAll: 0)
+static int kv_check(const char* who, int regime, int model, int N, int M, int d, int B,
+                    float smoothing, float n3) {
   SKGE_CHECK_ARG(model_known(model), "%s: unknown model %d", who, model);
   if (!model_diag(model)) {
-    set_error("%s: model %d (%s) is not served: KvsAll scores a query against every entity with "
-              "one dot product, which DistMult and ComplEx allow", who, model,
-              kv_model_name(model));
+    set_error("%s: model %d (%s) is not served: %s scores a query against every entity with "
+              "one dot product, which DistMult and ComplEx allow", who, model, model_name(model),
+              regime == KV_ONEVSALL ? "1vsAll" : "KvsAll");
     return SKGE_ENOTSUP;
   }
   SKGE_CHECK_ARG(N >= 1 && M >= 1 && d >= 1 && B >= 1, "%s: bad sizes (N = %d, M = %d, d = %d, "
@@ -716,68 +717,150 @@ static int kv_check(const char* who, int model, int N, int M, int d, int B, floa
   SKGE_CHECK_ARG(model != SKGE_COMPLEX || d % 2 == 0, "%s: ComplEx needs an even d (%d)", who, d);
   SKGE_CHECK_ARG(smoothing >= 0.0f && smoothing < 1.0f, "%s: label smoothing %g outside [0, 1)",
                  who, (double)smoothing);
-  return SKGE_OK;
-}
-
-// ---- 1vsAll: plan and checks ----
-struct OvaPlan {
-  KvPlan kv;             // ldg, the FWD tiles and the DQ slices are KvsAll's
-  int nsplit, chunk;     // k_ova_combine: workgroups per query, columns per workgroup
-  size_t o_q, o_g, o_part, o_rowp, o_lse, o_lpart, o_occ, o_ge, o_gr, o_touched, total;
-};
-
-static OvaPlan ova_plan(int B, int N, int M, int d) {
-  OvaPlan p;
-  p.kv = kv_plan(B, N, M, d);
-  // about 1024 workgroups, none with fewer than 1024 columns (but one per query)
-  const long long want = std::max<long long>(1, std::min<long long>((1024 + B - 1) / B,
-                                                                    ((long long)N + 1023) / 1024));
-  const long long per = (((long long)N + want - 1) / want + 3) & ~3ll;
-  p.chunk = (int)std::min<long long>(per, (1ll << 31) - 4);
-  p.nsplit = (int)(((long long)N + p.chunk - 1) / p.chunk);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  p.o_q = take((size_t)B * d * sizeof(float));
-  p.o_g = take((size_t)B * p.kv.ldg * sizeof(float));
-  p.o_part = take((size_t)p.kv.ns * B * d * sizeof(float));
-  p.o_rowp = take((size_t)3 * p.kv.nby * B * sizeof(float));
-  p.o_lse = take((size_t)B * sizeof(float));
-  p.o_lpart = take((size_t)B * sizeof(float));
-  p.o_occ = take(((size_t)N + M) * sizeof(int));
-  p.o_ge = take((size_t)N * d * sizeof(float));
-  p.o_gr = take((size_t)M * d * sizeof(float));
-  p.o_touched = take((size_t)M * sizeof(int));
-  p.total = o;
-  return p;
-}
-
-static int ova_check(const char* who, int model, int N, int M, int d, int B, float smoothing,
-                     float n3) {
-  SKGE_CHECK_ARG(model_known(model), "%s: unknown model %d", who, model);
-  if (!model_diag(model)) {
-    set_error("%s: model %d (%s) is not served: 1vsAll scores a query against every entity with "
-              "one dot product, which DistMult and ComplEx allow", who, model,
-              kv_model_name(model));
-    return SKGE_ENOTSUP;
-  }
-  int rc = kv_check(who, model, N, M, d, B, smoothing);
-  if (rc) return rc;
   SKGE_CHECK_ARG(n3 >= 0.0f && std::isfinite(n3), "%s: N3 weight %g is negative or not finite", who,
                  (double)n3);
   return SKGE_OK;
+}
+
+static int kv_check_workspace(const char* who, const KvPlan& p, const void* workspace,
+                              size_t ws_bytes, int B, int N, int M, int d) {
+  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "%s: workspace needs %zu bytes (B = %d, "
+                 "N = %d, M = %d, d = %d)", who, p.total, B, N, M, d);
+  return SKGE_OK;
+}
+
+// ---- a batch: the arguments both _grad entry points take, then what kv_open
+// derives from them ----
+struct KvBatch {
+  hipStream_t st;
+  int model;
+  const float *E, *R;
+  int N, M, d;
+  const int *qa, *qp, *qt;
+  int B;
+  float *gE, *gR;
+  int* touched;
+  float* loss;
+  KvPlan p;
+  char* ws;
+  float *Q, *G, *part, *lpart;   // the workspace parts of both regimes
+  unsigned qblocks;              // one wave per query, four to a workgroup
+};
+
+// The checks of a _grad entry point `who`, in the order the refusals are
+// documented in; own_ok: the regime's own pointer arguments are not NULL.
+static int kv_open(KvBatch& b, const char* who, int regime, bool own_ok, float smoothing, float n3,
+                   void* workspace, size_t ws_bytes) {
+  int rc = kv_check(who, regime, b.model, b.N, b.M, b.d, b.B, smoothing, n3);
+  if (rc) return rc;
+  SKGE_CHECK_ARG(b.E && b.R && b.qa && b.qp && b.qt && own_ok && b.gE && b.gR && b.touched &&
+                     b.loss, "%s: NULL argument", who);
+  b.p = kv_plan(regime, b.B, b.N, b.M, b.d);
+  if ((rc = kv_check_workspace(who, b.p, workspace, ws_bytes, b.B, b.N, b.M, b.d))) return rc;
+  SKGE_CHECK_ARG(((uintptr_t)workspace & 15) == 0 &&
+                     (b.d % 4 != 0 || (((uintptr_t)b.E | (uintptr_t)b.R) & 15) == 0),
+                 "%s: the workspace and, at d %% 4 == 0, E and R must be 16-byte aligned", who);
+  b.ws = (char*)workspace;
+  b.Q = (float*)(b.ws + b.p.o_q);
+  b.G = (float*)(b.ws + b.p.o_g);
+  b.part = (float*)(b.ws + b.p.o_part);
+  b.lpart = (float*)(b.ws + b.p.o_lpart);
+  b.qblocks = (unsigned)((b.B + 3) / 4);
+  return SKGE_OK;
+}
+
+// gR and the marks cleared (gE is the DE product's plain stores), then Q
+static int kv_queries(const KvBatch& b) {
+  SKGE_CHECK_HIP(hipMemsetAsync(b.gR, 0, (size_t)b.M * b.d * sizeof(float), b.st));
+  SKGE_CHECK_HIP(hipMemsetAsync(b.touched, 0, (size_t)b.M * sizeof(int), b.st));
+  hipLaunchKernelGGL(k_kv_query, dim3(b.qblocks), dim3(256), 0, b.st, b.model, b.E, b.R, b.N, b.M,
+                     b.d, b.qa, b.qp, b.qt, b.B, b.Q);
+  return SKGE_OK;
+}
+
+// Z = Q E^T into G (and scores): the forward's operands; the epilogue's fields
+// are the regime's
+static KvGemm kv_forward(const KvBatch& b, float* scores) {
+  KvGemm f = {};
+  f.A = b.Q;
+  f.lda = b.d;
+  f.B = b.E;
+  f.ldb = b.d;
+  f.Mr = b.B;
+  f.Nc = b.N;
+  f.K = b.d;
+  f.nbx = b.p.nbx;
+  f.G = b.G;
+  f.ldg = b.p.ldg;
+  f.scores = scores;
+  return f;
+}
+
+// the two products of G: the slices' partials of dq, and gE
+static void kv_backward(const KvBatch& b) {
+  const KvPlan& p = b.p;
+  KvGemm q = {};   // dq = G E: rows the queries, columns the dims, over the entities
+  q.A = b.G;
+  q.lda = p.ldg;
+  q.B = b.E;
+  q.ldb = b.d;
+  q.Mr = b.B;
+  q.Nc = b.d;
+  q.K = b.N;
+  q.kslice = p.kslice;
+  q.nbx = p.nbx;
+  q.C = b.part;
+  const unsigned ntd = (unsigned)((b.d + KV_T - 1) / KV_T);
+  hipLaunchKernelGGL((k_kv_gemm<false, true, KV_DQ>), dim3(p.nbx * ntd * (unsigned)p.ns),
+                     dim3(256), 0, b.st, q);
+  KvGemm e = {};   // gE = G^T Q: rows the entities, columns the dims, over the queries
+  e.A = b.G;
+  e.lda = p.ldg;
+  e.B = b.Q;
+  e.ldb = b.d;
+  e.Mr = b.N;
+  e.Nc = b.d;
+  e.K = b.B;
+  e.nbx = p.nby;
+  e.C = b.gE;
+  hipLaunchKernelGGL((k_kv_gemm<true, true, KV_DE>), dim3(p.nby * ntd), dim3(256), 0, b.st, e);
+}
+
+// A _step entry point `who`: the tables checked, grad(gE, gR, touched) -- the
+// regime's _grad into the workspace's own gradient buffers -- and the row
+// updates of skge_update.hip.
+template <class Grad>
+static int kv_step(const char* who, int regime, void* stream, int model, const skge_table_t* ent,
+                   const skge_table_t* rel, int d, int B, float smoothing, float n3,
+                   void* workspace, size_t ws_bytes, Grad grad) {
+  int rc = kv_check(who, regime, model, ent ? ent->rows : 1, rel ? rel->rows : 1, d, B, smoothing,
+                    n3);
+  if (rc) return rc;
+  if ((rc = check_table(ent, "ent", false)) || (rc = check_table(rel, "rel", false))) return rc;
+  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "%s: table widths %d / %d, d = %d", who,
+                 ent->width, rel->width, d);
+  const KvPlan p = kv_plan(regime, B, ent->rows, rel->rows, d);
+  if ((rc = kv_check_workspace(who, p, workspace, ws_bytes, B, ent->rows, rel->rows, d))) return rc;
+  char* ws = (char*)workspace;
+  float* gE = (float*)(ws + p.o_ge);
+  float* gR = (float*)(ws + p.o_gr);
+  int* touched = (int*)(ws + p.o_touched);
+  if ((rc = grad(gE, gR, touched))) return rc;
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row
+  return launch_update_table(st, rel, gR, touched);                   // the rows a query names
 }
 
 }  // namespace skge
 
 using namespace skge;
 
+// ---- KvsAll: the answers' bitmap, the BCE epilogue, one loss partial per
+// forward workgroup ----
 extern "C" size_t skge_kvsall_workspace_bytes(int model, int B, int N, int M, int d) {
-  if (kv_check("skge_kvsall_workspace_bytes", model, N, M, d, B, 0.0f) != SKGE_OK) return 0;
-  return kv_plan(B, N, M, d).total;
+  if (kv_check("skge_kvsall_workspace_bytes", KV_KVSALL, model, N, M, d, B, 0.0f, 0.0f) != SKGE_OK)
+    return 0;
+  return kv_plan(KV_KVSALL, B, N, M, d).total;
 }
 
 extern "C" int skge_kvsall_grad(void* stream, int model, const float* E, const float* R, int N,
@@ -785,80 +868,31 @@ extern "C" int skge_kvsall_grad(void* stream, int model, const float* E, const f
                                 const int* q_dir, int B, const int* ans_off, const int* ans_ids,
                                 float smoothing, float* gE, float* gR, int* r_touched, float* loss,
                                 float* scores, void* workspace, size_t ws_bytes) {
-  int rc = kv_check("skge_kvsall_grad", model, N, M, d, B, smoothing);
+  KvBatch b = {as_stream(stream), model, E, R, N, M, d, q_anchor, q_rel, q_dir, B, gE, gR,
+               r_touched, loss};
+  int rc = kv_open(b, "skge_kvsall_grad", KV_KVSALL, ans_off && ans_ids, smoothing, 0.0f, workspace,
+                   ws_bytes);
   if (rc) return rc;
-  SKGE_CHECK_ARG(E && R && q_anchor && q_rel && q_dir && ans_off && ans_ids && gE && gR &&
-                     r_touched && loss, "skge_kvsall_grad: NULL argument");
-  const KvPlan p = kv_plan(B, N, M, d);
-  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_kvsall_grad: workspace needs %zu bytes "
-                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, N, M, d);
-  SKGE_CHECK_ARG(((uintptr_t)workspace & 15) == 0 &&
-                     (d % 4 != 0 || (((uintptr_t)E | (uintptr_t)R) & 15) == 0),
-                 "skge_kvsall_grad: the workspace and, at d %% 4 == 0, E and R must be 16-byte "
-                 "aligned");
-  hipStream_t st = as_stream(stream);
-  char* ws = (char*)workspace;
-  float* Q = (float*)(ws + p.o_q);
-  unsigned* bits = (unsigned*)(ws + p.o_bits);
-  float* G = (float*)(ws + p.o_g);
-  float* part = (float*)(ws + p.o_part);
-  float* lpart = (float*)(ws + p.o_lpart);
-  SKGE_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)B * p.wpr * sizeof(unsigned), st));
-  SKGE_CHECK_HIP(hipMemsetAsync(gR, 0, (size_t)M * d * sizeof(float), st));
-  SKGE_CHECK_HIP(hipMemsetAsync(r_touched, 0, (size_t)M * sizeof(int), st));
-  const int qblocks = (B + 3) / 4;
-  hipLaunchKernelGGL(k_kv_query, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
-                     q_rel, q_dir, B, Q);
-  hipLaunchKernelGGL(k_kv_labels, dim3(qblocks), dim3(256), 0, st, ans_off, ans_ids, B, N, p.wpr,
-                     bits);
-  KvGemm f = {};
-  f.A = Q;
-  f.lda = d;
-  f.B = E;
-  f.ldb = d;
-  f.Mr = B;
-  f.Nc = N;
-  f.K = d;
-  f.nbx = p.nbx;
-  f.G = G;
-  f.ldg = p.ldg;
-  f.scores = scores;
+  const KvPlan& p = b.p;
+  unsigned* bits = (unsigned*)(b.ws + p.o_bits);
+  SKGE_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)B * p.wpr * sizeof(unsigned), b.st));
+  if ((rc = kv_queries(b))) return rc;
+  hipLaunchKernelGGL(k_kv_labels, dim3(b.qblocks), dim3(256), 0, b.st, ans_off, ans_ids, B, N,
+                     p.wpr, bits);
+  KvGemm f = kv_forward(b, scores);
   f.bits = bits;
   f.wpr = p.wpr;
   f.eps = smoothing;
   f.eps_n = smoothing / (float)N;
   f.inv_b = 1.0f / (float)B;
-  f.lpart = lpart;
+  f.lpart = b.lpart;
   const unsigned nfwd = p.nbx * p.nby;
-  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_FWD>), dim3(nfwd), dim3(256), 0, st, f);
-  KvGemm q = {};   // dq = G E: rows the queries, columns the dims, over the entities
-  q.A = G;
-  q.lda = p.ldg;
-  q.B = E;
-  q.ldb = d;
-  q.Mr = B;
-  q.Nc = d;
-  q.K = N;
-  q.kslice = p.kslice;
-  q.nbx = p.nbx;
-  q.C = part;
-  const unsigned ntd = (unsigned)((d + KV_T - 1) / KV_T);
-  hipLaunchKernelGGL((k_kv_gemm<false, true, KV_DQ>), dim3(p.nbx * ntd * (unsigned)p.ns),
-                     dim3(256), 0, st, q);
-  KvGemm e = {};   // gE = G^T Q: rows the entities, columns the dims, over the queries
-  e.A = G;
-  e.lda = p.ldg;
-  e.B = Q;
-  e.ldb = d;
-  e.Mr = N;
-  e.Nc = d;
-  e.K = B;
-  e.nbx = p.nby;
-  e.C = gE;
-  hipLaunchKernelGGL((k_kv_gemm<true, true, KV_DE>), dim3(p.nby * ntd), dim3(256), 0, st, e);
-  hipLaunchKernelGGL(k_kv_chain, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
-                     q_rel, q_dir, B, part, p.ns, gE, gR, r_touched);
-  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, st, lpart, nfwd, f.inv_b, loss);
+  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_FWD>), dim3(nfwd), dim3(256), 0, b.st, f);
+  kv_backward(b);
+  hipLaunchKernelGGL(k_kv_chain<false>, dim3(b.qblocks), dim3(256), 0, b.st, model, E, R, N, M, d,
+                     q_anchor, q_rel, q_dir, nullptr, B, b.part, p.ns, 0.0f, gE, gR, r_touched,
+                     nullptr);
+  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, b.st, b.lpart, nfwd, f.inv_b, loss);
   SKGE_CHECK_LAUNCH("kvsall grad");
   return SKGE_OK;
 }
@@ -868,33 +902,22 @@ extern "C" int skge_kvsall_step(void* stream, int model, const skge_table_t* ent
                                 const int* q_rel, const int* q_dir, int B, const int* ans_off,
                                 const int* ans_ids, float smoothing, float* loss, void* workspace,
                                 size_t ws_bytes) {
-  int rc = kv_check("skge_kvsall_step", model, ent ? ent->rows : 1, rel ? rel->rows : 1, d, B,
-                    smoothing);
-  if (rc) return rc;
-  if ((rc = check_table(ent, "ent", false)) || (rc = check_table(rel, "rel", false))) return rc;
-  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "skge_kvsall_step: table widths %d / %d, "
-                 "d = %d", ent->width, rel->width, d);
-  const KvPlan p = kv_plan(B, ent->rows, rel->rows, d);
-  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_kvsall_step: workspace needs %zu bytes "
-                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, ent->rows, rel->rows, d);
-  char* ws = (char*)workspace;
-  float* gE = (float*)(ws + p.o_ge);
-  float* gR = (float*)(ws + p.o_gr);
-  int* touched = (int*)(ws + p.o_touched);
-  rc = skge_kvsall_grad(stream, model, ent->param, rel->param, ent->rows, rel->rows, d, q_anchor,
-                        q_rel, q_dir, B, ans_off, ans_ids, smoothing, gE, gR, touched, loss,
-                        nullptr, workspace, ws_bytes);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row
-  return launch_update_table(st, rel, gR, touched);                   // the rows a query names
+  return kv_step("skge_kvsall_step", KV_KVSALL, stream, model, ent, rel, d, B, smoothing, 0.0f,
+                 workspace, ws_bytes, [&](float* gE, float* gR, int* touched) {
+                   return skge_kvsall_grad(stream, model, ent->param, rel->param, ent->rows,
+                                           rel->rows, d, q_anchor, q_rel, q_dir, B, ans_off,
+                                           ans_ids, smoothing, gE, gR, touched, loss, nullptr,
+                                           workspace, ws_bytes);
+                 });
 }
 
-// ---- 1vsAll entry points ----
+// ---- 1vsAll: the softmax partials and their combine, the N3 counts and
+// gradient, one loss partial per query ----
 extern "C" size_t skge_onevsall_workspace_bytes(int model, int B, int N, int M, int d) {
-  if (ova_check("skge_onevsall_workspace_bytes", model, N, M, d, B, 0.0f, 0.0f) != SKGE_OK)
+  if (kv_check("skge_onevsall_workspace_bytes", KV_ONEVSALL, model, N, M, d, B, 0.0f, 0.0f) !=
+      SKGE_OK)
     return 0;
-  return ova_plan(B, N, M, d).total;
+  return kv_plan(KV_ONEVSALL, B, N, M, d).total;
 }
 
 extern "C" int skge_onevsall_grad(void* stream, int model, const float* E, const float* R, int N,
@@ -902,84 +925,33 @@ extern "C" int skge_onevsall_grad(void* stream, int model, const float* E, const
                                   const int* q_dir, const int* q_target, int B, float smoothing,
                                   float n3, float* gE, float* gR, int* r_touched, float* loss,
                                   float* scores, float* lse, void* workspace, size_t ws_bytes) {
-  int rc = ova_check("skge_onevsall_grad", model, N, M, d, B, smoothing, n3);
+  KvBatch b = {as_stream(stream), model, E, R, N, M, d, q_anchor, q_rel, q_dir, B, gE, gR,
+               r_touched, loss};
+  int rc = kv_open(b, "skge_onevsall_grad", KV_ONEVSALL, q_target != nullptr, smoothing, n3,
+                   workspace, ws_bytes);
   if (rc) return rc;
-  SKGE_CHECK_ARG(E && R && q_anchor && q_rel && q_dir && q_target && gE && gR && r_touched && loss,
-                 "skge_onevsall_grad: NULL argument");
-  const OvaPlan p = ova_plan(B, N, M, d);
-  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_onevsall_grad: workspace needs %zu bytes "
-                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, N, M, d);
-  SKGE_CHECK_ARG(((uintptr_t)workspace & 15) == 0 &&
-                     (d % 4 != 0 || (((uintptr_t)E | (uintptr_t)R) & 15) == 0),
-                 "skge_onevsall_grad: the workspace and, at d %% 4 == 0, E and R must be 16-byte "
-                 "aligned");
-  hipStream_t st = as_stream(stream);
-  char* ws = (char*)workspace;
-  float* Q = (float*)(ws + p.o_q);
-  float* G = (float*)(ws + p.o_g);
-  float* part = (float*)(ws + p.o_part);
-  float* rowp = (float*)(ws + p.o_rowp);
-  float* lse_ws = (float*)(ws + p.o_lse);
-  float* lpart = (float*)(ws + p.o_lpart);
-  const size_t nrow = (size_t)p.kv.nby * B;
-  int* occ = n3 > 0.0f ? (int*)(ws + p.o_occ) : nullptr;
-  if (occ) SKGE_CHECK_HIP(hipMemsetAsync(occ, 0, ((size_t)N + M) * sizeof(int), st));
-  SKGE_CHECK_HIP(hipMemsetAsync(gR, 0, (size_t)M * d * sizeof(float), st));
-  SKGE_CHECK_HIP(hipMemsetAsync(r_touched, 0, (size_t)M * sizeof(int), st));
-  const int qblocks = (B + 3) / 4;
-  hipLaunchKernelGGL(k_kv_query, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
-                     q_rel, q_dir, B, Q);
-  KvGemm f = {};
-  f.A = Q;
-  f.lda = d;
-  f.B = E;
-  f.ldb = d;
-  f.Mr = B;
-  f.Nc = N;
-  f.K = d;
-  f.nbx = p.kv.nbx;
-  f.G = G;
-  f.ldg = p.kv.ldg;
-  f.scores = scores;
-  f.pm = rowp;
-  f.ps = rowp + nrow;
-  f.pt = rowp + 2 * nrow;
-  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_OVA>), dim3(p.kv.nbx * p.kv.nby), dim3(256), 0,
-                     st, f);
-  hipLaunchKernelGGL(k_ova_combine, dim3((unsigned)B * (unsigned)p.nsplit), dim3(256), 0, st, G,
-                     p.kv.ldg, N, M, B, (int)p.kv.nby, p.nsplit, p.chunk, f.pm, f.ps, f.pt,
-                     q_anchor, q_rel, q_dir, q_target, smoothing, lse_ws, lse, lpart, occ);
-  KvGemm q = {};   // dq = G E, as skge_kvsall_grad
-  q.A = G;
-  q.lda = p.kv.ldg;
-  q.B = E;
-  q.ldb = d;
-  q.Mr = B;
-  q.Nc = d;
-  q.K = N;
-  q.kslice = p.kv.kslice;
-  q.nbx = p.kv.nbx;
-  q.C = part;
-  const unsigned ntd = (unsigned)((d + KV_T - 1) / KV_T);
-  hipLaunchKernelGGL((k_kv_gemm<false, true, KV_DQ>), dim3(p.kv.nbx * ntd * (unsigned)p.kv.ns),
-                     dim3(256), 0, st, q);
-  KvGemm e = {};   // gE = G^T Q
-  e.A = G;
-  e.lda = p.kv.ldg;
-  e.B = Q;
-  e.ldb = d;
-  e.Mr = N;
-  e.Nc = d;
-  e.K = B;
-  e.nbx = p.kv.nby;
-  e.C = gE;
-  hipLaunchKernelGGL((k_kv_gemm<true, true, KV_DE>), dim3(p.kv.nby * ntd), dim3(256), 0, st, e);
+  const KvPlan& p = b.p;
+  float* lse_ws = (float*)(b.ws + p.o_lse);
+  int* occ = n3 > 0.0f ? (int*)(b.ws + p.o_occ) : nullptr;
+  if (occ) SKGE_CHECK_HIP(hipMemsetAsync(occ, 0, ((size_t)N + M) * sizeof(int), b.st));
+  if ((rc = kv_queries(b))) return rc;
+  KvGemm f = kv_forward(b, scores);
+  const size_t nrow = (size_t)p.nby * B;
+  f.pm = (float*)(b.ws + p.o_rowp);
+  f.ps = f.pm + nrow;
+  f.pt = f.pm + 2 * nrow;
+  hipLaunchKernelGGL((k_kv_gemm<false, false, KV_OVA>), dim3(p.nbx * p.nby), dim3(256), 0, b.st, f);
+  hipLaunchKernelGGL(k_ova_combine, dim3((unsigned)B * (unsigned)p.nsplit), dim3(256), 0, b.st,
+                     b.G, p.ldg, N, M, B, (int)p.nby, p.nsplit, p.chunk, f.pm, f.ps, f.pt, q_anchor,
+                     q_rel, q_dir, q_target, smoothing, lse_ws, lse, b.lpart, occ);
+  kv_backward(b);
   if (occ)
-    hipLaunchKernelGGL(k_ova_n3, dim3((unsigned)(((size_t)N + M + 3) / 4)), dim3(256), 0, st, model,
-                       E, R, N, M, d, occ, n3 / (float)B, gE, gR);
-  hipLaunchKernelGGL(k_ova_chain, dim3(qblocks), dim3(256), 0, st, model, E, R, N, M, d, q_anchor,
-                     q_rel, q_dir, q_target, B, part, p.kv.ns, n3, gE, gR, r_touched, lpart);
-  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, st, lpart, (unsigned)B, 1.0f / (float)B,
+    hipLaunchKernelGGL(k_ova_n3, dim3((unsigned)(((size_t)N + M + 3) / 4)), dim3(256), 0, b.st,
+                       model, E, R, N, M, d, occ, n3 / (float)B, gE, gR);
+  hipLaunchKernelGGL(k_kv_chain<true>, dim3(b.qblocks), dim3(256), 0, b.st, model, E, R, N, M, d,
+                     q_anchor, q_rel, q_dir, q_target, B, b.part, p.ns, n3, gE, gR, r_touched,
+                     b.lpart);
+  hipLaunchKernelGGL(k_kv_loss, dim3(1), dim3(256), 0, b.st, b.lpart, (unsigned)B, 1.0f / (float)B,
                      loss);
   SKGE_CHECK_LAUNCH("onevsall grad");
   return SKGE_OK;
@@ -990,24 +962,11 @@ extern "C" int skge_onevsall_step(void* stream, int model, const skge_table_t* e
                                   const int* q_rel, const int* q_dir, const int* q_target, int B,
                                   float smoothing, float n3, float* loss, void* workspace,
                                   size_t ws_bytes) {
-  int rc = ova_check("skge_onevsall_step", model, ent ? ent->rows : 1, rel ? rel->rows : 1, d, B,
-                     smoothing, n3);
-  if (rc) return rc;
-  if ((rc = check_table(ent, "ent", false)) || (rc = check_table(rel, "rel", false))) return rc;
-  SKGE_CHECK_ARG(ent->width == d && rel->width == d, "skge_onevsall_step: table widths %d / %d, "
-                 "d = %d", ent->width, rel->width, d);
-  const OvaPlan p = ova_plan(B, ent->rows, rel->rows, d);
-  SKGE_CHECK_ARG(workspace && ws_bytes >= p.total, "skge_onevsall_step: workspace needs %zu bytes "
-                 "(B = %d, N = %d, M = %d, d = %d)", p.total, B, ent->rows, rel->rows, d);
-  char* ws = (char*)workspace;
-  float* gE = (float*)(ws + p.o_ge);
-  float* gR = (float*)(ws + p.o_gr);
-  int* touched = (int*)(ws + p.o_touched);
-  rc = skge_onevsall_grad(stream, model, ent->param, rel->param, ent->rows, rel->rows, d, q_anchor,
-                          q_rel, q_dir, q_target, B, smoothing, n3, gE, gR, touched, loss, nullptr,
-                          nullptr, workspace, ws_bytes);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  if ((rc = launch_update_table(st, ent, gE, nullptr))) return rc;   // every row
-  return launch_update_table(st, rel, gR, touched);                   // the rows a query names
+  return kv_step("skge_onevsall_step", KV_ONEVSALL, stream, model, ent, rel, d, B, smoothing, n3,
+                 workspace, ws_bytes, [&](float* gE, float* gR, int* touched) {
+                   return skge_onevsall_grad(stream, model, ent->param, rel->param, ent->rows,
+                                             rel->rows, d, q_anchor, q_rel, q_dir, q_target, B,
+                                             smoothing, n3, gE, gR, touched, loss, nullptr,
+                                             nullptr, workspace, ws_bytes);
+                 });
 }

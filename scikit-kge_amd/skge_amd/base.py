@@ -363,7 +363,8 @@ class Model(object):
                                        L.ptr(pos), L.ptr(negK), P, negs, float(self.gamma),
                                        float(self.alpha), L.ptr(loss)), "sadv_step")
 
-    # ---- KvsAll / 1-N scoring with binary cross-entropy (DistMult, ComplEx) ----
+    # ---- 1-N training of DistMult and ComplEx: KvsAll (binary cross-entropy against a
+    # query's answers) and 1vsAll (softmax cross-entropy against one target, with N3) ----
     def _require_kvsall(self, regime="KvsAll"):
         if self._kernel_model() not in KVSALL_MODELS:
             raise ValueError("%s has no %s training: scoring a query against every entity "
@@ -371,21 +372,51 @@ class Model(object):
                              "with StochasticTrainer or PairwiseStochasticTrainer"
                              % (type(self).__name__, regime, type(self).__name__))
 
-    def _kvsall_args(self, batch):
-        """A KvsAllQueries batch on the model's device, checked, and the
-        workspace of its shape."""
-        self._require_kvsall()
+    def _kvsall_args(self, batch, regime="KvsAll"):
+        """A batch of the regime's queries (KvsAllQueries / OneVsAllQueries) on
+        the model's device, checked, and the workspace of its shape."""
+        self._require_kvsall(regime)
         B = len(batch)
         if B < 1 or B > 4096:
-            raise ValueError("KvsAll batch of %d queries; a batch holds 1 to 4096 (raise the "
-                             "trainer's nbatches)" % B)
+            raise ValueError("%s batch of %d queries; a batch holds 1 to 4096 (raise the "
+                             "trainer's nbatches)" % (regime, B))
         if batch.device != self.device:
             batch = batch.to(self.device)
         N, M = self.params["E"].rows, self.params["R"].rows
-        nbytes = L.lib().skge_kvsall_workspace_bytes(self._kernel_model(), B, N, M, self.d)
+        tag = {"KvsAll": "kvsall", "1vsAll": "onevsall"}[regime]
+        nbytes = getattr(L.lib(), "skge_%s_workspace_bytes" % tag)(self._kernel_model(), B, N, M,
+                                                                    self.d)
         if nbytes == 0:
-            raise L.SkgeError("kvsall: %s" % L.lib().skge_last_error().decode())
+            raise L.SkgeError("%s: %s" % (tag, L.lib().skge_last_error().decode()))
         return batch, B, N, M, self._workspace(nbytes), nbytes
+
+    def _kvsall_outputs(self, B, N, M, scores):
+        """The buffers a 1-N _grad call fills: gE, gR, touched, loss; _score."""
+        dev, d = self.device, self.d
+        self._score = torch.empty((B, N), dtype=torch.float32, device=dev) if scores else None
+        return (torch.empty((N, d), dtype=torch.float32, device=dev),
+                torch.empty((M, d), dtype=torch.float32, device=dev),
+                torch.empty(M, dtype=torch.int32, device=dev),
+                torch.zeros(1, dtype=torch.float32, device=dev))
+
+    def _kvsall_collect(self, gE, gR, touched, loss):
+        """What a 1-N _grad call left, as the trainer's gradients: sets
+        self.loss, gathers the marked R rows and adds rparam * param."""
+        self.loss = float(loss.item())
+        ids = torch.nonzero(touched).reshape(-1)
+        rows = gR[ids]
+        reg = self._reg("logistic")
+        for pid, g, idx in (("E", gE, None), ("R", rows, ids)):
+            rin, rout, _ = reg[pid]
+            if rin + rout != 0.0:   # g += rparam * param, as the _step's update does
+                p = self.params[pid].data
+                g.add_(p if idx is None else p[idx], alpha=float(rin + rout))
+        return {"E": (gE, torch.arange(gE.shape[0], device=gE.device)), "R": (rows, ids)}
+
+    def _kvsall_tables(self, updaters):
+        """The E and R update tables of a 1-N _step call."""
+        reg = self._reg("logistic")
+        return [updaters[pid].table(None, rin=reg[pid][0], rout=reg[pid][1]) for pid in ("E", "R")]
 
     def _kvsall_gradients(self, batch, scores=False):
         """KvsAll gradients of a batch of queries (kvsall.KvsAllQueries):
@@ -395,57 +426,25 @@ class Model(object):
         occurrences -- and sets self.loss = L.  scores=True
         keeps the raw z [B, N] in _score."""
         batch, B, N, M, ws, nbytes = self._kvsall_args(batch)
-        dev, d = self.device, self.d
-        gE = torch.empty((N, d), dtype=torch.float32, device=dev)
-        gR = torch.empty((M, d), dtype=torch.float32, device=dev)
-        touched = torch.empty(M, dtype=torch.int32, device=dev)
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._score = torch.empty((B, N), dtype=torch.float32, device=dev) if scores else None
+        gE, gR, touched, loss = self._kvsall_outputs(B, N, M, scores)
         L.check(L.lib().skge_kvsall_grad(
             L.stream_ptr(), self._kernel_model(), L.ptr(self.params["E"].data),
-            L.ptr(self.params["R"].data), N, M, d, L.ptr(batch.anchor), L.ptr(batch.rel),
+            L.ptr(self.params["R"].data), N, M, self.d, L.ptr(batch.anchor), L.ptr(batch.rel),
             L.ptr(batch.dir), B, L.ptr(batch.off), L.ptr(batch.ans),
             float(getattr(self, "label_smoothing", 0.0)), L.ptr(gE), L.ptr(gR), L.ptr(touched),
             L.ptr(loss), L.ptr(self._score), L.ptr(ws), nbytes), "kvsall_grad")
-        self.loss = float(loss.item())
-        ids = torch.nonzero(touched).reshape(-1)
-        rows = gR[ids]
-        reg = self._reg("logistic")
-        for pid, g, idx in (("E", gE, None), ("R", rows, ids)):
-            rin, rout, _ = reg[pid]
-            if rin + rout != 0.0:   # g += rparam * param, as skge_kvsall_step's update does
-                p = self.params[pid].data
-                g.add_(p if idx is None else p[idx], alpha=float(rin + rout))
-        return {"E": (gE, torch.arange(N, device=dev)), "R": (rows, ids)}
+        return self._kvsall_collect(gE, gR, touched, loss)
 
     def _kvsall_step(self, batch, updaters, loss):
         """scores + loss + gradients + update of a batch of queries in one
         skge_kvsall_step; the batch's L is added into the device word `loss`."""
         batch, B, N, M, ws, nbytes = self._kvsall_args(batch)
-        reg = self._reg("logistic")
-        te, tr = [updaters[pid].table(None, rin=reg[pid][0], rout=reg[pid][1]) for pid in ("E", "R")]
+        te, tr = self._kvsall_tables(updaters)
         L.check(L.lib().skge_kvsall_step(
             L.stream_ptr(), self._kernel_model(), te, tr, self.d, L.ptr(batch.anchor),
             L.ptr(batch.rel), L.ptr(batch.dir), B, L.ptr(batch.off), L.ptr(batch.ans),
             float(getattr(self, "label_smoothing", 0.0)), L.ptr(loss), L.ptr(ws), nbytes),
             "kvsall_step")
-
-    # ---- 1vsAll: softmax cross-entropy against one target, with N3 (DistMult, ComplEx) ----
-    def _onevsall_args(self, batch):
-        """A OneVsAllQueries batch on the model's device, checked, and the
-        workspace of its shape."""
-        self._require_kvsall("1vsAll")
-        B = len(batch)
-        if B < 1 or B > 4096:
-            raise ValueError("1vsAll batch of %d queries; a batch holds 1 to 4096 (raise the "
-                             "trainer's nbatches)" % B)
-        if batch.device != self.device:
-            batch = batch.to(self.device)
-        N, M = self.params["E"].rows, self.params["R"].rows
-        nbytes = L.lib().skge_onevsall_workspace_bytes(self._kernel_model(), B, N, M, self.d)
-        if nbytes == 0:
-            raise L.SkgeError("onevsall: %s" % L.lib().skge_last_error().decode())
-        return batch, B, N, M, self._workspace(nbytes), nbytes
 
     def _onevsall_gradients(self, batch, scores=False):
         """1vsAll gradients of a batch of queries (onevsall.OneVsAllQueries), in
@@ -454,39 +453,24 @@ class Model(object):
         of L = L_ce + L_n3 plus rparam * param -- and sets
         self.loss = L.  The rows' lse [B] stay in _lse; scores=True keeps the
         raw z [B, N] in _score."""
-        batch, B, N, M, ws, nbytes = self._onevsall_args(batch)
-        dev, d = self.device, self.d
-        gE = torch.empty((N, d), dtype=torch.float32, device=dev)
-        gR = torch.empty((M, d), dtype=torch.float32, device=dev)
-        touched = torch.empty(M, dtype=torch.int32, device=dev)
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._score = torch.empty((B, N), dtype=torch.float32, device=dev) if scores else None
-        self._lse = torch.empty(B, dtype=torch.float32, device=dev)
+        batch, B, N, M, ws, nbytes = self._kvsall_args(batch, "1vsAll")
+        gE, gR, touched, loss = self._kvsall_outputs(B, N, M, scores)
+        self._lse = torch.empty(B, dtype=torch.float32, device=self.device)
         L.check(L.lib().skge_onevsall_grad(
             L.stream_ptr(), self._kernel_model(), L.ptr(self.params["E"].data),
-            L.ptr(self.params["R"].data), N, M, d, L.ptr(batch.anchor), L.ptr(batch.rel),
+            L.ptr(self.params["R"].data), N, M, self.d, L.ptr(batch.anchor), L.ptr(batch.rel),
             L.ptr(batch.dir), L.ptr(batch.target), B,
             float(getattr(self, "label_smoothing", 0.0)), float(getattr(self, "n3", 0.0)),
             L.ptr(gE), L.ptr(gR), L.ptr(touched), L.ptr(loss), L.ptr(self._score),
             L.ptr(self._lse), L.ptr(ws), nbytes), "onevsall_grad")
-        self.loss = float(loss.item())
-        ids = torch.nonzero(touched).reshape(-1)
-        rows = gR[ids]
-        reg = self._reg("logistic")
-        for pid, g, idx in (("E", gE, None), ("R", rows, ids)):
-            rin, rout, _ = reg[pid]
-            if rin + rout != 0.0:   # g += rparam * param, as skge_onevsall_step's update does
-                p = self.params[pid].data
-                g.add_(p if idx is None else p[idx], alpha=float(rin + rout))
-        return {"E": (gE, torch.arange(N, device=dev)), "R": (rows, ids)}
+        return self._kvsall_collect(gE, gR, touched, loss)
 
     def _onevsall_step(self, batch, updaters, loss):
         """scores + softmax + loss + gradients + update of a batch of queries in
         one skge_onevsall_step; the batch's L is added into the device word
         `loss`."""
-        batch, B, N, M, ws, nbytes = self._onevsall_args(batch)
-        reg = self._reg("logistic")
-        te, tr = [updaters[pid].table(None, rin=reg[pid][0], rout=reg[pid][1]) for pid in ("E", "R")]
+        batch, B, N, M, ws, nbytes = self._kvsall_args(batch, "1vsAll")
+        te, tr = self._kvsall_tables(updaters)
         L.check(L.lib().skge_onevsall_step(
             L.stream_ptr(), self._kernel_model(), te, tr, self.d, L.ptr(batch.anchor),
             L.ptr(batch.rel), L.ptr(batch.dir), L.ptr(batch.target), B,

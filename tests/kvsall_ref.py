@@ -77,7 +77,7 @@ def chain(model, E, R, anchor, rel, dirn, dq):
     # heads: q.re = rr ar + ri ai, q.im = rr ai - ri ar
     ga_re = np.where(tail, qr * rr + qi * ri, qr * rr - qi * ri)
     ga_im = np.where(tail, -qr * ri + qi * rr, qr * ri + qi * rr)
-    gr_re = np.where(tail, qr * ar + qi * ai, qr * ar + qi * ai)
+    gr_re = qr * ar + qi * ai
     gr_im = np.where(tail, -qr * ai + qi * ar, qr * ai - qi * ar)
     return _join(ga_re, ga_im), _join(gr_re, gr_im)
 
@@ -128,13 +128,13 @@ def normless1_rows(P):
     return P / np.where(ss < 1.0, 1.0, ss)
 
 
-def step(model, params, state, batch, eps, lr, opt, rparam):
-    """One batch from params {"E", "R"} (and AdaGrad state, or None): returns
-    fw, the new params, the new state, and per table (g rows incl. rparam *
-    param, ids, the rows before the projection)."""
-    anchor, rel, dirn, off, ans = batch
+def step_from(grads, params, state, lr, opt, rparam):
+    """One batch from params {"E", "R"} (and AdaGrad state, or None) and the
+    batch's `gradients` (fw, gE, gR, touched): returns fw, the new params, the
+    new state, and per table (g rows incl. rparam * param, ids, the rows before
+    the projection)."""
+    fw, gE, gR, touched = grads
     E, R = params["E"], params["R"]
-    fw, gE, gR, touched = gradients(model, E, R, anchor, rel, dirn, off, ans, eps)
     ids = {"E": np.arange(E.shape[0]), "R": np.flatnonzero(touched)}
     g = {"E": gE + rparam * E, "R": (gR + rparam * R)[ids["R"]]}
     new, nstate, pre = {}, {}, {}
@@ -152,6 +152,12 @@ def step(model, params, state, batch, eps, lr, opt, rparam):
         pre[pid] = P.copy()
         new[pid] = normless1_rows(P) if pid == "E" else P
     return fw, new, nstate, {pid: (g[pid], ids[pid]) for pid in ("E", "R")}, pre
+
+
+def step(model, params, state, batch, eps, lr, opt, rparam):
+    """step_from on KvsAll's gradients of batch = (anchor, rel, dirn, off, ans)."""
+    grads = gradients(model, params["E"], params["R"], *batch, eps)
+    return step_from(grads, params, state, lr, opt, rparam)
 
 
 # ---- cases shared by the CPU and the GPU tests ----

@@ -30,56 +30,16 @@ rparam * param, takes SGD or AdaGrad on every E row and on the R rows some valid
 query names, and projects every E row with normless1."""
 import numpy as np
 
+# the query vectors, their Jacobian, the projection and the step are KvsAll's
+from kvsall_ref import (_join, _parts, chain, normless1_rows, query_vectors,  # noqa: F401
+                        step_from)
+
 MODELS = ("distmult", "complex")
-
-
-def _parts(x):
-    return x[..., 0::2], x[..., 1::2]
-
-
-def _join(re, im):
-    out = np.empty(re.shape[:-1] + (2 * re.shape[-1],), dtype=np.float64)
-    out[..., 0::2] = re
-    out[..., 1::2] = im
-    return out
 
 
 def valid(anchor, rel, dirn, target, N, M):
     a, p, t, g = (np.asarray(x, dtype=np.int64) for x in (anchor, rel, dirn, target))
     return (a >= 0) & (a < N) & (p >= 0) & (p < M) & ((t == 0) | (t == 1)) & (g >= 0) & (g < N)
-
-
-def query_vectors(model, E, R, anchor, rel, dirn):
-    """Q [B][d] of valid queries."""
-    a, r = E[np.asarray(anchor)], R[np.asarray(rel)]
-    if model == "distmult":
-        return a * r
-    tail = (np.asarray(dirn) == 0)[:, None]
-    ar, ai = _parts(a)
-    rr, ri = _parts(r)
-    # tails a r; heads conj(r) a
-    re = np.where(tail, ar * rr - ai * ri, rr * ar + ri * ai)
-    im = np.where(tail, ar * ri + ai * rr, rr * ai - ri * ar)
-    return _join(re, im)
-
-
-def chain(model, E, R, anchor, rel, dirn, dq):
-    """(d L / d E_a, d L / d R_p) rows [B][d] from dq [B][d]: the transposed
-    real Jacobian of query_vectors, component by component."""
-    a, r = E[np.asarray(anchor)], R[np.asarray(rel)]
-    if model == "distmult":
-        return dq * r, dq * a
-    tail = (np.asarray(dirn) == 0)[:, None]
-    ar, ai = _parts(a)
-    rr, ri = _parts(r)
-    qr, qi = _parts(dq)
-    # tails: q.re = ar rr - ai ri, q.im = ar ri + ai rr
-    # heads: q.re = rr ar + ri ai, q.im = rr ai - ri ar
-    ga_re = np.where(tail, qr * rr + qi * ri, qr * rr - qi * ri)
-    ga_im = np.where(tail, -qr * ri + qi * rr, qr * ri + qi * rr)
-    gr_re = qr * ar + qi * ai
-    gr_im = np.where(tail, -qr * ai + qi * ar, qr * ai - qi * ar)
-    return _join(ga_re, ga_im), _join(gr_re, gr_im)
 
 
 def n3_norm(model, X):
@@ -148,35 +108,11 @@ def gradients(model, E, R, anchor, rel, dirn, target, eps, n3=0.0):
     return fw, gE, gR, touched
 
 
-def normless1_rows(P):
-    ss = (P * P).sum(axis=1, keepdims=True)
-    return P / np.where(ss < 1.0, 1.0, ss)
-
-
 def step(model, params, state, batch, eps, n3, lr, opt, rparam):
-    """One batch from params {"E", "R"} (and AdaGrad state, or None): returns
-    fw, the new params, the new state, and per table (g rows incl. rparam *
-    param, ids, the rows before the projection)."""
-    anchor, rel, dirn, target = batch
-    E, R = params["E"], params["R"]
-    fw, gE, gR, touched = gradients(model, E, R, anchor, rel, dirn, target, eps, n3)
-    ids = {"E": np.arange(E.shape[0]), "R": np.flatnonzero(touched)}
-    g = {"E": gE + rparam * E, "R": (gR + rparam * R)[ids["R"]]}
-    new, nstate, pre = {}, {}, {}
-    for pid in ("E", "R"):
-        P = params[pid].copy()
-        i = ids[pid]
-        if opt == "adagrad":
-            p2 = state[pid].copy()
-            p2[i] += g[pid] ** 2
-            P[i] -= lr * g[pid] / np.maximum(np.sqrt(p2[i]), 1e-7)
-            nstate[pid] = p2
-        else:
-            P[i] -= lr * g[pid]
-            nstate[pid] = None
-        pre[pid] = P.copy()
-        new[pid] = normless1_rows(P) if pid == "E" else P
-    return fw, new, nstate, {pid: (g[pid], ids[pid]) for pid in ("E", "R")}, pre
+    """kvsall_ref.step_from on 1vsAll's gradients of batch = (anchor, rel, dirn,
+    target)."""
+    grads = gradients(model, params["E"], params["R"], *batch, eps, n3)
+    return step_from(grads, params, state, lr, opt, rparam)
 
 
 # ---- cases shared by the CPU and the GPU tests ----
