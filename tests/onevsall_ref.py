@@ -32,7 +32,7 @@ import numpy as np
 
 # the query vectors, their Jacobian, the projection and the step are KvsAll's
 from kvsall_ref import (_join, _parts, chain, normless1_rows, query_vectors,  # noqa: F401
-                        step_from)
+                        split_ids, step_from)
 
 MODELS = ("distmult", "complex")
 
@@ -122,7 +122,10 @@ def build_case(model, N, M, B, d, seed, integer=False):
     (odd relation rows are named by no query when M > 1).  When the sizes
     allow, the batch holds a repeated anchor (queries 0 and 1), a query whose
     target is its own anchor (query 0), two identical queries (2 and 3) and
-    targets at entity 0, N - 1, 127 and 128 (queries 4..7).  Float tables are
+    targets at entity 0, N - 1, 127 and 128 (queries 4..7).  Where the plan
+    splits a score row between workgroups, targets also sit at the seams
+    (kvsall_ref.split_ids: chunk, N - 1, chunk - 1, 0 and the last workgroup's
+    element tail, as many as the batch has queries for).  Float tables are
     fp32 values, so the device starts from the same numbers."""
     rng = np.random.RandomState(seed)
     if integer:
@@ -145,4 +148,14 @@ def build_case(model, N, M, B, d, seed, integer=False):
     for b, g in zip(range(4, 8), (0, N - 1, 127, 128)):
         if b < B and 0 <= g < N:
             target[b] = g
+    # the seams of the column split, on the queries no record above holds;
+    # when those run out, query 0 takes one as its anchor and target
+    seams = split_ids(N, M, B, d)
+    free = [b for b in range(B) if b >= 8 or b == 1 or (b == 2 and B == 3)]
+    for b, g in zip(free, seams):
+        target[b] = g
+    if len(free) < len(seams):
+        target[0] = anchor[0] = seams[len(free)]
+        if B > 1:
+            anchor[1] = anchor[0]
     return E, R, (anchor, rel, dirn, target)

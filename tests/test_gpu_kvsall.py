@@ -256,4 +256,17 @@ def test_refusals():
                                   L.ptr(f), L.ptr(z), L.ptr(f), None, L.ptr(f), 640)
         assert rc == want, (code, rc)
         assert str(code).encode() in lib.skge_last_error()
+
+    # the size limits, ComplEx's even d and a workspace one byte short
+    def grad(code=5, d=8, B=2, ws=640):
+        return lib.skge_kvsall_grad(L.stream_ptr(), code, L.ptr(E), L.ptr(R), 20, 3, d, L.ptr(z),
+                                    L.ptr(z), L.ptr(z), B, L.ptr(z), L.ptr(z), 0.0, L.ptr(f),
+                                    L.ptr(f), L.ptr(z), L.ptr(f), None, L.ptr(f), ws)
+
+    assert grad(B=4097) == -3 and b"4097" in lib.skge_last_error()
+    assert grad(d=1025) == -3 and b"1025" in lib.skge_last_error()
+    assert grad(code=6, d=3) == -1 and b"even" in lib.skge_last_error()
+    need = KR.plan("kvsall", 2, 20, 3, 8).total
+    assert lib.skge_kvsall_workspace_bytes(5, 2, 20, 3, 8) == need
+    assert grad(ws=need - 1) == -1 and str(need).encode() in lib.skge_last_error()
     torch.cuda.synchronize()

@@ -315,10 +315,10 @@ def test_refusals():
     z = torch.zeros(64, dtype=torch.int32, device=DEV)
     f = torch.zeros(20 * 8, dtype=torch.float32, device=DEV)
 
-    def grad(code, n3=0.0):
-        return lib.skge_onevsall_grad(L.stream_ptr(), code, L.ptr(E), L.ptr(R), 20, 3, 8, L.ptr(z),
-                                      L.ptr(z), L.ptr(z), L.ptr(z), 2, 0.0, n3, L.ptr(f), L.ptr(f),
-                                      L.ptr(z), L.ptr(f), None, None, L.ptr(f), 640)
+    def grad(code, n3=0.0, d=8, B=2, ws=640):
+        return lib.skge_onevsall_grad(L.stream_ptr(), code, L.ptr(E), L.ptr(R), 20, 3, d, L.ptr(z),
+                                      L.ptr(z), L.ptr(z), L.ptr(z), B, 0.0, n3, L.ptr(f), L.ptr(f),
+                                      L.ptr(z), L.ptr(f), None, None, L.ptr(f), ws)
 
     for code, want in ((0, -3), (1, -3), (2, -3), (3, -3), (7, -3), (4, -1)):
         rc = grad(code)
@@ -326,4 +326,11 @@ def test_refusals():
         assert str(code).encode() in lib.skge_last_error()
     assert grad(5, n3=-0.1) == -1 and b"N3" in lib.skge_last_error()
     assert grad(5, n3=float("nan")) == -1 and b"N3" in lib.skge_last_error()
+    # the size limits, ComplEx's even d and a workspace one byte short
+    assert grad(5, B=4097) == -3 and b"4097" in lib.skge_last_error()
+    assert grad(5, d=1025) == -3 and b"1025" in lib.skge_last_error()
+    assert grad(6, d=3) == -1 and b"even" in lib.skge_last_error()
+    need = KR.plan("onevsall", 2, 20, 3, 8).total
+    assert lib.skge_onevsall_workspace_bytes(5, 2, 20, 3, 8) == need
+    assert grad(5, ws=need - 1) == -1 and str(need).encode() in lib.skge_last_error()
     torch.cuda.synchronize()

@@ -72,6 +72,113 @@ def test_label_smoothing_and_loss_definition():
     assert np.isclose(fw["y"][0, 2], 0.9 + 0.1 / 6) and np.isclose(fw["y"][0, 0], 0.1 / 6)
 
 
+def test_invalid_queries_score_as_zero():
+    """An anchor of N, a relation of M and a direction of 2: the gradients are
+    those of the batch without the three queries, with B unchanged, and each of
+    the three adds N log 2 / B to the loss.  Answer ids of -1 and N are no
+    answers."""
+    N, M, B, d = 40, 7, 9, 6
+    E, R, (a, p, t, off, ans) = KR.build_case("complex", N, M, B, d, seed=3)
+    a2, p2, t2 = a.copy(), p.copy(), t.copy()
+    a2[1], p2[4], t2[6] = N, M, 2
+    bad = [1, 4, 6]
+    keep = np.setdiff1d(np.arange(B), bad)
+    # -1 and N inside query 0's list
+    ans2 = np.concatenate([ans[:1], [-1, N], ans[1:]]).astype(np.int32)
+    off2 = off.copy()
+    off2[1:] += 2
+    assert off[1] - off[0] >= 1 and not KR.valid(a2, p2, t2, N, M)[bad].any()
+    fw, gE, gR, touched = KR.gradients("complex", E, R, a2, p2, t2, off2, ans2, 0.1)
+    lists = [ans[off[b]:off[b + 1]] for b in keep]
+    offk = np.cumsum([0] + [len(x) for x in lists])
+    fk, gEk, gRk, tk = KR.gradients("complex", E, R, a[keep], p[keep], t[keep], offk,
+                                    np.concatenate(lists), 0.1)
+    scale = len(keep) / float(B)
+    assert np.allclose(gE, gEk * scale, rtol=1e-12, atol=1e-15)
+    assert np.allclose(gR, gRk * scale, rtol=1e-12, atol=1e-15) and np.array_equal(touched, tk)
+    assert np.isclose(fw["loss"], fk["loss"] * scale + 3 * N * np.log(2.0) / B, rtol=1e-12)
+    assert np.all(fw["z"][bad] == 0) and np.all(fw["Q"][bad] == 0)
+    assert np.array_equal(fw["y"][0], KR.forward("complex", E, R, a, p, t, off, ans, 0.1)["y"][0])
+
+
+def test_plan_equals_the_library_workspace():
+    """plan() restates kv_plan: the same bytes at every shape of the suites,
+    the benchmark's and both sides of the plan's thresholds."""
+    from skge_amd import _lib as L
+    lib = L.load()
+    grid = KR.plan_grid()
+    assert len(set(grid)) > 150
+    for B, N, M, d in grid:
+        for code in (5, 6) if d % 2 == 0 else (5,):
+            want = lib.skge_kvsall_workspace_bytes(code, B, N, M, d)
+            assert want > 0 and KR.plan("kvsall", B, N, M, d).total == want, (B, N, M, d)
+    # the thresholds are inside the grid: both values of each choice occur
+    plans = [KR.plan("onevsall", *g) for g in grid]
+    assert {p.ns == 1 for p, g in zip(plans, grid) if g[1] > KR.KC} == {False, True}
+    assert {p.nsplit for p in plans} >= {1, 2, 3}
+    assert {p.kslice for p in plans} >= {32, 64, 96}
+
+
+def test_bench_shape_plans_to_the_regimes():
+    N, B, d = KR.BENCH_SHAPE
+    p = KR.plan("onevsall", B, N, KR.BENCH_M, d)
+    # (the 16 MB cap, 40 slices, binds before the 512 workgroups' 64)
+    assert (p.kslice, p.ns, p.nsplit, p.chunk, p.nby) == (1024, 40, 2, 20472, 320)
+    assert all(KR.PREDICATES[k](p, N, B, d) for k in
+               ("kslice > 32", "nsplit > 1", "chunk > 1024", "nby > 256", "nbx nby > 256"))
+
+
+@pytest.mark.parametrize("shape", KR.REGIME_SHAPES, ids=KR.regime_id)
+def test_regime_shape_meets_its_predicates(shape):
+    N, B, d, models, (values, preds) = shape
+    assert d % 2 == 0 or models == ("distmult",)
+    p = KR.plan("onevsall", B, N, KR.EDGE_M, d)
+    kv = KR.plan("kvsall", B, N, KR.EDGE_M, d)
+    assert kv[:7] == p[:7] and (kv.nsplit, kv.chunk) == (0, 0)
+    got = dict(p._asdict(), last=KR.last_slice(p, N))
+    assert {k: got[k] for k in values} == values
+    for k in preds:
+        assert KR.PREDICATES[k](p, N, B, d), k
+    assert B <= 4096 and d <= 1024 and 3 * N < 2 ** 24
+
+
+def test_regime_shapes_cover_what_edge_shapes_do_not():
+    def met(shapes):
+        out = set()
+        for s in shapes:
+            N, B, d = s[:3]
+            p = KR.plan("onevsall", B, N, KR.EDGE_M, d)
+            out |= {k for k, f in KR.PREDICATES.items() if f(p, N, B, d)}
+        return out
+
+    assert met(KR.REGIME_SHAPES) == set(KR.PREDICATES)
+    assert KR.GAP == ["kslice > 32", "ns == 1 < chunks", "nsplit > 1", "chunk > 1024",
+                      "nby > 256", "nbx nby > 256"]
+    assert not met(KR.EDGE_SHAPES) & set(KR.GAP)
+    # every claimed predicate is claimed by name somewhere, not met by accident
+    claimed = {k for s in KR.REGIME_SHAPES for k in s[4][1]}
+    assert claimed == set(KR.PREDICATES)
+    # the exact test's extra shapes keep the slices of the shapes they stand for:
+    # several chunks each, the last one ragged past one chunk
+    for (N, B, d, _), want in zip(KR.EXACT_EXTRA_SHAPES, ((96, 342, 65), (64, 130, 44))):
+        assert B & (B - 1) == 0
+        p = KR.plan("kvsall", B, N, KR.EDGE_M, d)
+        assert (p.kslice, p.ns, KR.last_slice(p, N)) == want
+        assert KR.PREDICATES["last slice past one chunk"](p, N, B, d)
+
+
+def test_build_case_puts_answers_at_the_split_seams():
+    for N, B, d in ((1025, 3, 2), (2501, 600, 2), (32801, 2, 2)):
+        ids = KR.split_ids(N, KR.EDGE_M, B, d)
+        chunk = KR.plan("onevsall", B, N, KR.EDGE_M, d).chunk
+        assert ids[:4] == [chunk, N - 1, chunk - 1, 0] and (N & ~3) in ids
+        _, _, (a, p, t, off, ans) = KR.build_case("distmult", N, KR.EDGE_M, B, d, seed=1)
+        assert set(ids) <= set(ans[off[1]:off[2]].tolist())
+        assert a[0] == a[1] and a[0] in ans[off[0]:off[1]]
+    assert KR.split_ids(8300, KR.EDGE_M, 130, 130) == [1040, 8299, 1039, 0]
+    assert all(KR.split_ids(N, KR.EDGE_M, B, d) == [] for N, B, d in KR.EDGE_SHAPES)
+
+
 # (s, o, p): duplicated triples, a self-loop (3, 3, 0), entity 4 only ever an object
 KG = [(0, 1, 0), (0, 2, 0), (0, 1, 0), (3, 3, 0), (1, 4, 1), (2, 4, 1), (2, 4, 1), (0, 4, 0)]
 SZ = (5, 5, 2)

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import kvsall_ref as KR
 import onevsall_ref as OR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,6 +104,43 @@ def test_build_case_holds_its_special_records():
     assert set(t.tolist()) == {0, 1} and np.all(p % 2 == 0)
     _, _, (_, _, _, g) = OR.build_case("distmult", 128, 7, 33, 8, seed=1)
     assert g[4:7].tolist() == [0, 127, 127]
+
+
+def test_build_case_puts_targets_at_the_split_seams():
+    """Where k_ova_combine splits a row: the first column of workgroup 1, the
+    last of the last workgroup (in its element tail when N is no multiple of
+    4), the last of workgroup 0 and column 0, as far as the queries reach; the
+    records of the unsplit shapes stay."""
+    for N, B, d in ((2501, 600, 2), (8300, 130, 130)):
+        chunk = KR.plan("onevsall", B, N, 7, d).chunk
+        _, _, (a, p, t, g) = OR.build_case("distmult", N, 7, B, d, seed=1)
+        assert {chunk, N - 1, chunk - 1, 0} <= set(g.tolist())
+        assert N % 4 == 0 or (N & ~3) in g.tolist()
+        assert a[0] == a[1] and g[0] == a[0]
+        assert (a[2], p[2], t[2], g[2]) == (a[3], p[3], t[3], g[3])
+        assert g[4:8].tolist() == [0, N - 1, 127, 128]
+    _, _, (a, p, t, g) = OR.build_case("distmult", 1025, 7, 3, 2, seed=1)
+    assert g.tolist() == [515, 516, 1024] and a[0] == a[1] == 515
+    _, _, (a, p, t, g) = OR.build_case("distmult", 32801, 7, 2, 2, seed=1)
+    assert g.tolist() == [32800, 996] and a[0] == a[1] == 32800
+    # the owner of every seam target: each workgroup of a split is some query's
+    for N, B, d, want in ((1025, 3, 2, {0, 1}), (2501, 600, 2, {0, 1}),
+                          (8300, 130, 130, set(range(8)))):
+        chunk = KR.plan("onevsall", B, N, 7, d).chunk
+        _, _, (_, _, _, g) = OR.build_case("complex", N, 7, B, d, seed=2)
+        assert {int(x) // chunk for x in g} == want
+
+
+def test_plan_equals_the_library_workspace():
+    """kvsall_ref.plan restates kv_plan for this regime too: the same bytes at
+    every shape of the suites, the benchmark's and both sides of the plan's
+    thresholds."""
+    from skge_amd import _lib as L
+    lib = L.load()
+    for B, N, nrel, d in KR.plan_grid():
+        for code in (5, 6) if d % 2 == 0 else (5,):
+            want = lib.skge_onevsall_workspace_bytes(code, B, N, nrel, d)
+            assert want > 0 and KR.plan("onevsall", B, N, nrel, d).total == want, (B, N, nrel, d)
 
 
 # (s, o, p): a duplicated triple, a self-loop (3, 3, 0), entity 4 only ever an object
