@@ -467,6 +467,11 @@ skge_runner_t *skge_runner_create_smp(void *stream, int l1, const skge_table_t *
                                       const skge_sampler_t *smp);
 int skge_pair_runner_run(skge_pair_runner_t *r, void *stream, int nepochs);
 int skge_pair_runner_nlaunches(const skge_pair_runner_t *r);
+/* How the captured batches update the entity rows: 0 = sums accumulated by
+ * the gradient launch, then an apply launch; 1 = RESCAL's row-grouped apply
+ * (one wave per distinct row of the batch sums and applies; no apply launch).
+ * Fixed at capture; -1 for a NULL runner. */
+int skge_pair_runner_entity_apply(const skge_pair_runner_t *r);
 void skge_pair_runner_destroy(skge_pair_runner_t *r);
 
 /*

@@ -140,6 +140,7 @@ struct skge_pair_runner : GraphRunnerCore {
   int* nviol = nullptr;   // [nbatches]: each batch's gate word (its violations)
   void* ws = nullptr;
   size_t ws_bytes = 0;
+  int entity_apply = 0;   // 1: the batches' entity rows go through RESCAL's row-grouped apply
 };
 
 extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
@@ -242,6 +243,7 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
                                            r->rec, r->rec_n1, start, count, margin, r->ws,
                                            r->ws_bytes, gate);
       if (!rc && wst.applied) {   // the row-grouped apply updated the entity rows and W
+        r->entity_apply = 1;
         if (wst.cur) wsync = wst;
       } else if (!rc) {   // the entity table's apply (and W's, unless the dW kernel updated it)
         skge_table_t te = *ent;
@@ -467,6 +469,10 @@ extern "C" int skge_pair_runner_run(skge_pair_runner_t* r, void* stream, int nep
 
 extern "C" int skge_pair_runner_nlaunches(const skge_pair_runner_t* r) {
   return r ? r->nnodes : -1;
+}
+
+extern "C" int skge_pair_runner_entity_apply(const skge_pair_runner_t* r) {
+  return r ? r->entity_apply : -1;
 }
 
 extern "C" void skge_pair_runner_destroy(skge_pair_runner_t* r) { delete r; }

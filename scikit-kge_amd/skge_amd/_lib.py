@@ -161,6 +161,7 @@ SIGNATURES = {
     "skge_onevsall_step": (c_i, [c_p, c_i, T_P, T_P, c_i, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p,
                                  c_p, c_sz]),
     "skge_pair_runner_nlaunches": (c_i, [c_p]),
+    "skge_pair_runner_entity_apply": (c_i, [c_p]),
     "skge_pair_runner_destroy": (None, [c_p]),
     "skge_triple_runner_create": (c_p, [c_p, c_i, T_P, T_P, c_i, c_p, c_i64, c_p, c_i64, c_i, c_u64,
                                         c_p, c_i, c_p]),

@@ -709,10 +709,14 @@ class PairLoopRunner(_Runner):
                          self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
                          L.ptr(self.nviol_total), self._smp, self._neg,
                          create="skge_pair_runner_create_multi")
-            return
-        self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te, self.tr,
-                     model.d, *self._epoch_args(), float(model.margin), self.ntries,
-                     L.ptr(self.nviol_total), self._smp, create="skge_pair_runner_create_ex")
+        else:
+            self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te,
+                         self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
+                         L.ptr(self.nviol_total), self._smp, create="skge_pair_runner_create_ex")
+        # how the captured batches update the entity rows: "scatter" (sums by
+        # the gradient launch, then an apply launch) or "rows" (RESCAL's
+        # row-grouped apply, k_rescal_fold)
+        self.entity_apply = ("scatter", "rows")[L.lib().skge_pair_runner_entity_apply(self.handle)]
 
 
 def _require_logistic_model(model):

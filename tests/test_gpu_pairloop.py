@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import rescal_rows_ref as RR
+
 pytestmark = pytest.mark.gpu
 
 ATOL = RTOL = 1e-5
@@ -645,6 +647,16 @@ def test_rescal_in_front_w_step_matches_apply_side(n_ent, n_rel, T, d, nb, opt, 
         np.testing.assert_allclose(out[1][1][k], out[0][1][k], rtol=RTOL, atol=ATOL, err_msg=k)
 
 
+# the entity-apply form the default leg of the cases below captures.  One case
+# is not the row-grouped apply: 666 positives over 5 relations are 399 items
+# per relation, 4 dW groups, so the dW is split 4 ways (rs_front_splits,
+# skge_rescal.hip:242-254), the W step is not in the front and both legs run
+# the scatter (skge_rescal.hip:2416-2418, 2451).  d = 30 under the row-grouped
+# apply is held to the oracle in test_gpu_rescal_rows.py.
+ROWS_FORM = {(2000, 16, 7): "rows", (2000, 24, 50): "rows", (2000, 30, 3): "scatter",
+             (3000, 20, 8): "rows", (14140, 200, 10): "rows", (14140, 200, 9): "rows"}
+
+
 @pytest.mark.parametrize("n_ent,n_rel,T,d,nb,opt", [
     (300, 7, 2000, 16, 7, "sgd"),            # ragged remainder batch
     (300, 40, 2000, 24, 50, "adagrad"),      # ~40 positives / batch: most relations absent
@@ -675,6 +687,10 @@ def test_rescal_row_grouped_apply_matches_scatter(n_ent, n_rel, T, d, nb, opt, m
         cls = S.SGD if opt == "sgd" else S.AdaGrad
         upd = {pid: cls(p, 0.1) for pid, p in m.params.items()}
         r = PairLoopRunner(m, upd, DeviceKG(xs, m.device), nb, seed=15)
+        # the legs differ only where the code's conditions give the default leg
+        # the row-grouped apply (tests/rescal_rows_ref.entity_apply_form)
+        assert ROWS_FORM[(T, d, nb)] == RR.entity_apply_form(T, nb, n_rel)
+        assert r.entity_apply == ("scatter" if form else ROWS_FORM[(T, d, nb)])
         with torch.cuda.stream(r.stream):
             r.run(2)
         r.synchronize()
@@ -720,6 +736,7 @@ def _two_runs(S, DeviceKG, PairLoopRunner, xs, n_ent, n_rel, d, nb):
         m.add_hyperparam("margin", 0.2)
         upd = {pid: S.AdaGrad(p, 0.1) for pid, p in m.params.items()}
         r = PairLoopRunner(m, upd, DeviceKG(xs, m.device), nb, seed=17)
+        assert r.entity_apply == "rows"
         with torch.cuda.stream(r.stream):
             r.run(2)
         r.synchronize()

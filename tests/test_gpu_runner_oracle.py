@@ -31,7 +31,10 @@ import pytest
 import torch
 
 import parity_util
+import rescal_rows_ref as RR
 from oracle import skge_oracle as O
+from runner_oracle_util import epoch_vs_oracle, pairs as _pairs
+from runner_oracle_util import snapshot as _snapshot  # noqa: F401  (tools/diag_adagrad.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,65 +52,11 @@ def _kg(T, seed=21):
     return np.array(out, dtype=np.int32)
 
 
-def _pairs(rec, n1, start, count):
-    pos, neg = [], []
-    for j in range(start, start + count):
-        s, o, p, a = (int(x) for x in rec[j])
-        b = int(n1[j])
-        if a >= 0:
-            pos.append((s, o, p))
-            neg.append((a, o, p))
-        if b >= 0:
-            pos.append((s, o, p))
-            neg.append((s, b, p))
-    return np.array(pos, dtype=np.int64), np.array(neg, dtype=np.int64)
-
-
-def _snapshot(m, upd):
-    params = {pid: p.data.detach().cpu().numpy().astype(np.float64) for pid, p in m.params.items()}
-    state = {pid: upd[pid].p2.detach().cpu().numpy().astype(np.float64)
-             for pid in m.params if getattr(upd[pid], "p2", None) is not None}
-    return params, state
-
-
 def _epoch_vs_oracle(kind, m, upd, runner, kg, seed, epoch, nb, opt, what, **kw):
-    """Run epoch `epoch` (0-based; the runner's key is at it) on the device and
-    replay its batches through the oracle from the device state before it."""
-    from skge_amd.device import batch_sizes, epoch_records
-    params, state = _snapshot(m, upd)
-    if opt == "sgd":
-        state = {k: np.zeros_like(v) for k, v in params.items()}
-    v0 = int(runner.nviol_total.item())
-    rec, n1 = epoch_records(kg, N, seed, epoch)
-    rec, n1 = rec.cpu().numpy(), n1.cpu().numpy()
-    runner.run(1)
-    runner.synchronize()
-    got_v = int(runner.nviol_total.item()) - v0
-    want_v, start = 0, 0
-    sizes = batch_sizes(kg.T, nb)
-    assert sizes == [B] * nb
-    for c in sizes:
-        pos, neg = _pairs(rec, n1, start, c)
-        start += c
-        assert len(pos) == 2 * c          # WN18-sparse: every negative found
-        before = {k: v.copy() for k, v in params.items()}
-        _, _, nv, grads = O.pairwise_step(kind, params, state, pos, neg, 0.1, float(m.margin),
-                                          opt, **kw)
-        want_v += nv
-    assert got_v == want_v, (what, got_v, want_v)
-    for pid in m.params:
-        if nb == 1:     # one step from the snapshot: the step-aware bound (parity_util.check_step)
-            parity_util.check_step(m.params[pid].data, params[pid], before[pid],
-                                   grads[pid] if grads else None, state[pid], 0.1,
-                                   "%s %s" % (what, pid), post=parity_util.POSTS[kind].get(pid),
-                                   opt=opt)
-        else:
-            parity_util.check(m.params[pid].data, params[pid], "%s %s" % (what, pid),
-                              lr=0.1 if opt == "adagrad" else None,
-                              p2=state[pid] if opt == "adagrad" else None)
-        if opt == "adagrad":
-            parity_util.check(upd[pid].p2, state[pid], "%s p2 %s" % (what, pid))
-    return got_v
+    """runner_oracle_util.epoch_vs_oracle at WN18 geometry: nb batches of B,
+    every negative found (WN18-sparse)."""
+    return epoch_vs_oracle(kind, m, upd, runner, kg, seed, epoch, nb, opt, what, n_ent=N,
+                           sizes=[B] * nb, all_found=True, **kw)
 
 
 def _setup(cls, T, opt, d=D, lr=0.1, no_post=False, **kw):
@@ -195,18 +144,20 @@ def test_config1_padded_runner_three_batches_vs_oracle():
                                 "config1 padded runner sgd 3 batches", l1=True) > 0
 
 
-@pytest.mark.parametrize("kind", ["transe", "hole"])
+@pytest.mark.parametrize("kind", ["transe", "hole", "rescal"])
 def test_runner_skewed_kg_hot_rows_vs_oracle(kind):
     """SURVEY 8(d)'s skew variant (bench.make_zipf_kg: entity ids Zipf(1.1),
     WN18's entity and relation counts) on the shipped runners with their
     hub rows in replicated sums whose updated values every reader computes
-    itself (TransE: k_pipe_batch's hot rows; HolE: k_hole_pipe's pair form):
-    one epoch of 3 batches of B = 1414, SGD, after a first epoch, replayed
-    DIRECTLY by the oracle -- not only against another HIP runner
-    (test_gpu_skew.py)."""
+    itself (TransE: k_pipe_batch's hot rows; HolE: k_hole_pipe's pair form)
+    or, for RESCAL, in the row-grouped apply's hub path (k_rescal_fold: rows
+    of more than 8 work items summed through the entity accumulator and
+    applied by the last arriver): one epoch of 3 batches of B = 1414, SGD,
+    after a first epoch, replayed DIRECTLY by the oracle -- not only against
+    another HIP runner (test_gpu_skew.py)."""
     import skge_amd as S
     from bench import make_zipf_kg
-    from skge_amd.device import DeviceKG
+    from skge_amd.device import DeviceKG, epoch_records
     name, ckw, margin, okw = CASES[kind]
     np.random.seed(42)
     m = getattr(S, name)((N, N, M), D, **ckw)
@@ -214,7 +165,17 @@ def test_runner_skewed_kg_hot_rows_vs_oracle(kind):
     upd = {pid: S.SGD(p, 0.1) for pid, p in m.params.items()}
     kg = DeviceKG(make_zipf_kg(N, M, 3 * B, seed=7), m.device)
     r = _runner(kind, m, upd, kg, 3, 45)
-    assert r.hot_rows > 0, "the skewed KG must give the runner hub rows"
+    if kind == "rescal":
+        # the pair loop has no hot-row count: the captured form, and hub rows
+        # (tests/rescal_rows_ref.py) in every batch of both epochs
+        assert r.entity_apply == "rows"
+        for epoch in (0, 1):
+            rec, n1 = (x.cpu().numpy() for x in epoch_records(kg, N, 45, epoch))
+            for b in range(3):
+                hubs = RR.regime_counts(RR.group_rows(rec, n1, b * B, B))["hub"]
+                assert hubs > 0, "the skewed KG must give every batch hub rows"
+    else:
+        assert r.hot_rows > 0, "the skewed KG must give the runner hub rows"
     with torch.cuda.stream(r.stream):
         r.run(1)
         r.synchronize()
