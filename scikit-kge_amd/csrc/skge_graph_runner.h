@@ -3,7 +3,8 @@
 // geometry, the argument refusals, and GraphRunnerCore -- the captured graph
 // and the device buffers it names.  A runner supplies its own checks beyond
 // check_runner_args, its buffers (alloc) and the launches between
-// begin_capture and end_capture.
+// begin_capture and end_capture; the pair and triple loops' creates share
+// more than that, and are written on skge_loop_runner.h.
 #pragma once
 #include <cstdint>
 #include <memory>

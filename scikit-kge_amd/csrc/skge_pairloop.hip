@@ -24,12 +24,7 @@
 // DistMult and ComplEx (d <= 256) do the same with k_diag_pos: 5 row reads per
 // positive instead of 12, one accumulator add per distinct row; RotatE with
 // k_rot_pos.
-#include <cstdlib>
-#include <vector>
-
-#include "skge_graph_runner.h"
-#include "skge_hole_fft.h"
-#include "skge_sampler.h"
+#include "skge_loop_runner.h"
 
 namespace skge {
 
@@ -133,140 +128,117 @@ using namespace skge;
 
 constexpr int TRANSE_POS_MIN_K = 10;   // k_transe_pos_multi is the default from here on
 
-struct skge_pair_runner : GraphRunnerCore {
-  int4* rec = nullptr;
-  int* rec_n1 = nullptr;
+struct skge_pair_runner : LoopRunner {
   int* pairs = nullptr;   // the epoch's pairs: pos [2T][3], then neg [2T][3]
   int* nviol = nullptr;   // [nbatches]: each batch's gate word (its violations)
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
   int entity_apply = 0;   // 1: the batches' entity rows go through RESCAL's row-grouped apply
 };
+
+// the pair creates' finish
+static int launch_pairs_epoch_end(hipStream_t st, const int* gates, int nb, int* nviol_total,
+                                  uint64_t* epoch_key) {
+  hipLaunchKernelGGL(k_pairs_epoch_end, dim3(1), dim3(256), 0, st, gates, nb, nviol_total,
+                     epoch_key);
+  SKGE_CHECK_LAUNCH("epoch end launch");
+  return SKGE_OK;
+}
 
 extern "C" skge_pair_runner_t* skge_pair_runner_create_ex(
     void* stream, int model, int af, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
     uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total,
     const skge_sampler_t* smp) {
-  if (!ent || !rel) return fail("pair runner: NULL table");
-  if (check_sampler(smp, "pair runner")) return nullptr;
-  if (!model_known(model)) return fail("pair runner: unknown model");
-  if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
-  if (model == SKGE_ROTATE && d % 2) return fail("pair runner: RotatE needs an even d");
-  if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity,
-                         2 * T, ntries, stream))
+  const char* who = "pair runner";
+  if (!check_loop_model(who, ent, rel, smp, model, d) ||
+      !check_runner_args(who, trip, set, epoch_key, T, INT32_MAX, nbatches, set_capacity, 2 * T,
+                         ntries, stream))
     return nullptr;
   hipStream_t st = as_stream(stream);
   const EpochBatches batches = epoch_batches(T, nbatches);
-  const int64_t bs = batches.bs;
-  const int Pmax = (int)(2 * batches.maxb);
-  if ((long long)4 * Pmax > ent->touched_cap && ent->acc_touched)
-    return fail("pair runner: entity accumulator needs 8 * batch_size touched slots");
+  const int bs = (int)batches.bs, nb = batches.size(), Pmax = (int)(2 * batches.maxb);
+  // (the relation side is skge_pair_step's own refusal, at the capture)
+  if (!check_touched(who, ent, (long long)4 * Pmax, "entity")) return nullptr;
   // HolE with the register-tiled correlations: both pairs of a positive in
   // one wave straight from the records, 4 entity slots and 1 relation slot per
   // positive (SKGE_HOLE_PAIRS=1 keeps the explicit pairs)
-  const char* hp = getenv("SKGE_HOLE_PAIRS");
-  const bool hpos = model == SKGE_HOLE && !(hp && atoi(hp)) && hole_pos_ok(af, ent, rel, d);
+  const bool hpos = model == SKGE_HOLE && !env_flag("SKGE_HOLE_PAIRS", 0) &&
+                    hole_pos_ok(af, ent, rel, d);
   // RESCAL on the matrix cores: each positive once in the GEMMs and dW, both
   // of its pairs per scatter wave (k_rescal_pos_scatter; SKGE_RESCAL_PAIRS=1
   // keeps the explicit pairs)
-  const char* rp = getenv("SKGE_RESCAL_PAIRS");
-  const bool rpos = model == SKGE_RESCAL && !(rp && atoi(rp)) &&
+  const bool rpos = model == SKGE_RESCAL && !env_flag("SKGE_RESCAL_PAIRS", 0) &&
                     rescal_pair_mfma_selected(d, rel->rows);
   // DistMult / ComplEx: both pairs of a positive in one wave straight from the
   // records (k_diag_pos, skge_grad.hip; SKGE_DIAG_PAIRS=1 keeps the explicit
   // pairs)
-  const char* dg = getenv("SKGE_DIAG_PAIRS");
-  const bool dpos = !(dg && atoi(dg)) && diag_pos_ok(model, af, ent, rel, d);
+  const bool dpos = !env_flag("SKGE_DIAG_PAIRS", 0) && diag_pos_ok(model, af, ent, rel, d);
   // RotatE: the same with k_rot_pos (SKGE_ROT_PAIRS=1 keeps the explicit pairs)
-  const char* rg = getenv("SKGE_ROT_PAIRS");
-  const bool tpos = !(rg && atoi(rg)) && rot_pos_ok(model, ent, rel, d);
-  const int nb = batches.size();
+  const bool tpos = !env_flag("SKGE_ROT_PAIRS", 0) && rot_pos_ok(model, ent, rel, d);
   // RESCAL: every batch's relation buckets built once per epoch, up front (the
   // items do not depend on the parameters); SKGE_RESCAL_EPOCH_BUCKETS=0 keeps
   // the per-batch bucketing
-  const char* eb = getenv("SKGE_RESCAL_EPOCH_BUCKETS");
-  const bool rep = rpos && rescal_epoch_ok(rel->rows) && !(eb && atoi(eb) == 0);
+  const bool rep = rpos && rescal_epoch_ok(rel->rows) && env_flag("SKGE_RESCAL_EPOCH_BUCKETS", 1);
   std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
-  r->ws_bytes = rep ? rescal_epoch_ws_bytes((int)bs, nb, rel->rows, d)
-                    : skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
-  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
-  r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
+  r->alloc_draw(T, 0);
   if (!hpos && !dpos && !tpos) r->pairs = (int*)r->alloc((size_t)T * 12 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
-  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
-  // an absent negative by a zero coefficient, which only discards FINITE stale values
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
-  if (!r->alloc_ok) return fail("pair runner: device allocation failed");
+  r->alloc_ws(rep ? rescal_epoch_ws_bytes(bs, nb, rel->rows, d)
+                  : skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d));
   int* pos = r->pairs;
   int* neg = r->pairs ? r->pairs + (size_t)T * 6 : nullptr;
-  const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
-    return fail("pair runner: HolE FFT twiddle table allocation failed");
-  if (!r->begin_capture(st)) return nullptr;
-  int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
-                               r->rec, r->rec_n1, smp);
-  if (!rc) {
-    const int64_t blocks = std::max((int64_t)1, std::min((T + 255) / 256, (int64_t)4096));
-    hipLaunchKernelGGL(k_pairs_of_epoch, dim3((unsigned)blocks), dim3(256), 0, st, r->rec,
-                       r->rec_n1, (long long)T, pos, neg, r->nviol, nb, rpos ? 1 : 0);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("pairs launch failed");
-      rc = SKGE_EHIP;
-    }
-    if (!rc && rep) rc = rescal_epoch_bucket(st, pos, neg, (long long)T, (int)bs, nb, rel->rows, d,
-                                             r->ws, r->rec, r->rec_n1);
-  }
   WStep wsync{};   // RESCAL with the in-front W step: synced back at the epoch's end
-  for (int k = 0; k < nb && !rc; ++k) {
-    const long long start = batches[k].first;
-    const int count = (int)batches[k].second;
-    int* gate = r->nviol + k;
-    if (hpos || dpos || tpos) {
-      rc = hpos   ? launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin,
-                                    gate, nullptr, nullptr)
-           : dpos ? launch_diag_pos(st, model, af, ent, rel, d, r->rec, r->rec_n1, start, count,
-                                    margin, gate)
-                  : launch_rot_pos(st, ent, rel, d, r->rec, r->rec_n1, start, count, margin, gate);
-      if (!rc) {
-        skge_table_t t[2] = {*ent, *rel};
-        t[0].gate = gate;
-        t[1].gate = gate;
-        const int ns[2] = {4 * count, count};
-        rc = skge_accum_apply(stream, t, 2, ns);
-      }
-    } else if (rpos) {
-      WStep wst{};   // set by the fused front (Linear): the W step rides the entity apply
-      rc = rep ? skge_rescal_pos_grad_mfma_ep(st, af, ent, rel, d, r->rec, r->rec_n1, (long long)T,
-                                              (int)bs, nb, k, margin, r->ws, gate, &wst)
-               : skge_rescal_pos_grad_mfma(st, af, ent, rel, d, pos + 3 * start, neg + 6 * start,
-                                           r->rec, r->rec_n1, start, count, margin, r->ws,
-                                           r->ws_bytes, gate);
-      if (!rc && wst.applied) {   // the row-grouped apply updated the entity rows and W
-        r->entity_apply = 1;
+  return capture_epoch(
+      r, who, st, model, d, batches,
+      [&]() -> int {
+        return launch_epoch_sample(st, trip, (long long)T, seed, epoch_key,
+                                   triple_set_view(set, set_capacity), ent->rows, ntries, r->rec,
+                                   r->rec_n1, smp);
+      },
+      [&]() -> int {
+        hipLaunchKernelGGL(k_pairs_of_epoch, build_grid(T), dim3(256), 0, st, r->rec, r->rec_n1,
+                           (long long)T, pos, neg, r->nviol, nb, rpos ? 1 : 0);
+        SKGE_CHECK_LAUNCH("pairs launch");
+        return rep ? rescal_epoch_bucket(st, pos, neg, (long long)T, bs, nb, rel->rows, d, r->ws,
+                                         r->rec, r->rec_n1)
+                   : SKGE_OK;
+      },
+      [&](int k, long long start, int count) -> int {
+        int* gate = r->nviol + k;
+        if (hpos || dpos || tpos) {
+          const int rc =
+              hpos   ? launch_hole_pos(st, af, ent, rel, d, r->rec, r->rec_n1, start, count, margin,
+                                       gate, nullptr, nullptr)
+              : dpos ? launch_diag_pos(st, model, af, ent, rel, d, r->rec, r->rec_n1, start, count,
+                                       margin, gate)
+                     : launch_rot_pos(st, ent, rel, d, r->rec, r->rec_n1, start, count, margin, gate);
+          return rc ? rc : apply_tables(stream, ent, rel, gate_word(gate), 4 * count, count);
+        }
+        if (!rpos)
+          return skge_pair_step(stream, model, af, ent, rel, d, pos + 6 * start, neg + 6 * start,
+                                2 * count, margin, r->ws, r->ws_bytes, gate);
+        WStep wst{};   // set by the fused front (Linear): the W step rides the entity apply
+        int rc = rep ? skge_rescal_pos_grad_mfma_ep(st, af, ent, rel, d, r->rec, r->rec_n1,
+                                                    (long long)T, bs, nb, k, margin, r->ws, gate, &wst)
+                     : skge_rescal_pos_grad_mfma(st, af, ent, rel, d, pos + 3 * start,
+                                                 neg + 6 * start, r->rec, r->rec_n1, start, count,
+                                                 margin, r->ws, r->ws_bytes, gate);
+        if (rc) return rc;
+        if (wst.applied) {   // the row-grouped apply updated the entity rows and W
+          r->entity_apply = 1;
+        } else {   // the entity table's apply (and W's, unless the dW kernel updated it)
+          skge_table_t te = *ent;
+          te.gate = gate;
+          const int ns = 4 * count;
+          rc = wst.part ? apply_with_wstep(st, &te, ns, wst) : skge_accum_apply(stream, &te, 1, &ns);
+        }
         if (wst.cur) wsync = wst;
-      } else if (!rc) {   // the entity table's apply (and W's, unless the dW kernel updated it)
-        skge_table_t te = *ent;
-        te.gate = gate;
-        const int ns = 4 * count;
-        rc = wst.part ? apply_with_wstep(st, &te, ns, wst) : skge_accum_apply(stream, &te, 1, &ns);
-        if (wst.cur) wsync = wst;
-      }
-    } else {
-      rc = skge_pair_step(stream, model, af, ent, rel, d, pos + 6 * start, neg + 6 * start,
-                          2 * count, margin, r->ws, r->ws_bytes, gate);
-    }
-  }
-  if (!rc && wsync.cur) rc = rescal_w_sync(st, wsync);
-  if (!rc) {
-    hipLaunchKernelGGL(k_pairs_epoch_end, dim3(1), dim3(256), 0, st, r->nviol, nb, nviol_total,
-                       epoch_key);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("epoch end launch failed");
-      rc = SKGE_EHIP;
-    }
-  }
-  return r->end_capture(st, rc) ? r.release() : nullptr;
+        return rc;
+      },
+      [&]() -> int {
+        if (wsync.cur)
+          if (int rc = rescal_w_sync(st, wsync)) return rc;
+        return launch_pairs_epoch_end(st, r->nviol, nb, nviol_total, epoch_key);
+      });
 }
 
 extern "C" skge_pair_runner_t* skge_pair_runner_create(
@@ -292,93 +264,62 @@ extern "C" skge_pair_runner_t* skge_pair_runner_create_multi(
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
     uint64_t seed, uint64_t* epoch_key, float margin, int ntries, int* nviol_total,
     const skge_sampler_t* smp, const skge_negatives_t* negs) {
-  if (!ent || !rel) return fail("pair runner: NULL table");
-  if (check_sampler(smp, "pair runner")) return nullptr;
-  if (!model_known(model)) return fail("pair runner: unknown model");
-  if (model == SKGE_COMPLEX && d % 2) return fail("pair runner: ComplEx needs an even d");
-  if (model == SKGE_ROTATE && d % 2) return fail("pair runner: RotatE needs an even d");
+  const char* who = "pair runner";
   int K = 0;
-  if (check_negatives(negs, smp, rel->rows, "pair runner", &K)) return nullptr;
   // pairs, their 3 ids and their 4 entity slots are indexed with ints
-  if (!check_runner_args("pair runner", trip, set, epoch_key, T, INT32_MAX / (4 * K), nbatches,
-                         set_capacity, 2 * T, ntries, stream))
+  if (!check_loop_model(who, ent, rel, smp, model, d) ||
+      check_negatives(negs, smp, rel->rows, who, &K) ||
+      !check_runner_args(who, trip, set, epoch_key, T, INT32_MAX / (4 * K), nbatches, set_capacity,
+                         2 * T, ntries, stream))
     return nullptr;
   hipStream_t st = as_stream(stream);
   const EpochBatches batches = epoch_batches(T, nbatches);
-  const int Pmax = (int)(K * batches.maxb);
-  if (ent->acc_touched && (long long)4 * Pmax > ent->touched_cap)
-    return fail("pair runner: entity accumulator needs 4 * K * batch_size = %lld touched slots, "
-                "has %lld", (long long)4 * Pmax, (long long)ent->touched_cap);
-  if (rel->acc_touched) {
-    const long long need = model == SKGE_RESCAL ? rel->rows : (long long)2 * Pmax;
-    if (need > rel->touched_cap)
-      return fail("pair runner: relation accumulator needs %lld touched slots, has %lld", need,
-                  (long long)rel->touched_cap);
-  }
-  const int nb = batches.size();
+  const int Pmax = (int)(K * batches.maxb), nb = batches.size();
+  if (!check_touched(who, ent, (long long)4 * Pmax, "entity") ||
+      !check_touched(who, rel, model == SKGE_RESCAL ? rel->rows : (long long)2 * Pmax, "relation"))
+    return nullptr;
   // TransE: the per-positive kernel from K = 10 on, where it was measured to
   // win (1.9x at K = 10, 2.2x at K = 20; at K = 2 the two forms tie and the
   // explicit pairs stay).  SKGE_TRANSE_PAIRS=1 forces the explicit
   // pairs, =0 the per-positive kernel, at any K.
-  const char* tp = getenv("SKGE_TRANSE_PAIRS");
   const bool tpos = (model == SKGE_TRANSE_L1 || model == SKGE_TRANSE_L2) &&
-                    (tp ? atoi(tp) == 0 : K >= TRANSE_POS_MIN_K) && ent->acc_replicas <= 1;
+                    env_flag("SKGE_TRANSE_PAIRS", K >= TRANSE_POS_MIN_K ? 0 : 1) == 0 &&
+                    ent->acc_replicas <= 1;
   std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
-  r->ws_bytes = skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d);
-  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
-  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
+  r->alloc_draw(T, K);
   if (!tpos) r->pairs = (int*)r->alloc((size_t)T * K * 6 * sizeof(int), false);
   r->nviol = (int*)r->alloc((size_t)nb * sizeof(int), true);
-  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
-  // an absent negative by a zero coefficient, which only discards FINITE stale values
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
-  if (!r->alloc_ok) return fail("pair runner: device allocation failed");
+  r->alloc_ws(skge_pair_step_workspace_bytes(model, Pmax, rel->rows, d));
   int* pos = r->pairs;
   int* neg = r->pairs ? r->pairs + (size_t)T * K * 3 : nullptr;
   const Negatives ng = negatives_of(negs);
-  const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
-    return fail("pair runner: HolE FFT twiddle table allocation failed");
-  if (!r->begin_capture(st)) return nullptr;
-  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
-                                     rel->rows, ntries, pos3, negK, smp, negs);
-  if (!rc) {
-    const int64_t blocks = std::max((int64_t)1, std::min((T * K + 255) / 256, (int64_t)4096));
-    hipLaunchKernelGGL(k_pairs_of_epoch_multi, dim3((unsigned)blocks), dim3(256), 0, st, pos3,
-                       negK, (long long)T, ng, pos, neg, r->nviol, nb);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("pairs launch failed");
-      rc = SKGE_EHIP;
-    }
-  }
-  for (int k = 0; k < nb && !rc; ++k) {
-    const int count = (int)batches[k].second;
-    int* gate = r->nviol + k;
-    if (tpos) {
-      rc = launch_transe_pos_multi(st, model == SKGE_TRANSE_L1, ent, rel, d, pos3, negK,
-                                   batches[k].first, count, ng, margin, gate);
-      if (!rc) {
-        skge_table_t t[2] = {*ent, *rel};
-        t[0].gate = gate;
-        t[1].gate = gate;
-        const int ns[2] = {(2 + K) * count, (1 + K) * count};
-        rc = skge_accum_apply(stream, t, 2, ns);
-      }
-      continue;
-    }
-    const size_t at = (size_t)3 * K * batches[k].first;
-    rc = skge_pair_step(stream, model, af, ent, rel, d, pos + at, neg + at, K * count, margin,
-                        r->ws, r->ws_bytes, gate);
-  }
-  if (!rc) {
-    hipLaunchKernelGGL(k_pairs_epoch_end, dim3(1), dim3(256), 0, st, r->nviol, nb, nviol_total,
-                       epoch_key);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("epoch end launch failed");
-      rc = SKGE_EHIP;
-    }
-  }
-  return r->end_capture(st, rc) ? r.release() : nullptr;
+  return capture_epoch(
+      r, who, st, model, d, batches,
+      [&]() -> int {
+        return launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key,
+                                         triple_set_view(set, set_capacity), ent->rows, rel->rows,
+                                         ntries, r->pos3, r->negK, smp, negs);
+      },
+      [&]() -> int {
+        hipLaunchKernelGGL(k_pairs_of_epoch_multi, build_grid(T * K), dim3(256), 0, st, r->pos3,
+                           r->negK, (long long)T, ng, pos, neg, r->nviol, nb);
+        SKGE_CHECK_LAUNCH("pairs launch");
+        return SKGE_OK;
+      },
+      [&](int k, long long start, int count) -> int {
+        int* gate = r->nviol + k;
+        if (tpos) {
+          const int rc = launch_transe_pos_multi(st, model == SKGE_TRANSE_L1, ent, rel, d, r->pos3,
+                                                 r->negK, start, count, ng, margin, gate);
+          return rc ? rc
+                    : apply_tables(stream, ent, rel, gate_word(gate), (2 + K) * count,
+                                   (1 + K) * count);
+        }
+        const size_t at = (size_t)3 * K * start;
+        return skge_pair_step(stream, model, af, ent, rel, d, pos + at, neg + at, K * count, margin,
+                              r->ws, r->ws_bytes, gate);
+      },
+      [&]() -> int { return launch_pairs_epoch_end(st, r->nviol, nb, nviol_total, epoch_key); });
 }
 
 // The self-adversarial loop (TransE-L1 / -L2, RotatE): the
@@ -391,45 +332,37 @@ extern "C" skge_pair_runner_t* skge_sadv_runner_create(
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches,
     uint64_t seed, uint64_t* epoch_key, float gamma, float alpha, int ntries, float* loss_total,
     const skge_sampler_t* smp, const skge_negatives_t* negs) {
-  if (check_sampler(smp, "sadv runner")) return nullptr;
+  const char* who = "sadv runner";
   int K = 0;
-  if (check_sadv("sadv runner", model, ent, rel, d, negs, smp, gamma, alpha, &K)) return nullptr;
   // a batch's 2 + K entity slots per positive are indexed with ints
-  if (!check_runner_args("sadv runner", trip, set, epoch_key, T, INT32_MAX / (2 + K), nbatches,
-                         set_capacity, 2 * T, ntries, stream))
+  if (check_sampler(smp, who) ||
+      check_sadv(who, model, ent, rel, d, negs, smp, gamma, alpha, &K) ||
+      !check_runner_args(who, trip, set, epoch_key, T, INT32_MAX / (2 + K), nbatches, set_capacity,
+                         2 * T, ntries, stream))
     return nullptr;
   hipStream_t st = as_stream(stream);
   const EpochBatches batches = epoch_batches(T, nbatches);
-  if (ent->acc_touched && (long long)(2 + K) * batches.maxb > ent->touched_cap)
-    return fail("sadv runner: entity accumulator needs (2 + K) * batch_size = %lld touched slots, "
-                "has %lld", (long long)(2 + K) * batches.maxb, (long long)ent->touched_cap);
-  if (rel->acc_touched && (long long)(1 + K) * batches.maxb > rel->touched_cap)
-    return fail("sadv runner: relation accumulator needs (1 + K) * batch_size = %lld touched "
-                "slots, has %lld", (long long)(1 + K) * batches.maxb, (long long)rel->touched_cap);
-  const int nb = batches.size();
+  if (!check_touched(who, ent, (long long)(2 + K) * batches.maxb, "entity") ||
+      !check_touched(who, rel, (long long)(1 + K) * batches.maxb, "relation"))
+    return nullptr;
   std::unique_ptr<skge_pair_runner_t> r(new skge_pair_runner_t());
-  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
-  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
-  if (!r->alloc_ok) return fail("sadv runner: device allocation failed");
+  r->alloc_draw(T, K);
   const Negatives ng = negatives_of(negs);
-  const TripleSet ts = triple_set_view(set, set_capacity);
-  if (!r->begin_capture(st)) return nullptr;
-  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
-                                     rel->rows, ntries, pos3, negK, smp, negs);
-  for (int k = 0; k < nb && !rc; ++k) {
-    const int count = (int)batches[k].second;
-    rc = launch_sadv_pos(st, model, ent, rel, d, pos3, negK, batches[k].first, count, ng, gamma,
-                         alpha, nullptr, nullptr, nullptr, loss_total);
-    if (!rc) {
-      skge_table_t t[2] = {*ent, *rel};
-      t[0].gate = nullptr;
-      t[1].gate = nullptr;
-      const int ns[2] = {(2 + K) * count, (1 + K) * count};
-      rc = skge_accum_apply(stream, t, 2, ns);
-    }
-  }
-  if (!rc) rc = skge_epoch_advance(stream, epoch_key);
-  return r->end_capture(st, rc) ? r.release() : nullptr;
+  return capture_epoch(
+      r, who, st, model, d, batches,
+      [&]() -> int {
+        return launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key,
+                                         triple_set_view(set, set_capacity), ent->rows, rel->rows,
+                                         ntries, r->pos3, r->negK, smp, negs);
+      },
+      []() -> int { return SKGE_OK; },   // k_sadv_pos reads the records
+      [&](int, long long start, int count) -> int {
+        const int rc = launch_sadv_pos(st, model, ent, rel, d, r->pos3, r->negK, start, count, ng,
+                                       gamma, alpha, nullptr, nullptr, nullptr, loss_total);
+        return rc ? rc
+                  : apply_tables(stream, ent, rel, gate_none(), (2 + K) * count, (1 + K) * count);
+      },
+      [&]() -> int { return skge_epoch_advance(stream, epoch_key); });
 }
 
 extern "C" int skge_epoch_sample_multi(void* stream, const int* trip, int64_t T, const void* set,

@@ -23,12 +23,7 @@
 // positive and both of its corruptions in one wave straight from the records
 // (k_hole_logistic_pos below): the same triples, contributions and counts,
 // 5 forward + 5 inverse transforms per positive instead of 9 + 9.
-#include <cstdlib>
-#include <vector>
-
-#include "skge_graph_runner.h"
-#include "skge_hole_fft.h"
-#include "skge_sampler.h"
+#include "skge_loop_runner.h"
 
 namespace skge {
 
@@ -227,97 +222,80 @@ static int launch_hole_logistic_pos(hipStream_t st, const skge_table_t* ent,
 
 using namespace skge;
 
-struct skge_triple_runner : GraphRunnerCore {
-  int4* rec = nullptr;
-  int* rec_n1 = nullptr;
+struct skge_triple_runner : LoopRunner {
   int* trip = nullptr;    // the epoch's labelled triples [3T][3], batch b's at 9 * start_b
   float* ys = nullptr;    // [3T]
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
 };
+
+// the shared refusals, then the models without a logistic loss
+static bool check_triple_model(const char* who, const skge_table_t* ent, const skge_table_t* rel,
+                               const skge_sampler_t* smp, int model, int d) {
+  if (!check_loop_model(who, ent, rel, smp, model, d)) return false;
+  if (model == SKGE_ROTATE)
+    set_error("%s: RotatE is not served here (its scores are <= 0: no logistic loss)", who);
+  else if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
+    set_error("%s: logistic loss is defined for HolE and RESCAL only (and DistMult and ComplEx)",
+              who);
+  else return true;
+  return false;
+}
+
+// the explicit triples' slot map (skge_triple_grad) for a batch of n: 2 entity slots
+// per triple; a relation slot per triple (HolE) or per relation (RESCAL's W)
+static bool check_triple_touched(const char* who, int model, const skge_table_t* ent,
+                                 const skge_table_t* rel, long long n) {
+  return check_touched(who, ent, 2 * n, "entity") &&
+         (model == SKGE_RESCAL ? check_touched(who, rel, rel->rows, "W")
+                               : check_touched(who, rel, n, "relation"));
+}
 
 extern "C" skge_triple_runner_t* skge_triple_runner_create_ex(
     void* stream, int model, const skge_table_t* ent, const skge_table_t* rel, int d,
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
     uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp) {
-  if (!ent || !rel) return fail("triple runner: NULL table");
-  if (check_sampler(smp, "triple runner")) return nullptr;
-  if (model == SKGE_ROTATE)
-    return fail("triple runner: RotatE is not served here (its scores are <= 0: no logistic loss)");
-  if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
-    return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
-                "and ComplEx)");
-  if (model == SKGE_COMPLEX && d % 2) return fail("triple runner: ComplEx needs an even d");
-  if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / 3, nbatches,
-                         set_capacity, 2 * T, ntries, stream))
+  const char* who = "triple runner";
+  if (!check_triple_model(who, ent, rel, smp, model, d) ||
+      !check_runner_args(who, trip, set, epoch_key, T, INT32_MAX / 3, nbatches, set_capacity, 2 * T,
+                         ntries, stream))
     return nullptr;
   hipStream_t st = as_stream(stream);
   const EpochBatches batches = epoch_batches(T, nbatches);
-  const int64_t bs = batches.bs, maxb = batches.maxb;
-  // the explicit triples' slot map (skge_triple_grad): 2 entity slots per
-  // triple; a relation slot per triple (HolE) or per relation (RESCAL's W)
-  if (ent->acc_touched && 6 * maxb > ent->touched_cap)
-    return fail("triple runner: entity accumulator needs 6 * batch_size = %lld touched slots",
-                (long long)(6 * maxb));
-  if (rel->acc_touched) {
-    const long long need = model == SKGE_RESCAL ? rel->rows : 3 * maxb;
-    if (need > rel->touched_cap)
-      return fail(model == SKGE_RESCAL
-                      ? "triple runner: W accumulator needs rel->rows = %lld touched slots"
-                      : "triple runner: relation accumulator needs 3 * batch_size = %lld touched "
-                        "slots",
-                  need);
-  }
+  const int Tmax = (int)(3 * batches.maxb);
+  if (!check_triple_touched(who, model, ent, rel, Tmax)) return nullptr;
   // HolE in the wave FFT's range: a positive and both corruptions in one wave
   // straight from the records (SKGE_HOLE_TRIPLES=1 keeps the explicit triples)
-  const char* ht = getenv("SKGE_HOLE_TRIPLES");
-  const bool hpos = model == SKGE_HOLE && !(ht && atoi(ht)) && hole_logistic_pos_ok(ent, rel, d);
-  const int nb = batches.size();
-  const int Tmax = (int)(3 * maxb);
+  const bool hpos = model == SKGE_HOLE && !env_flag("SKGE_HOLE_TRIPLES", 0) &&
+                    hole_logistic_pos_ok(ent, rel, d);
   std::unique_ptr<skge_triple_runner_t> r(new skge_triple_runner_t());
-  r->ws_bytes = hpos ? 0 : skge_triple_step_workspace_bytes(model, Tmax, rel->rows, d);
-  r->rec = (int4*)r->alloc((size_t)T * sizeof(int4), false);
-  r->rec_n1 = (int*)r->alloc((size_t)T * sizeof(int), false);
+  r->alloc_draw(T, 0);
   if (!hpos) {
     r->trip = (int*)r->alloc((size_t)T * 9 * sizeof(int), false);
     r->ys = (float*)r->alloc((size_t)T * 3 * sizeof(float), false);
   }
-  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
-  // an absent negative by a zero coefficient, which only discards FINITE stale values
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
-  if (!r->alloc_ok) return fail("triple runner: device allocation failed");
-  const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
-    return fail("triple runner: HolE FFT twiddle table allocation failed");
-  if (!r->begin_capture(st)) return nullptr;
-  int rc = launch_epoch_sample(st, trip, (long long)T, seed, epoch_key, ts, ent->rows, ntries,
-                               r->rec, r->rec_n1, smp);
-  if (!rc && !hpos) {
-    const int64_t blocks = std::max((int64_t)1, std::min((T + 255) / 256, (int64_t)4096));
-    hipLaunchKernelGGL(k_triples_of_epoch, dim3((unsigned)blocks), dim3(256), 0, st, r->rec,
-                       r->rec_n1, (long long)T, (long long)bs, r->trip, r->ys);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("triples launch failed");
-      rc = SKGE_EHIP;
-    }
-  }
-  for (int k = 0; k < nb && !rc; ++k) {
-    const long long start = batches[k].first;
-    const int count = (int)batches[k].second;
-    if (hpos) {
-      rc = launch_hole_logistic_pos(st, ent, rel, d, r->rec, r->rec_n1, start, count, loss_total);
-      if (!rc) {
-        const skge_table_t t[2] = {*ent, *rel};
-        const int ns[2] = {4 * count, count};
-        rc = skge_accum_apply(stream, t, 2, ns);
-      }
-    } else {
-      rc = skge_triple_step(stream, model, ent, rel, d, r->trip + 9 * start, r->ys + 3 * start,
-                            3 * count, r->ws, r->ws_bytes, loss_total);
-    }
-  }
-  if (!rc) rc = skge_epoch_advance(stream, epoch_key);
-  return r->end_capture(st, rc) ? r.release() : nullptr;
+  r->alloc_ws(hpos ? 0 : skge_triple_step_workspace_bytes(model, Tmax, rel->rows, d));
+  return capture_epoch(
+      r, who, st, model, d, batches,
+      [&]() -> int {
+        return launch_epoch_sample(st, trip, (long long)T, seed, epoch_key,
+                                   triple_set_view(set, set_capacity), ent->rows, ntries, r->rec,
+                                   r->rec_n1, smp);
+      },
+      [&]() -> int {
+        if (hpos) return SKGE_OK;   // k_hole_logistic_pos reads the records
+        hipLaunchKernelGGL(k_triples_of_epoch, build_grid(T), dim3(256), 0, st, r->rec, r->rec_n1,
+                           (long long)T, (long long)batches.bs, r->trip, r->ys);
+        SKGE_CHECK_LAUNCH("triples launch");
+        return SKGE_OK;
+      },
+      [&](int, long long start, int count) -> int {
+        if (!hpos)
+          return skge_triple_step(stream, model, ent, rel, d, r->trip + 9 * start,
+                                  r->ys + 3 * start, 3 * count, r->ws, r->ws_bytes, loss_total);
+        const int rc = launch_hole_logistic_pos(st, ent, rel, d, r->rec, r->rec_n1, start, count,
+                                                loss_total);
+        return rc ? rc : apply_tables(stream, ent, rel, gate_callers(), 4 * count, count);
+      },
+      [&]() -> int { return skge_epoch_advance(stream, epoch_key); });
 }
 
 extern "C" skge_triple_runner_t* skge_triple_runner_create(
@@ -338,67 +316,43 @@ extern "C" skge_triple_runner_t* skge_triple_runner_create_multi(
     const int* trip, int64_t T, const void* set, int64_t set_capacity, int nbatches, uint64_t seed,
     uint64_t* epoch_key, int ntries, float* loss_total, const skge_sampler_t* smp,
     const skge_negatives_t* negs) {
-  if (!ent || !rel) return fail("triple runner: NULL table");
-  if (check_sampler(smp, "triple runner")) return nullptr;
-  if (model == SKGE_ROTATE)
-    return fail("triple runner: RotatE is not served here (its scores are <= 0: no logistic loss)");
-  if (model != SKGE_HOLE && model != SKGE_RESCAL && !model_diag(model))
-    return fail("triple runner: logistic loss is defined for HolE and RESCAL only (and DistMult "
-                "and ComplEx)");
-  if (model == SKGE_COMPLEX && d % 2) return fail("triple runner: ComplEx needs an even d");
+  const char* who = "triple runner";
   int K = 0;
-  if (check_negatives(negs, smp, rel->rows, "triple runner", &K)) return nullptr;
   // triples, their 3 ids and their 2 entity slots are indexed with ints
-  if (!check_runner_args("triple runner", trip, set, epoch_key, T, INT32_MAX / (3 * (1 + K)),
-                         nbatches, set_capacity, 2 * T, ntries, stream))
+  if (!check_triple_model(who, ent, rel, smp, model, d) ||
+      check_negatives(negs, smp, rel->rows, who, &K) ||
+      !check_runner_args(who, trip, set, epoch_key, T, INT32_MAX / (3 * (1 + K)), nbatches,
+                         set_capacity, 2 * T, ntries, stream))
     return nullptr;
   hipStream_t st = as_stream(stream);
   const EpochBatches batches = epoch_batches(T, nbatches);
-  const int64_t bs = batches.bs, maxb = batches.maxb;
-  const long long Tmax = (long long)(1 + K) * maxb;
-  if (ent->acc_touched && 2 * Tmax > ent->touched_cap)
-    return fail("triple runner: entity accumulator needs 2 * (1 + K) * batch_size = %lld touched "
-                "slots, has %lld", 2 * Tmax, (long long)ent->touched_cap);
-  if (rel->acc_touched) {
-    const long long need = model == SKGE_RESCAL ? rel->rows : Tmax;
-    if (need > rel->touched_cap)
-      return fail("triple runner: relation accumulator needs %lld touched slots, has %lld", need,
-                  (long long)rel->touched_cap);
-  }
-  const int nb = batches.size();
+  const int Tmax = (int)((1 + K) * batches.maxb);
+  if (!check_triple_touched(who, model, ent, rel, Tmax)) return nullptr;
   std::unique_ptr<skge_triple_runner_t> r(new skge_triple_runner_t());
-  r->ws_bytes = skge_triple_step_workspace_bytes(model, (int)Tmax, rel->rows, d);
-  int* pos3 = (int*)r->alloc((size_t)T * 3 * sizeof(int), false);
-  int* negK = (int*)r->alloc((size_t)T * K * sizeof(int), false);
+  r->alloc_draw(T, K);
   r->trip = (int*)r->alloc((size_t)T * (1 + K) * 3 * sizeof(int), false);
   r->ys = (float*)r->alloc((size_t)T * (1 + K) * sizeof(float), false);
-  // zero-filled once: RESCAL's kernels multiply the WE / EW rows and partial scores of
-  // an absent negative by a zero coefficient, which only discards FINITE stale values
-  if (r->ws_bytes) r->ws = r->alloc(r->ws_bytes, true);
-  if (!r->alloc_ok) return fail("triple runner: device allocation failed");
-  const TripleSet ts = triple_set_view(set, set_capacity);
-  if (model == SKGE_HOLE && hole_use_fft(d) && !hole_fft_table(d))   // before the capture
-    return fail("triple runner: HolE FFT twiddle table allocation failed");
-  if (!r->begin_capture(st)) return nullptr;
-  int rc = launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key, ts, ent->rows,
-                                     rel->rows, ntries, pos3, negK, smp, negs);
-  if (!rc) {
-    const Negatives ng = negatives_of(negs);
-    const int64_t blocks = std::max((int64_t)1, std::min((T * K + 255) / 256, (int64_t)4096));
-    hipLaunchKernelGGL(k_triples_of_epoch_multi, dim3((unsigned)blocks), dim3(256), 0, st, pos3,
-                       negK, (long long)T, (long long)bs, ng, r->trip, r->ys);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("triples launch failed");
-      rc = SKGE_EHIP;
-    }
-  }
-  for (int k = 0; k < nb && !rc; ++k) {
-    const size_t at = (size_t)(1 + K) * batches[k].first;
-    rc = skge_triple_step(stream, model, ent, rel, d, r->trip + 3 * at, r->ys + at,
-                          (1 + K) * (int)batches[k].second, r->ws, r->ws_bytes, loss_total);
-  }
-  if (!rc) rc = skge_epoch_advance(stream, epoch_key);
-  return r->end_capture(st, rc) ? r.release() : nullptr;
+  r->alloc_ws(skge_triple_step_workspace_bytes(model, Tmax, rel->rows, d));
+  return capture_epoch(
+      r, who, st, model, d, batches,
+      [&]() -> int {
+        return launch_epoch_sample_multi(st, trip, (long long)T, seed, epoch_key,
+                                         triple_set_view(set, set_capacity), ent->rows, rel->rows,
+                                         ntries, r->pos3, r->negK, smp, negs);
+      },
+      [&]() -> int {
+        hipLaunchKernelGGL(k_triples_of_epoch_multi, build_grid(T * K), dim3(256), 0, st, r->pos3,
+                           r->negK, (long long)T, (long long)batches.bs, negatives_of(negs),
+                           r->trip, r->ys);
+        SKGE_CHECK_LAUNCH("triples launch");
+        return SKGE_OK;
+      },
+      [&](int, long long start, int count) -> int {
+        const size_t at = (size_t)(1 + K) * start;
+        return skge_triple_step(stream, model, ent, rel, d, r->trip + 3 * at, r->ys + at,
+                                (1 + K) * count, r->ws, r->ws_bytes, loss_total);
+      },
+      [&]() -> int { return skge_epoch_advance(stream, epoch_key); });
 }
 
 extern "C" int skge_triple_runner_run(skge_triple_runner_t* r, void* stream, int nepochs) {

@@ -298,6 +298,15 @@ class _Runner(object):
         self._abi, self.handle = prefix, h
         self.nlaunches = getattr(lib, prefix + "_nlaunches")(h)
 
+    def _create_loop(self, prefix, *args):
+        """The pair and logistic loops' create: the (1, [0, 1]) entry point or,
+        with any other (n, modes), the _multi one, which takes them as one
+        more argument."""
+        if self._neg is None:
+            self._create(prefix, *args, create=prefix + "_create_ex")
+        else:
+            self._create(prefix, *args, self._neg, create=prefix + "_create_multi")
+
     def _pad_in(self):
         pass
 
@@ -702,17 +711,9 @@ class PairLoopRunner(_Runner):
         P = self.K * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("pairwise", updaters, slots=model._pair_slots(P))
         self._hold_captured(updaters)
-        if self._neg is not None:
-            # n negatives per positive over any modes: K pairs per positive,
-            # every model on its explicit-pair kernels
-            self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te,
-                         self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
-                         L.ptr(self.nviol_total), self._smp, self._neg,
-                         create="skge_pair_runner_create_multi")
-        else:
-            self._create("skge_pair_runner", model._kernel_model(), model._af_code(), self.te,
-                         self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
-                         L.ptr(self.nviol_total), self._smp, create="skge_pair_runner_create_ex")
+        self._create_loop("skge_pair_runner", model._kernel_model(), model._af_code(), self.te,
+                          self.tr, model.d, *self._epoch_args(), float(model.margin), self.ntries,
+                          L.ptr(self.nviol_total), self._smp)
         # how the captured batches update the entity rows: "scatter" (sums by
         # the gradient launch, then an apply launch) or "rows" (RESCAL's
         # row-grouped apply, k_rescal_fold)
@@ -757,14 +758,8 @@ class LogisticLoopRunner(_Runner):
         T3 = (1 + self.K) * max(batch_sizes(kg.T, nbatches))
         self.te, self.tr = model._tables("logistic", updaters, slots=model._triple_slots(T3))
         self._hold_captured(updaters)
-        if self._neg is not None:   # (1 + K) triples per positive, explicit-triple kernels
-            self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
-                         *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp,
-                         self._neg, create="skge_triple_runner_create_multi")
-            return
-        self._create("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
-                     *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp,
-                     create="skge_triple_runner_create_ex")
+        self._create_loop("skge_triple_runner", model._kernel_model(), self.te, self.tr, model.d,
+                          *self._epoch_args(), self.ntries, L.ptr(self.loss_total), self._smp)
 
 
 class SadvLoopRunner(_Runner):
@@ -799,20 +794,26 @@ class SadvLoopRunner(_Runner):
                      create="skge_sadv_runner_create")
 
 
-def sadv_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
-    """SelfAdversarialTrainer.fit with device_loop=True: per epoch _pre_epoch,
-    one graph replay, the runner's error word, then the post_epoch callbacks
-    (which read the epoch's loss through trainer.loss)."""
+def _loss_loop_optim(runner_cls, trainer, xs, ntries, sampler, negatives):
+    """The fit of a trainer whose device loop adds the epoch's loss into
+    trainer._loss_dev: the runner, then _fit_epochs."""
     model = trainer.model
     dev = model.device
     if trainer._loss_dev is None:
         trainer._loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
     kg = DeviceKG(xs, dev)
-    runner = SadvLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
-                            ntries=trainer.ntries if ntries is None else ntries,
-                            loss_total=trainer._loss_dev, sampler=sampler, negatives=negatives)
+    runner = runner_cls(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
+                        ntries=trainer.ntries if ntries is None else ntries,
+                        loss_total=trainer._loss_dev, sampler=sampler, negatives=negatives)
     trainer.batch_size = kg.T // trainer.nbatches
     _fit_epochs(trainer, runner)
+
+
+def sadv_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDOM, negatives=None):
+    """SelfAdversarialTrainer.fit with device_loop=True: per epoch _pre_epoch,
+    one graph replay, the runner's error word, then the post_epoch callbacks
+    (which read the epoch's loss through trainer.loss)."""
+    _loss_loop_optim(SadvLoopRunner, trainer, xs, ntries, sampler, negatives)
 
 
 def _fit_epochs(trainer, runner):
@@ -838,17 +839,7 @@ def logistic_device_optim(trainer, xs, ntries=None, sampler=L.SKGE_SAMPLER_RANDO
     read the epoch's loss through trainer.loss as on the per-batch path).
     sampler: the kind device_sampler_args reported; negatives: its (n, modes,
     rel_range) (None: (1, [0, 1]))."""
-    model = trainer.model
-    dev = model.device
-    if trainer._loss_dev is None:
-        trainer._loss_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-    kg = DeviceKG(xs, dev)
-    runner = LogisticLoopRunner(model, trainer._updaters, kg, trainer.nbatches, seed=trainer.seed,
-                                ntries=trainer.ntries if ntries is None else ntries,
-                                loss_total=trainer._loss_dev, sampler=sampler,
-                                negatives=negatives)
-    trainer.batch_size = kg.T // trainer.nbatches
-    _fit_epochs(trainer, runner)
+    _loss_loop_optim(LogisticLoopRunner, trainer, xs, ntries, sampler, negatives)
 
 
 def epoch_records(kg, n_ent, seed, epoch_key, ntries=100, stream=None,
